@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mrays/s of the wavefront path-tracing hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 With N > 1 and no launcher in the environment the parent starts the N ranks itself (torch.distributed.run as a
 child process, before anything here has touched a GPU) and relays rank 0's JSON line; under a launcher
@@ -27,6 +27,10 @@ once.  The same workload at the reference's queue size is measured too (config.r
 config.steady_state: the same kernels with the queue kept full by top-ups for as long as the measurement lasts (the
 reference's viewer never stops: main.cpp:164-170) -- no thin iterations at the end of a render.  Reported beside the
 metric, never as it.
+
+--dump-outputs DIR: after the timed steps, the accumulation buffer the last of them left (what tyr_render's caller reads; rank 0's
+combined frame for N > 1) goes to DIR/accum.npy -- see dump_outputs.  The inputs are seeded: the same arguments render the
+same job, so two builds can be compared output for output.
 
 Mrays/s = (extend rays + shadow rays traced by all ranks) / wall time.  config.in_tree_Mrays/s
 is the same with only the rays that pass the root box (three primary rays in four miss the tree on c3 and cost one box
@@ -98,7 +102,37 @@ def parse_args(argv=None):
     ap.add_argument("--save-pmc", default="", help="write the live PMC counters to this JSON file (copied to profiles/pmc_<workload>.json, the fallback when rocprofv3 cannot run beside the bench)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--tune", action="append", default=[], help="launch-shape knob of tyr_set_tuning, e.g. --tune refill_min_idle=8 (never changes results)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the accumulation buffer of the last one to DIR/accum.npy (float32, H*W x 4; above 64 MB a fixed sample of its pixels)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6  # all files of --dump-outputs together
+DUMP_SEED = 20240917  # the pixel sample of a frame above the limit: the same for every run and every build
+
+
+def dump_outputs(out_dir: str, accum, limit_bytes: int = DUMP_LIMIT_BYTES) -> list:
+    """--dump-outputs: the accumulation buffer (H*W pixels x r, g, b radiance sums and the count of finished paths, float32) as
+    out_dir/accum.npy.  Above limit_bytes, a fixed seeded sample of its pixels instead, in pixel order, with their indices
+    (float64, exact) in out_dir/accum_pixels.npy.  Returns the names written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.ascontiguousarray(accum, dtype=np.float32).reshape(-1, 4)
+    header = 128  # an .npy header
+    files = {"accum": a}
+    if a.nbytes + header > limit_bytes:
+        n = (limit_bytes - 2 * header) // (a.itemsize * 4 + 8)  # a sampled pixel: four floats + its float64 index
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], size=n, replace=False))
+        files = {"accum": a[idx], "accum_pixels": idx.astype(np.float64)}
+    stale = os.path.join(out_dir, "accum_pixels.npy")
+    if "accum_pixels" not in files and os.path.exists(stale):
+        os.remove(stale)  # (from an earlier, larger frame in the same directory)
+    for name, v in files.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
+    return sorted(files)
 
 def free_port() -> int:
     with socket.socket() as s:
@@ -222,9 +256,10 @@ def main():
         v = sorted(v)
         return v[min(len(v) - 1, int(round(p * (len(v) - 1))))] if v else None
 
-    def measure(N, steps, warmup, spp, shard, ranks, sc=sc, spread_blocks=0):
+    def measure(N, steps, warmup, spp, shard, ranks, sc=sc, spread_blocks=0, keep_output=False):
         """one renderer at queue size N: untimed counting render, warm-up, `steps` timed renders (ranks > 1: + the combine);
-        spread_blocks: that many blocks of twenty more renders BEHIND the timed region, each render timed by itself"""
+        spread_blocks: that many blocks of twenty more renders BEHIND the timed region, each render timed by itself;
+        keep_output: rank 0 copies the frame the last timed render left to the host (after the timed region)"""
         # the caller owns blit_buffer (main.cpp:129-130): a torch tensor here (device memory is torch's job in this script)
         accum = torch.zeros(H * W * 4, dtype=torch.float32, device=dev)
         frame = torch.zeros(H * W * 4, dtype=torch.float32, device=dev) if (ranks > 1 and rank == 0) else None
@@ -368,6 +403,7 @@ def main():
             # sanity of the combined frame: every pixel has exactly spp completed paths
             a = (frame if frame is not None else accum).view(H * W, 4)[:, 3]
             assert float(a.min()) == float(a.max()) == float(spp), (float(a.min()), float(a.max()), spp)
+        output = (frame if frame is not None else accum).cpu().numpy() if keep_output and rank == 0 else None
         # what the last timed render left in the accumulation buffer (every step resets it and renders the same job): the sums the committed
         # oracle file holds for this job are compared with it below (oracle_counters_check: oracle_radiance_match)
         radiance = [float(x) for x in accum.view(H * W, 4)[:, :3].to(torch.float64).sum(0).tolist()] if ranks == 1 else None
@@ -395,9 +431,9 @@ def main():
             comm = True if native_used else None  # (only its truth value is reported below)
         r.close()
         per_render = {k: round(v["ms"] / warmup, 3) for k, v in tm_all.items()} if tm_all is not None else {k: round(v["ms"] / steps, 3) for k, v in tm.items()}
-        return {"native_combine": bool(comm is not None and native_ok[0]), "comm_info": comm_info, "ext": ext, "shd": shd, "survivors": survivors, "ext_all": ext_all, "shd_all": shd_all, "dt_all": dt_all, "iters": iters, "tm": tm, "kernel_ms_per_render": per_render, "counter_deltas": deltas, "upload": upload, "step_ms": step_ms, "spread": spread, "radiance_sum_rgb": radiance, **visits}
+        return {"native_combine": bool(comm is not None and native_ok[0]), "comm_info": comm_info, "ext": ext, "shd": shd, "survivors": survivors, "ext_all": ext_all, "shd_all": shd_all, "dt_all": dt_all, "iters": iters, "tm": tm, "kernel_ms_per_render": per_render, "counter_deltas": deltas, "upload": upload, "step_ms": step_ms, "spread": spread, "radiance_sum_rgb": radiance, "output": output, **visits}
 
-    m = measure(N, args.steps, args.warmup, spp_total, shard, world, spread_blocks=0 if (world > 1 or args.no_spread) else 10)
+    m = measure(N, args.steps, args.warmup, spp_total, shard, world, spread_blocks=0 if (world > 1 or args.no_spread) else 10, keep_output=bool(args.dump_outputs))
     # the secondary workload (NOT the metric): the same scene and job from where the room's opening fills the frame
     framed = None
     if world == 1 and args.workload == "c3" and not args.no_framed and (W, H, spp_total) == (1920, 1080, 8):
@@ -539,6 +575,8 @@ def main():
             }
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sc, W, H, N, args.cpu_iterations, sc.triangle_materials, spp_total)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, m["output"])
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

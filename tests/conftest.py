@@ -1,12 +1,13 @@
 """Shared fixtures.
 
-`-m "not gpu"`: oracle vs golden vectors / the reference-header harness, host logic,
-C-ABI symbol checks -- no GPU, no /root/reference at run time (the harness .so is prebuilt).
+`-m "not gpu"`: oracle vs golden vectors / the reference-header harness's answers, host logic,
+C-ABI symbol checks -- no GPU, and nothing outside the repository (see `ref_answers`).
 `-m gpu`: parity of the HIP path (through the C ABI) against the oracle on an MI355X.
 """
 from __future__ import annotations
 
 import functools
+import hashlib
 import json
 import os
 import sys
@@ -62,12 +63,73 @@ def orc():
     return pyorc
 
 
+# The reference-header harness (oracle/_ref/libref_traverse.so, `make -C oracle ref`) can only be built where the
+# reference's sources are.  The tests that consult it therefore go through `ref_answers`: where the harness is built
+# they ask it live and hold the record to what it says; everywhere else they get what it answered to the same inputs,
+# recorded in tests/golden/ref_answers.npz.  With the harness built, TYR_RECORD_REF_ANSWERS=1 rewrites the record of
+# every test that runs (python -m pytest -m "not gpu" tests).
+REF_ANSWERS = os.path.join(GOLDEN, "ref_answers.npz")
+
+
+def _digest(arrays) -> str:
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(repr(a.shape).encode())
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def _same(a: np.ndarray, b: np.ndarray) -> bool:
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+class RefAnswers:
+    """answers(key, ask, inputs, needs) -> {name: array}: `ask(harness)` computes them live; `inputs` are the arrays they
+    depend on (their digest is recorded with them, so a record is never replayed for other inputs); `needs` names the
+    harness exports `ask` calls (an older harness without them is not asked)"""
+
+    def __init__(self, lib):
+        self.lib = lib
+        self.recording = os.environ.get("TYR_RECORD_REF_ANSWERS") == "1"
+        self.recorded = {}
+        if os.path.exists(REF_ANSWERS):
+            with np.load(REF_ANSWERS) as z:
+                self.recorded = dict(z)
+        self.new = {}
+
+    def __call__(self, key, ask, inputs=(), needs=()):
+        digest = _digest(inputs)
+        live = self.lib is not None and all(hasattr(self.lib, n) for n in needs)
+        got = {k: np.asarray(v) for k, v in ask(self.lib).items()} if live else None
+        if self.recording:
+            if not live:
+                pytest.fail(f"{key}: recording needs the reference harness (make -C oracle ref)")
+            self.new[key] = {"inputs": np.array(digest), **got}
+            return got
+        rec = {k.split("/", 1)[1]: v for k, v in self.recorded.items() if k.split("/", 1)[0] == key}
+        assert rec, f"{key}: no answers of the reference harness recorded in {os.path.relpath(REF_ANSWERS, ROOT)}"
+        assert str(rec.pop("inputs")) == digest, f"{key}: the inputs differ from those the reference's answers were recorded for"
+        if live:
+            assert rec.keys() == got.keys() and all(_same(rec[k], got[k]) for k in got), f"{key}: the recorded answers are not what the reference harness says now"
+            return got
+        return rec
+
+    def save(self):
+        if not self.new:
+            return
+        keep = {k: v for k, v in self.recorded.items() if k.split("/", 1)[0] not in self.new}
+        keep.update({f"{key}/{name}": v for key, d in self.new.items() for name, v in d.items()})
+        np.savez_compressed(REF_ANSWERS, **dict(sorted(keep.items())))
+
+
 @pytest.fixture(scope="session")
-def ref(orc):
-    r = orc.ref()
-    if r is None:
-        pytest.skip("oracle/_ref/libref_traverse.so not built (needs /root/reference; run `make -C oracle ref`)")
-    return r
+def ref_answers(orc):
+    r = RefAnswers(orc.ref())
+    yield r
+    if r.recording:
+        r.save()
 
 
 @pytest.fixture(scope="session")

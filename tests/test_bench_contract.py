@@ -169,6 +169,33 @@ def test_nominal_step_fraction_and_gather_ceiling():
     assert r5["bound"] == "hbm" and r5["unit"] == "GB/s" and "r06_whatif_ray_order_c5" in r5["bound_note"]
 
 
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample_within_the_limit(tmp_path):
+    """--dump-outputs: the whole accumulation buffer while it fits, else the same seeded sample of its pixels every time, with
+    their indices; never more than the limit in all"""
+    import numpy as np
+
+    acc = np.arange(64 * 48 * 4, dtype=np.float32).reshape(-1, 4)
+    assert bench.dump_outputs(str(tmp_path / "a"), acc) == ["accum"]
+    got = np.load(tmp_path / "a" / "accum.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, acc)
+    limit = 20000
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), acc, limit_bytes=limit) == ["accum", "accum_pixels"]
+    files = [tmp_path / "b" / "accum.npy", tmp_path / "b" / "accum_pixels.npy"]
+    assert sum(os.path.getsize(f) for f in files) <= limit
+    smp, idx = (np.load(f) for f in files)
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and smp.shape == (idx.shape[0], 4) and idx.shape[0] > 500
+    assert np.array_equal(smp, acc[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "accum_pixels.npy"))  # the same pixels in every run
+    bench.dump_outputs(str(tmp_path / "b"), acc)  # a smaller frame into the same directory: no stale index beside it
+    assert not (tmp_path / "b" / "accum_pixels.npy").exists()
+
+
+def test_steps_must_be_positive():
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
 def _bench_line(stdout: str) -> dict:
     lines = [l for l in stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, stdout[-2000:]
@@ -208,6 +235,25 @@ def test_bench_emits_the_contract_line():
     # timings of this micro-job sit at the resolution of the clock and of the line's rounding: presence and sign only
     # (round 3: `bvh_build_s.port > 0` on a 0.2 ms build rounded to 3 places was a coin flip that hid every parity test)
     assert c["whole_path_first_iterations"]["value"] >= 0 and c["bvh_build_s"]["port"] >= 0 and "port_us" in c["bvh_build_s"]
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_render(tmp_path):
+    """--dump-outputs DIR: the accumulation buffer the last timed render left, every pixel holding exactly spp paths; --steps is
+    the number of timed steps the line reports"""
+    import numpy as np
+
+    W, H, spp = 320, 180, 2
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "c1", "--width", str(W), "--height", str(H), "--spp", str(spp), "--steps", "3", "--warmup", "1", "--pmc", "off",
+           "--no-reference-queue", "--no-cpu-baseline", "--no-spread", "--no-steady-state", "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    d = _bench_line(p.stdout)
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    assert sorted(os.listdir(tmp_path)) == ["accum.npy"]
+    a = np.load(tmp_path / "accum.npy")
+    assert a.dtype == np.float32 and a.shape == (W * H, 4)
+    assert np.all(a[:, 3] == spp) and np.all(np.isfinite(a[:, :3])) and a[:, :3].sum() > 0
 
 
 @pytest.mark.gpu

@@ -3,12 +3,14 @@
 the reference's Bbox.h (-> tests/golden/ref_bbox_ops.npz):
 
   CPU   the oracle's v3* helpers (oracle/orc_internal.h, via orc_glm) and its BBox ops reproduce the fixtures bit for
-        bit; when oracle/_ref is present (authoring container) the fixtures are re-derived from the live library too.
+        bit; the fixtures are re-derived from oracle/_ref (live where it is built, else its recorded answers:
+        conftest.ref_answers).
   GPU   hip/vecmath.hpp evaluated on the device (tyr_vecmath_probe) reproduces the same fixtures bit for bit.
 
 pow and exp go through <cmath> inside glm; the path's versions are the deterministic polynomial layer (DESIGN.md
 "Numeric contract" item 2), so those two ops are held to <= 1 ulp of glm's answers instead of equality -- except
 pow(x, 0.5), which the path evaluates as sqrt(x) and which must agree exactly on the path's range of arguments."""
+import hashlib
 import os
 
 import numpy as np
@@ -58,15 +60,26 @@ def test_oracle_helpers_equal_glm(orc, glm, op):
     check(op, out, glm)
 
 
-def test_fixture_is_what_the_live_glm_says(ref, glm):
-    """authoring container only: the committed answers are the vendored library's, byte for byte"""
-    if not hasattr(ref, "ref_glm"):
-        pytest.skip("oracle/_ref predates ref_glm: make -C oracle ref")
+def sha(a: np.ndarray) -> str:
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def test_fixture_is_what_the_live_glm_says(ref_answers, glm):
+    """the committed answers are the vendored library's, byte for byte (its answers by SHA-256)"""
+
+    def ask(ref):
+        out = {}
+        for op in range(N_OPS):
+            a, b, c = (np.ascontiguousarray(glm[f"{k}{op}"]) for k in "abc")
+            o = np.zeros_like(a)
+            assert ref.ref_glm(op, a.ctypes.data, b.ctypes.data, c.ctypes.data, a.shape[0], o.ctypes.data) == 0
+            out[f"shape{op}"] = np.array(o.shape, dtype=np.int64)
+            out[f"out{op}_sha256"] = np.array(sha(bits(o)))
+        return out
+
+    want = ref_answers("glm", ask, inputs=[glm[f"{k}{op}"] for op in range(N_OPS) for k in "abc"], needs=("ref_glm",))
     for op in range(N_OPS):
-        a, b, c = (np.ascontiguousarray(glm[f"{k}{op}"]) for k in "abc")
-        out = np.zeros_like(a)
-        assert ref.ref_glm(op, a.ctypes.data, b.ctypes.data, c.ctypes.data, a.shape[0], out.ctypes.data) == 0
-        assert np.array_equal(bits(out), bits(glm[f"out{op}"])), NAMES[op]
+        assert tuple(want[f"shape{op}"]) == glm[f"out{op}"].shape and str(want[f"out{op}_sha256"]) == sha(bits(glm[f"out{op}"])), NAMES[op]
 
 
 def test_bbox_host_ops_equal_reference(orc, hip):
@@ -91,15 +104,25 @@ def test_bbox_host_ops_equal_reference(orc, hip):
     assert np.array_equal(bits(bb["bounds"].reshape(-1, 6)[exact]), bits(z["boxes"][tri][exact]))
 
 
-def test_ref_bbox_fixture_is_live(ref):
+def test_ref_bbox_fixture_is_live(ref_answers):
     z = np.load(os.path.join(GOLDEN, "ref_bbox_ops.npz"))
     import ctypes as C
 
-    for v, k, box, ae in list(zip(z["verts"], z["counts"], z["boxes"], z["area_extent"]))[::7]:
-        vv = np.ascontiguousarray(v[:k])
-        b = np.zeros(6, dtype=np.float32)
-        o2 = np.zeros(2, dtype=np.float32)
-        ref.ref_bbox_host_ops(vv.ctypes.data_as(C.POINTER(C.c_float)), int(k), b.ctypes.data, o2.ctypes.data_as(C.POINTER(C.c_float)))
+    cases = list(zip(z["verts"], z["counts"], z["boxes"], z["area_extent"]))[::7]
+
+    def ask(ref):
+        boxes, area_extent = [], []
+        for v, k, _, _ in cases:
+            vv = np.ascontiguousarray(v[:k])
+            b = np.zeros(6, dtype=np.float32)
+            o2 = np.zeros(2, dtype=np.float32)
+            ref.ref_bbox_host_ops(vv.ctypes.data_as(C.POINTER(C.c_float)), int(k), b.ctypes.data, o2.ctypes.data_as(C.POINTER(C.c_float)))
+            boxes.append(b)
+            area_extent.append(o2)
+        return {"boxes": np.stack(boxes), "area_extent": np.stack(area_extent)}
+
+    want = ref_answers("bbox_host_ops", ask, inputs=[np.stack([c[i] for c in cases]) for i in (0, 1)])
+    for (_, _, box, ae), b, o2 in zip(cases, want["boxes"], want["area_extent"]):
         assert np.array_equal(bits(b), bits(box)) and np.array_equal(bits(o2), bits(ae))
 
 

@@ -1,7 +1,9 @@
 """The oracle against the known answers of SURVEY.md section 8c (tests/golden/kat.json),
-the committed reference-traversal fixtures, and -- when it has been built -- the
-reference's own header code in oracle/_ref.  CPU only."""
+the committed reference-traversal fixtures, and the reference's own header code in
+oracle/_ref (live where it has been built, else its recorded answers: conftest.ref_answers).
+CPU only."""
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -65,32 +67,36 @@ def test_cone_sample_known_answer(orc, golden):
     assert seed.value == k["seed_after"]
 
 
-def test_kat_values_rederive_from_the_reference(ref, golden):
+def test_kat_values_rederive_from_the_reference(ref_answers, golden):
     """the sun / sky / cone known answers of kat.json (recorded during the survey) are what the reference's own sunsky.cu,
-    compiled unmodified into oracle/_ref, answers now (authoring container only)"""
-    if not hasattr(ref, "ref_atmosphere"):
-        pytest.skip("oracle/_ref predates the atmosphere exports")
-    setup = (C.c_float * 8)()
-    ref.ref_sun_setup((C.c_float * 2)(*golden["sun_position"]), setup)
-    assert _close9(setup[0:3], golden["sunDirection"]) and _close9([setup[3]], [golden["sunAngularDiameterCos"]])
+    compiled unmodified into oracle/_ref, answers"""
     n = _f(1) / np.sqrt(_f(3))
-
-    def run(which, d):
-        dirs = np.array([d], dtype=np.float32)
-        out = np.zeros((1, 3), dtype=np.float32)
-        assert ref.ref_atmosphere(which, dirs.ctypes.data, 1, out.ctypes.data) == 0
-        return out[0]
-
-    for e in golden["sky"]:
-        d = (n, n, n) if e["dir"] == "norm111" else e["dir"]
-        assert _close9(run(1, d), e["value"]), e
-    sd = setup[0:3]
-    assert _close9(run(0, sd), golden["sun_at_sunDirection"]) and _close9(run(2, sd), golden["sunsky_at_sunDirection"])
+    sky_dirs = np.array([(n, n, n) if e["dir"] == "norm111" else e["dir"] for e in golden["sky"]], dtype=np.float32)
     k = golden["cone_sample"]
-    seed = C.c_uint32(k["seed"])
-    out = np.zeros((1, 3), dtype=np.float32)
-    ref.ref_cone_samples(C.byref(seed), 1, out.ctypes.data)
-    assert _close9(out[0], k["value"]) and seed.value == k["seed_after"]
+
+    def ask(ref):
+        setup = (C.c_float * 8)()
+        ref.ref_sun_setup((C.c_float * 2)(*golden["sun_position"]), setup)
+
+        def run(which, d):
+            dirs = np.array([d], dtype=np.float32)
+            out = np.zeros((1, 3), dtype=np.float32)
+            assert ref.ref_atmosphere(which, dirs.ctypes.data, 1, out.ctypes.data) == 0
+            return out[0]
+
+        sd = setup[0:3]
+        seed = C.c_uint32(k["seed"])
+        cone = np.zeros((1, 3), dtype=np.float32)
+        ref.ref_cone_samples(C.byref(seed), 1, cone.ctypes.data)
+        return {"setup": np.array(setup[:], dtype=np.float32), "sky": np.stack([run(1, d) for d in sky_dirs]), "sun": run(0, sd), "sunsky": run(2, sd),
+                "cone": cone[0], "cone_seed_after": np.uint32(seed.value)}
+
+    r = ref_answers("kat", ask, inputs=(np.array(golden["sun_position"], dtype=np.float32), sky_dirs, np.uint32(k["seed"])), needs=("ref_atmosphere",))
+    assert _close9(r["setup"][0:3], golden["sunDirection"]) and _close9([r["setup"][3]], [golden["sunAngularDiameterCos"]])
+    for e, v in zip(golden["sky"], r["sky"]):
+        assert _close9(v, e["value"]), e
+    assert _close9(r["sun"], golden["sun_at_sunDirection"]) and _close9(r["sunsky"], golden["sunsky_at_sunDirection"])
+    assert _close9(r["cone"], k["value"]) and int(r["cone_seed_after"]) == k["seed_after"]
 
 
 def test_sunsky_quirks(orc):
@@ -104,7 +110,7 @@ def test_sunsky_quirks(orc):
     assert np.all(orc.sun(S, away) > 0)
 
 
-def test_layout_matches_golden_and_reference(orc, golden, ref):
+def test_layout_matches_golden_and_reference(orc, golden, ref_answers):
     from tyrant_amd import scenes
 
     lay = golden["layout"]
@@ -119,9 +125,12 @@ def test_layout_matches_golden_and_reference(orc, golden, ref):
     assert scenes.NODE_DTYPE.fields["primitiveCount"][1] == lay["BVHNode"]["primitiveCount"]
     assert scenes.NODE_DTYPE.fields["splitAxis"][1] == lay["BVHNode"]["splitAxis"]
     # the same numbers straight from the reference headers
-    out = (C.c_int * 64)()
-    n = ref.ref_layout(out, 64)
-    got = list(out[:n])
+    def ask(ref):
+        out = (C.c_int * 64)()
+        n = ref.ref_layout(out, 64)
+        return {"layout": np.array(out[:n], dtype=np.int32)}
+
+    got = [int(x) for x in ref_answers("layout", ask)["layout"]]
     R, S, T, N = lay["RayQueue"], lay["ShadowQueue"], lay["Triangle"], lay["BVHNode"]
     want = [R["size"], R["origin"], R["direction"], R["direct"], R["distance"], R["identifier"], R["bounces"], R["index"], R["geometry_type"], R["lastSpecular"]]
     want += [S["size"], S["origin"], S["direction"], S["color"], S["buffer_index"], S["closestDistance"]]
@@ -130,10 +139,13 @@ def test_layout_matches_golden_and_reference(orc, golden, ref):
     assert got == want
 
 
-def test_reference_constants(ref, golden):
-    out = (C.c_double * 64)()
-    n = ref.ref_constants(out, 64)
-    v = list(out[:n])
+def test_reference_constants(ref_answers, golden):
+    def ask(ref):
+        out = (C.c_double * 64)()
+        n = ref.ref_constants(out, 64)
+        return {"constants": np.array(out[:n], dtype=np.float64)}
+
+    v = [float(x) for x in ref_answers("constants", ask)["constants"]]
     k = golden["constants"]
     assert np.float32(v[0]) == np.float32(k["pi"])
     assert v[2] == k["render_width"] and v[3] == k["render_height"]
@@ -173,8 +185,9 @@ def test_traversal_matches_reference_fixture(orc, name):
     assert np.array_equal(anyhit, z["anyhit"])
 
 
-def test_traversal_matches_live_reference(orc, ref):
-    """same comparison against the reference headers compiled here, on a fresh ray set"""
+def test_traversal_matches_live_reference(orc, ref_answers):
+    """same comparison against the reference headers compiled here, on a fresh ray set (the rays after the reference's
+    CachedBVH::intersect by SHA-256)"""
     from conftest import built_scene
     from tyrant_amd import scenes
 
@@ -190,15 +203,21 @@ def test_traversal_matches_live_reference(orc, ref):
     L = orc.lib()
     for i in range(n):
         L.orc_bvh_intersect(nodes.ctypes.data, prims.ctypes.data, a[i : i + 1].ctypes.data, None)
-    hit = np.zeros(n, dtype=np.int32)
-    ref.ref_bvh_intersect(nodes.ctypes.data, prims.ctypes.data, b.ctypes.data, n, hit.ctypes.data_as(C.POINTER(C.c_int)), None)
-    assert a.tobytes() == b.tobytes()
+
+    def ask(ref):
+        hit = np.zeros(n, dtype=np.int32)
+        ref.ref_bvh_intersect(nodes.ctypes.data, prims.ctypes.data, b.ctypes.data, n, hit.ctypes.data_as(C.POINTER(C.c_int)), None)
+        return {"rays_sha256": np.array(hashlib.sha256(b.tobytes()).hexdigest())}
+
+    want = ref_answers("traversal_soup2k", ask, inputs=(nodes, prims, rays))
+    assert hashlib.sha256(a.tobytes()).hexdigest() == str(want["rays_sha256"])
 
 
-def test_bbox_and_triangle_primitives_match_reference(orc, ref):
+def test_bbox_and_triangle_primitives_match_reference(orc, ref_answers):
     rng = np.random.default_rng(5)
     L = orc.lib()
     fp = C.POINTER(C.c_float)
+    cases, got_box, got_tri = [], [], []
     for _ in range(2000):
         lo = rng.uniform(-10, 10, 3)
         box = np.array([lo, lo + rng.uniform(0, 8, 3)], dtype=np.float32)
@@ -210,14 +229,20 @@ def test_bbox_and_triangle_primitives_match_reference(orc, ref):
             inv = (np.float32(1) / d).astype(np.float32)
         neg = (inv < 0).astype(np.int32)
         lowest = np.float32(rng.uniform(0.1, 100))
-        a = L.orc_bbox_intersect(box.ctypes.data, o.ctypes.data_as(fp), inv.ctypes.data_as(fp), neg.ctypes.data_as(C.POINTER(C.c_int)), lowest)
-        b = ref.ref_bbox_intersect(box.ctypes.data, o.ctypes.data_as(fp), inv.ctypes.data_as(fp), neg.ctypes.data_as(C.POINTER(C.c_int)), lowest)
-        assert a == b
+        got_box.append(L.orc_bbox_intersect(box.ctypes.data, o.ctypes.data_as(fp), inv.ctypes.data_as(fp), neg.ctypes.data_as(C.POINTER(C.c_int)), lowest))
         tri = np.zeros(10, dtype=np.float32)
         tri[:9] = rng.uniform(-5, 5, 9)
-        ta = L.orc_triangle_intersect(tri.ctypes.data, o.ctypes.data_as(fp), d.ctypes.data_as(fp))
-        tb = ref.ref_triangle_intersect(tri.ctypes.data, o.ctypes.data_as(fp), d.ctypes.data_as(fp))
-        assert np.float32(ta).view(np.uint32) == np.float32(tb).view(np.uint32)
+        got_tri.append(L.orc_triangle_intersect(tri.ctypes.data, o.ctypes.data_as(fp), d.ctypes.data_as(fp)))
+        cases.append((box, o, inv, neg, lowest, tri, d))
+
+    def ask(ref):
+        boxes = [ref.ref_bbox_intersect(box.ctypes.data, o.ctypes.data_as(fp), inv.ctypes.data_as(fp), neg.ctypes.data_as(C.POINTER(C.c_int)), lowest) for box, o, inv, neg, lowest, _, _ in cases]
+        tris = [ref.ref_triangle_intersect(tri.ctypes.data, o.ctypes.data_as(fp), d.ctypes.data_as(fp)) for _, o, _, _, _, tri, d in cases]
+        return {"bbox": np.array(boxes, dtype=np.int32), "triangle": np.array(tris, dtype=np.float32)}
+
+    want = ref_answers("bbox_triangle_primitives", ask, inputs=[np.stack([c[i] for c in cases]) for i in range(7)])
+    assert np.array_equal(np.array(got_box, dtype=np.int32), want["bbox"])
+    assert np.array_equal(bits(np.array(got_tri, dtype=np.float32)), bits(want["triangle"]))
 
 
 def test_triangle_culls_back_faces(orc):

@@ -6,8 +6,8 @@ tests/golden/make_ref_build_golden.py).
 
   CPU   oracle builder == fixture bytes (SAH); product builder (tyr_bvh_build, host code) == fixture bytes; C3's
         1.1 M-node tree by SHA-256; the oracle's sun / sky / sunsky within SUNSKY_MAX_ULP of the reference's and bit-equal
-        on >= 99 % of the components; setup constants and the sun-cone samples; when oracle/_ref is present the
-        fixtures are re-derived live.
+        on >= 99 % of the components; setup constants and the sun-cone samples; the fixtures re-derived from
+        oracle/_ref (live where it is built, else its recorded answers: conftest.ref_answers).
   GPU   the product builder on the GPU box's host for C3 and C5 (hash); the DEVICE's sun / sky / sunsky / cone sample
         through tyr_sunsky_probe within the same bound.
 
@@ -126,35 +126,44 @@ def test_c3_tree_of_oracle_and_product_equals_the_reference_tree(orc, hip, hashe
         assert sha(defined_triangle_bytes(prims)) == want["prims_sha256"]
 
 
-def test_fixtures_rederive_from_the_reference_when_it_is_present(ref, hashes):
-    """authoring container only (skipped where oracle/_ref is absent or older): the committed fixtures are what the
-    reference's builder emits now"""
-    if not hasattr(ref, "ref_bvh_build"):
-        pytest.skip("oracle/_ref predates the builder exports")
+def test_fixtures_rederive_from_the_reference_when_it_is_present(ref_answers, hashes):
+    """the committed fixtures are what the reference's builder emits (its nodes and reordered triangles by SHA-256)"""
     from tyrant_amd import scenes
 
-    for name in SMALL:
-        tris, bb, nodes_ref, prims_ref = load_build(name)
-        prims = np.ascontiguousarray(tris.copy())
-        nodes = np.zeros(2 * tris.shape[0] - 1, dtype=scenes.NODE_DTYPE)
-        nn = ref.ref_bvh_build(prims.ctypes.data, tris.shape[0], bb.ctypes.data, nodes.ctypes.data, 2)
-        assert nn == nodes_ref.shape[0] and nodes[:nn].tobytes() == nodes_ref.tobytes()
-        assert defined_triangle_bytes(prims) == np.ascontiguousarray(prims_ref[:, :37]).tobytes()
+    builds = {name: load_build(name) for name in SMALL}
+
+    def ask(ref):
+        out = {}
+        for name, (tris, bb, _, _) in builds.items():
+            prims = np.ascontiguousarray(tris.copy())
+            nodes = np.zeros(2 * tris.shape[0] - 1, dtype=scenes.NODE_DTYPE)
+            nn = ref.ref_bvh_build(prims.ctypes.data, tris.shape[0], bb.ctypes.data, nodes.ctypes.data, 2)
+            out.update({f"{name}_nodes": np.int64(nn), f"{name}_nodes_sha256": np.array(sha(nodes[:nn].tobytes())), f"{name}_prims_sha256": np.array(sha(defined_triangle_bytes(prims)))})
+        return out
+
+    want = ref_answers("ref_build", ask, inputs=[a for tris, bb, _, _ in builds.values() for a in (tris, bb)], needs=("ref_bvh_build",))
+    for name, (_, _, nodes_ref, prims_ref) in builds.items():
+        assert int(want[f"{name}_nodes"]) == nodes_ref.shape[0] and str(want[f"{name}_nodes_sha256"]) == sha(nodes_ref.tobytes())
+        assert str(want[f"{name}_prims_sha256"]) == sha(np.ascontiguousarray(prims_ref[:, :37]).tobytes())
 
 
-def test_bbox_union_matches_reference(ref, orc):
-    """Bbox.cpp:3-14 (fmin / fmax per component) against the oracle's union as the builder uses it"""
-    if not hasattr(ref, "ref_bbox_union"):
-        pytest.skip("oracle/_ref predates the builder exports")
+def test_bbox_union_matches_reference(ref_answers, orc):
+    """Bbox.cpp:3-14 (fmin / fmax per component) against the oracle's union as the builder uses it (the reference's
+    result by SHA-256)"""
     rng = np.random.default_rng(3)
     a = rng.normal(size=(4096, 2, 3)).astype(np.float32)
     b = rng.normal(size=(4096, 2, 3)).astype(np.float32)
     a[:8, 0] = 1e10  # Bbox.h:4 initial bounds
     a[:8, 1] = -1e10
-    out = np.zeros_like(a)
-    ref.ref_bbox_union(a.ctypes.data, b.ctypes.data, a.shape[0], out.ctypes.data)
+
+    def ask(ref):
+        out = np.zeros_like(a)
+        ref.ref_bbox_union(a.ctypes.data, b.ctypes.data, a.shape[0], out.ctypes.data)
+        return {"union_sha256": np.array(sha(out.tobytes()))}
+
+    got = ref_answers("bbox_union", ask, inputs=(a, b), needs=("ref_bbox_union",))
     want = np.stack([np.minimum(a[:, 0], b[:, 0]), np.maximum(a[:, 1], b[:, 1])], axis=1)
-    assert out.tobytes() == want.tobytes()
+    assert str(got["union_sha256"]) == sha(want.tobytes())
 
 
 def test_equal_counts_is_not_byte_pinned(hashes):
@@ -240,20 +249,28 @@ def test_oracle_scalar_helpers_follow_reference(orc, sunsky_gold):
     assert np.isfinite(h).all() and (h[:, 0] > 0).all() and (h[:, 1] > 0).all() and (h[:, 2] >= 0).all()
 
 
-def test_sunsky_fixture_rederives_from_the_reference_when_it_is_present(ref, sunsky_gold):
+def test_sunsky_fixture_rederives_from_the_reference_when_it_is_present(ref_answers, sunsky_gold):
+    """the committed atmosphere fixture is what the reference's sunsky.cu answers (its sun / sky / sunsky by SHA-256)"""
     import ctypes as C
 
-    if not hasattr(ref, "ref_atmosphere"):
-        pytest.skip("oracle/_ref predates the atmosphere exports")
+    def ask(ref):
+        out = {}
+        for k in range(3):
+            setup = (C.c_float * 8)()
+            ref.ref_sun_setup((C.c_float * 2)(*[float(x) for x in sunsky_gold[f"sun_position{k}"]]), setup)
+            out[f"setup{k}"] = np.array(setup[:], dtype=np.float32)
+            dirs = np.ascontiguousarray(sunsky_gold[f"dirs{k}"])
+            for which, name in enumerate(("sun", "sky", "sunsky")):
+                o = np.zeros_like(dirs)
+                assert ref.ref_atmosphere(which, dirs.ctypes.data, dirs.shape[0], o.ctypes.data) == 0
+                out[f"{name}{k}_sha256"] = np.array(sha(o.tobytes()))
+        return out
+
+    want = ref_answers("sunsky", ask, inputs=[sunsky_gold[f"{f}{k}"] for k in range(3) for f in ("sun_position", "dirs")], needs=("ref_atmosphere",))
     for k in range(3):
-        setup = (C.c_float * 8)()
-        ref.ref_sun_setup((C.c_float * 2)(*[float(x) for x in sunsky_gold[f"sun_position{k}"]]), setup)
-        assert np.array(setup[:], dtype=np.float32).tobytes() == sunsky_gold[f"setup{k}"].tobytes()
-        dirs = np.ascontiguousarray(sunsky_gold[f"dirs{k}"])
-        for which, name in enumerate(("sun", "sky", "sunsky")):
-            out = np.zeros_like(dirs)
-            assert ref.ref_atmosphere(which, dirs.ctypes.data, dirs.shape[0], out.ctypes.data) == 0
-            assert out.tobytes() == sunsky_gold[f"{name}{k}"].tobytes()
+        assert want[f"setup{k}"].tobytes() == sunsky_gold[f"setup{k}"].tobytes()
+        for name in ("sun", "sky", "sunsky"):
+            assert str(want[f"{name}{k}_sha256"]) == sha(sunsky_gold[f"{name}{k}"].tobytes())
 
 
 # ---- on the GPU box ---------------------------------------------------------------------------------------------------

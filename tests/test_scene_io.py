@@ -6,6 +6,8 @@ import struct
 import numpy as np
 import pytest
 
+from conftest import GOLDEN
+
 CUBE_PLY = """ply
 format ascii 1.0           { ascii/binary, format version number }
 comment made by anonymous  { comments are keyword specified }
@@ -87,12 +89,15 @@ def test_ply_errors(hip, tmp_path):
         hip.load_ply(str(notply))
 
 
-def test_reference_dragon_if_present(hip):
-    """Data/dragon.ply of the reference checkout (only in the authoring container): 22,126 vertices, 37,986 triangles"""
-    path = "/root/reference/PathTracer/Data/dragon.ply"
-    if not os.path.exists(path):
-        pytest.skip("reference data not present on this machine")
-    t = hip.load_ply(path)
+def test_reference_dragon_if_present(hip, tmp_path):
+    """Data/dragon.ply of the reference (stored xz-compressed as tests/golden/dragon.ply.xz): 22,126 vertices, 37,986
+    triangles"""
+    import lzma
+
+    path = tmp_path / "dragon.ply"
+    with lzma.open(os.path.join(GOLDEN, "dragon.ply.xz")) as f:
+        path.write_bytes(f.read())
+    t = hip.load_ply(str(path))
     assert t.shape[0] == 37986 and np.all(np.isfinite(t["vert"]))
     nodes, prims = hip.bvh_build(t)
     assert nodes[nodes["primitiveCount"] > 0]["primitiveCount"].sum() == 37986
