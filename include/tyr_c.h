@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -450,6 +450,33 @@ typedef struct tyr_camera_pose {
 int tyr_camera_handle_input(tyr_camera_pose* camera, const tyr_input_state* input, double delta);
 /* the reference's hard-wired sphere table, kernel.cu:674-680 */
 int tyr_default_spheres(tyr_sphere* out7);
+
+/* ---- ray queries on the uploaded scene (extension) -------------------------------------------------------------------
+ * "What does this ray hit?" / "is this segment blocked?" for a caller's batch of rays, against the scene the ctx holds --
+ * the same traversal as the render's, without its queues.  Semantics are the reference's, bit for bit:
+ *   closest hit: CachedBVH::intersect (bvh.h:118-161) with ray.distance = tmax -- accepted when t > 1e-3, t < dist and
+ *                dist - t > 1e-3; back faces culled (loader.h:21-46); ties resolve in the reference's visit order.
+ *                prim indexes the triangle array as uploaded (build order).  A miss leaves t = tmax, prim = geom = -1,
+ *                uv = (0, 0).  uv: Moller-Trumbore's u, v of the winning triangle.
+ *   any hit:     CachedBVH::intersectSimple(ray, closestAllowed = tmax) (bvh.h:213-256): occluded = 1 / 0.
+ *   TYR_QUERY_SPHERES: also the ctx's sphere table -- closest hit as intersect_scene (kernel.cu:125-140: the spheres in
+ *                reverse order, then the tree seeded with their distance; geom 0 = sphere with prim = its index, 1 = triangle),
+ *                any hit as intersect_scene_simple (kernel.cu:163-174: a sphere blocks when (d + 1e-3) < tmax).
+ * A ray with a NaN or infinite origin / direction component is a miss.  A scene without triangles answers from the spheres
+ * alone, or with misses.
+ * Every array pointer is a DEVICE pointer (hipMalloc'd memory or a torch tensor's data), float32 / int32 / uint8,
+ * contiguous: origins, directions n x 3; tmax n, or NULL for VERY_FAR (kernel.cu:15); t_out, prim_out, geom_out, occluded_out
+ * n; uv_out n x 2.  n up to 2^31 - 1, independent of queue_size; n == 0: TYR_OK and nothing launched.  The work is enqueued on
+ * `stream` (NULL: the ctx's stream) and the call returns once it is: synchronise that stream before reading.  A query uses the
+ * ctx's device, restores the caller's current device and touches no render state (queues, counters, frame, accumulation,
+ * timings).  TYR_ERR_INVALID: a required pointer is NULL or n >= 2^31; TYR_ERR_NO_SCENE: nothing uploaded yet. */
+#define TYR_QUERY_SPHERES 1u
+int tyr_query_closest(tyr_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* tmax, uint32_t flags, float* t_out, int32_t* prim_out,
+                      int32_t* geom_out /* NULL ok */, float* uv_out /* n x 2, NULL ok */, void* stream);
+int tyr_query_any(tyr_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* tmax, uint32_t flags, uint8_t* occluded_out, void* stream);
+/* device-side errors of the ctx's queries since the last reset (bit 1: a traversal stack overflowed the reference's 64
+ * entries, bvh.h:124); waits for the queries in flight on every stream they used first.  reset != 0 clears the bits. */
+int tyr_query_error(tyr_ctx* ctx, uint32_t* bits_out, int reset);
 
 #ifdef __cplusplus
 }

@@ -22,8 +22,12 @@ TYR_FLAG_COUNT_VISITS = 4
 TYR_FLAG_LIGHT_LIST = 8
 TYR_FLAG_TRIANGLE_COLORS = 16
 TYR_FLAG_DEBUG_BVH = 32
+TYR_ERR_INVALID = -1
 TYR_ERR_NO_DEVICE = -2
+TYR_ERR_NO_SCENE = -3
+TYR_ERR_DEVICE = -6
 TYR_ERR_UNSUPPORTED = -7
+TYR_QUERY_SPHERES = 1
 TYR_DIST_GATHER, TYR_DIST_REDUCE = 0, 1
 TYR_DIST_ID_BYTES = 128
 KERNEL_NAMES = ("primary", "extend", "shade", "connect", "resolve")
@@ -162,6 +166,9 @@ SYMBOLS = {
     "tyr_dist_row_owner": (C.c_int, [c_u32, c_u32, C.POINTER(c_u32), C.POINTER(c_u32)]),
     "tyr_dist_pack_rows": (C.c_int, [P, P, c_u32, c_u32, c_u32, c_u32, P]),
     "tyr_dist_scatter_rows": (C.c_int, [P, P, c_u32, c_u32, c_u32, P]),
+    "tyr_query_closest": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P, P, P, P]),
+    "tyr_query_any": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
+    "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
 }
 
 _libs: dict = {}
@@ -290,6 +297,8 @@ class Renderer:
     def __init__(self, width, height, queue_size, device=0, rank=0, nranks=1, flags=0, stream=None, blit_buffer=None):
         self.L = lib()
         self.W, self.H, self.N = width, height, queue_size
+        self.device = device
+        self._side = None  # query_* on a stream without a handle of its own (the default stream): see _on_stream
         cfg = Config(width, height, queue_size, device, rank, nranks, flags, stream)
         h = P()
         _check(self.L.tyr_create(C.byref(h), C.byref(cfg)), "tyr_create")
@@ -440,6 +449,89 @@ class Renderer:
     def import_work_queue(self, rays: np.ndarray, n_survivors: int):
         r = np.ascontiguousarray(rays)
         _check(self.L.tyr_queue_import(self.h, _ptr(r), n_survivors), "tyr_queue_import")
+
+    # ---- ray queries on the uploaded scene (tyr_query_closest / tyr_query_any) ----
+    def _query_rays(self, origins, directions, tmax):
+        """the caller's (N, 3) float32 CUDA tensors as they are (numpy arrays are copied to the ctx's device first)"""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+
+        def take(a, what, shape):
+            if isinstance(a, np.ndarray):
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+            if not isinstance(a, torch.Tensor):
+                raise TypeError(f"{what}: a torch tensor or a numpy array")
+            if a.dtype != torch.float32 or a.device != dev or not a.is_contiguous() or tuple(a.shape) != shape:
+                raise ValueError(f"{what}: a contiguous float32 tensor of shape {shape} on {dev}, not {tuple(a.shape)} {a.dtype} on {a.device}")
+            return a
+
+        staged = not all(isinstance(a, torch.Tensor) for a in (origins, directions, tmax) if a is not None)
+        o = origins if isinstance(origins, torch.Tensor) else np.asarray(origins)
+        n = o.shape[0] if o.ndim == 2 else -1
+        o = take(o, "origins", (n, 3))
+        d = take(directions, "directions", (n, 3))
+        t = take(tmax, "tmax", (n,)) if tmax is not None else None
+        return dev, n, o, d, t, staged
+
+    def _on_stream(self, stream, launch, staged):
+        """launch(handle) on `stream` (default: torch's current stream).  The default stream has no handle of its own (0 means
+        the ctx's stream to the library): the work then goes to a side stream ordered after it and before what follows on it."""
+        import torch
+
+        cur = torch.cuda.current_stream(self.device)
+        s = stream if stream is not None else cur
+        if staged and s != cur:
+            s.wait_stream(cur)  # the copies of numpy inputs were made on the current stream
+        if s.cuda_stream != 0:
+            _check(launch(s.cuda_stream), "tyr_query")
+            return
+        if self._side is None:
+            self._side = torch.cuda.Stream(self.device)
+        self._side.wait_stream(s)
+        _check(launch(self._side.cuda_stream), "tyr_query")
+        s.wait_stream(self._side)
+
+    def query_error(self, reset=True) -> int:
+        """tyr_query_error: the device-side error bits of this ctx's queries (1: traversal stack overflow); waits for them"""
+        bits = c_u32()
+        _check(self.L.tyr_query_error(self.h, C.byref(bits), 1 if reset else 0), "tyr_query_error")
+        return bits.value
+
+    def _query_finish(self):
+        bits = self.query_error(reset=True)
+        if bits:
+            raise TyrError(TYR_ERR_DEVICE, f"tyr_query: device error bits {bits:#x}")
+
+    def query_closest(self, origins, directions, tmax=None, spheres=False, stream=None):
+        """closest hit of every ray against the uploaded scene (CachedBVH::intersect with ray.distance = tmax, bvh.h:118-161;
+        with spheres=True intersect_scene, kernel.cu:125-140).  Returns torch tensors (t, prim, geom, uv): a miss keeps
+        t = tmax with prim = geom = -1 and uv = (0, 0); geom 0 = sphere (prim = its index), 1 = triangle (prim = build order)."""
+        import torch
+
+        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        geom = torch.empty(n, dtype=torch.int32, device=dev)
+        uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        flags = TYR_QUERY_SPHERES if spheres else 0
+        tp = tm.data_ptr() if tm is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_closest(self.h, n, o.data_ptr(), d.data_ptr(), tp, flags, t.data_ptr(), prim.data_ptr(), geom.data_ptr(), uv.data_ptr(), h), staged)
+        self._query_finish()
+        return t, prim, geom, uv
+
+    def query_any(self, origins, directions, tmax=None, spheres=False, stream=None):
+        """is anything hit within tmax (CachedBVH::intersectSimple, bvh.h:213-256; with spheres=True intersect_scene_simple,
+        kernel.cu:163-174)?  Returns a bool torch tensor."""
+        import torch
+
+        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
+        occ = torch.empty(n, dtype=torch.bool, device=dev)
+        flags = TYR_QUERY_SPHERES if spheres else 0
+        tp = tm.data_ptr() if tm is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_any(self.h, n, o.data_ptr(), d.data_ptr(), tp, flags, occ.data_ptr(), h), staged)
+        self._query_finish()
+        return occ
 
 
 def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: int = 0) -> np.ndarray:

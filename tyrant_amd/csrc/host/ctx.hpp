@@ -2,6 +2,8 @@
 // host/dist.cpp reads the stream, the blit buffer and the sharding from it).
 #pragma once
 
+#include <vector>
+
 #include <hip/hip_runtime.h>
 
 #include "host.hpp"
@@ -87,6 +89,18 @@ struct tyr_ctx {
 	Tuning tuning{};
 	LaunchCache launchCache{}; // occupancy answers of the persistent kernels, per ctx (not process-wide)
 	int numCUs = 256;
+
+	// tyr_query_* (host/query.cpp): their own device words -- the error bits, then a ring of chunk tickets, one per launch --
+	// and one event per stream they ran on (what tyr_query_error, a scene change and tyr_destroy wait for).  No render state.
+	struct QueryStream {
+		hipStream_t stream;
+		hipEvent_t done;   // recorded behind this stream's last query
+		uint32_t word;     // its ticket word
+		uint64_t lastUse;
+	};
+	uint32_t* dQuery = nullptr;
+	uint64_t querySeq = 0;
+	std::vector<QueryStream> queryStreams;
 
 	hipEvent_t ev[2][2 * TYR_K_COUNT]{}; // TYR_FLAG_PROFILE: start / stop per stage, two sets (iteration i uses set i & 1: two iterations may be queued)
 	bool evUsed[2][TYR_K_COUNT]{};

@@ -496,6 +496,7 @@ int tyr_destroy(tyr_ctx* c) {
 	(void)hipSetDevice(c->cfg.device);
 	if (c->stream)
 		(void)hipStreamSynchronize(c->stream);
+	query_free(c);
 	free_rayq(c->q[0]);
 	free_rayq(c->q[1]);
 	for (auto& sq : c->shadow) {
@@ -564,6 +565,8 @@ int upload_light_list(tyr_ctx* c, const tyr_triangle* prims, int32_t nPrims) {
 // the ctx lets go of its scene (the stream is idle afterwards)
 int drop_scene(tyr_ctx* c) {
 	HIPCHK(hipStreamSynchronize(c->stream));
+	if (int rc = query_wait(c)) // queries on the caller's streams read the arrays too
+		return rc;
 	dev_free(c->dNodes);
 	dev_free(c->dQuads);
 	dev_free(c->dTris);

@@ -59,6 +59,9 @@ bool merged_render(const tyr_ctx* c);
 int flush_pending_shadow(tyr_ctx* c);
 void stage_end(tyr_ctx* c);
 int check_device_error(const tyr_ctx* c);
+// host/query.cpp: wait for the ctx's queries in flight on any stream; free their device words (tyr_destroy)
+int query_wait(tyr_ctx* c);
+void query_free(tyr_ctx* c);
 // AoS import / export (host/staged_api.cpp): physical slots that hold a record, per segment counter array `seg` (device pointer)
 int valid_slots(const uint32_t* dSeg, std::vector<uint32_t>& slots, uint32_t* total = nullptr);
 void dense_counts(uint32_t n, uint32_t* cnt /* [kSegs * kSegStride] */);
