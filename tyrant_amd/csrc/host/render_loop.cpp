@@ -270,11 +270,12 @@ static int render_run_ahead(tyr_ctx* c, uint32_t max_iterations, uint32_t& it) {
 	// budget left behind j (exact once it is zero) and the last iteration that gave birth to rays.
 	const bool mayFold = c->tuning.foldPrologue != 0 && c->tuning.foldSpheres != 0;
 	// INVARIANT the kernels rely on: an iteration that turns out to have no rays (n_live == 0: the one queued ahead of its predecessor's
-	// counts for nothing) is never followed by another -- the loop below returns when it sees "budget == 0 && s == 0" -- so the kernels that
-	// would open its successor (k_scan_words' and k_shade's last blocks) skip that when n_live is 0, and the counters of the last real
-	// iteration stay what tyr_shadow_export reads.
+	// counts for nothing, or iteration 0 of a render that starts with no survivors and no budget) is never followed by another -- the loop
+	// below returns when it sees "budget == 0 && s == 0", and nothing is queued behind an iteration known to have no rays (live == 0 below:
+	// no fold, no look-ahead) -- so the kernels that would open its successor (k_scan_words' and k_shade's last blocks) skip that when
+	// n_live is 0, and the counters of the last real iteration stay what tyr_shadow_export reads.
 	auto queued_ahead_behind = [&](uint32_t j, uint64_t budgetBehindJ, uint32_t lastBirthAtJ) { return j + 1 < max_iterations && (budgetBehindJ != 0 || j < lastBirthAtJ + static_cast<uint32_t>(kMaxBounces)); };
-	bool folded = mayFold && budget == 0 && queued_ahead_behind(0, budget, 0); // (of the iteration queued last: its k_scan_words has opened the next one)
+	bool folded = mayFold && budget == 0 && live != 0 && queued_ahead_behind(0, budget, 0); // (of the iteration queued last: its k_scan_words has opened the next one)
 	if ((rc = enqueue_merged_iteration(c, IterationPlan{ nNew, live, static_cast<uint32_t>(s), 0u }, true, folded, false)))
 		return rc;
 	uint32_t enq = 1;
@@ -290,7 +291,7 @@ static int render_run_ahead(tyr_ctx* c, uint32_t max_iterations, uint32_t& it) {
 		uint32_t frameBefore = c->frame;
 		const uint32_t shadowSetBefore = c->shadowSet; // (enqueue_shade of an iteration queued ahead moves it: an iteration that turns out empty must give it back, or tyr_shadow_export would read the empty iteration's counters)
 		const bool foldedBefore = c->lastShadeFolded;
-		const bool canHaveSurvivors = budget != 0 || enq - 1 < lastBirth + static_cast<uint32_t>(kMaxBounces); // of iteration enq - 1
+		const bool canHaveSurvivors = live != 0 && (budget != 0 || enq - 1 < lastBirth + static_cast<uint32_t>(kMaxBounces)); // of iteration enq - 1 (live: its exact ray count)
 		if (enq < max_iterations && canHaveSurvivors) {
 			const uint32_t liveMax = static_cast<uint32_t>(std::min<uint64_t>(N, static_cast<uint64_t>(live) + budget));
 			const uint32_t newMax = static_cast<uint32_t>(std::min<uint64_t>(N, budget));
@@ -310,7 +311,7 @@ static int render_run_ahead(tyr_ctx* c, uint32_t max_iterations, uint32_t& it) {
 		// shadow rays goes out now, sized from an upper bound (at most one shadow ray per ray; the kernel takes its counts from the
 		// device), instead of after the ~25 us it takes the counts to reach the host and the launch to reach the GPU.
 		bool flushedEarly = false;
-		if (!ahead && mayFold && budget == 0 && !canHaveSurvivors) {
+		if (!ahead && mayFold && budget == 0 && !canHaveSurvivors && live != 0) {
 			c->shadowPending = true;
 			c->shadowPendingMax = live;
 			if ((rc = flush_pending_shadow(c)))
