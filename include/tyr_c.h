@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -139,6 +139,7 @@ typedef struct tyr_config {
 #define TYR_FLAG_DEBUG_BVH 32u         /* the reference's compile-time BVH_DEBUG (kernel.cu:721-722): the extend stage is extend_debug_BVH (kernel.cu:300-328,
                                         * intersect_debug bvh.h:164-209) -- spheres ignored, and the blit_buffer receives, per ray, green = steps x 0.0002 x 255.99
                                         * (red instead from 70 steps on), a = 1 -- and tyr_launch_kernels / tyr_render run primary + that stage only */
+#define TYR_FLAG_REFIT 64u             /* every scene upload keeps what tyr_scene_refit needs on the device (counted in tyr_scene_info.device_bytes) */
 
 typedef struct tyr_ctx tyr_ctx;
 
@@ -265,7 +266,7 @@ typedef struct tyr_scene_info {
 	uint32_t max_quad_nodes;   /* 1 << 25 */
 	uint32_t max_prim_offset;  /* 1 << 26 */
 	uint32_t quad_max_stack;   /* the most stack entries any traversal of this tree can need (the drain's four-lanes-to-a-ray form holds 48 and is used only below that) */
-	uint64_t device_bytes;     /* quad nodes + pair nodes + 48-byte triangles resident in HBM */
+	uint64_t device_bytes;     /* quad nodes + pair nodes + 48-byte triangles resident in HBM (+ the refit plan with TYR_FLAG_REFIT) */
 	double upload_layout_s;    /* the last tyr_scene_upload / tyr_scene_build_upload: seconds in the layout passes (on the device, or on the threads of tyr_set_build_threads) ... */
 	double upload_copy_s;      /* ... and in device allocation + the copies to HBM */
 	uint32_t layout_on_device; /* 1: that layout ran on the device (TYR_TUNE_LAYOUT_ON_DEVICE; hip/bvh_layout_dev.hip), 0: on the host */
@@ -477,6 +478,30 @@ int tyr_query_any(tyr_ctx* ctx, uint32_t n, const float* origins, const float* d
 /* device-side errors of the ctx's queries since the last reset (bit 1: a traversal stack overflowed the reference's 64
  * entries, bvh.h:124); waits for the queries in flight on every stream they used first.  reset != 0 clears the bits. */
 int tyr_query_error(tyr_ctx* ctx, uint32_t* bits_out, int reset);
+
+/* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
+ * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;
+ * only the triangles and the boxes change (the boxes by the reference's rule: a leaf's box is Union folded from BBox{} over its
+ * primitives' boxes in array order, bvh.cpp:71-73; an interior node's Union(left, right), bvh.cpp:222).
+ *   prims   nPrims new records in the order of the array that was uploaded (the builder's reordered order).
+ *   bboxes  their boxes in that order, or NULL: computed from the records by tyr_triangle_bboxes's rule (as tyr_bvh_build takes them).
+ *   After the call the ctx's scene is byte for byte what tyr_scene_upload(nodes', prims) would have made, where nodes' is the
+ *   uploaded node array with every box recomputed by that rule -- pair records (TYR_FLAG_COUNT_VISITS / TYR_FLAG_DEBUG_BVH)
+ *   included.  nodes_out (may be NULL; a HOST array of nNodes entries) receives nodes'.
+ *   Only geometry changes: every record's materialType and palette byte (offsets 36, 37) must equal the uploaded ones, so the
+ *   light list and the palette stay valid.
+ *   Failures leave the scene unchanged (the same tyr_scene_hash): TYR_ERR_INVALID for a changed materialType / palette byte, a
+ *   non-finite coordinate or box, nPrims other than the uploaded count or a NULL prims; TYR_ERR_UNSUPPORTED for a ctx without
+ *   TYR_FLAG_REFIT; TYR_ERR_NO_SCENE when nothing has been uploaded.  An empty scene with nPrims == 0 is a no-op.
+ *   Render state is untouched (queues, survivors, accumulation, frame, budget): survivors are traced against the new geometry at
+ *   the next launch.  tyr_reset_accum starts a fresh image.
+ *   Ordering: with TYR_REFIT_DEVICE, prims / bboxes are DEVICE addresses and the refit waits for `stream` (NULL: the ctx's
+ *   stream) before reading them; without it they are host arrays and `stream` is ignored.  The refit runs after all work queued
+ *   on the ctx's stream and after the ctx's queries on other streams, and returns once the scene is updated (the root box comes
+ *   back to the host): queries and renders issued after it see the new scene.  A ctx without TYR_FLAG_REFIT uploads, lays out
+ *   and reports device_bytes exactly as before. */
+#define TYR_REFIT_DEVICE 1u /* tyr_scene_refit: prims / bboxes are device addresses, ready on `stream` */
+int tyr_scene_refit(tyr_ctx* ctx, const tyr_triangle* prims, const tyr_bbox* bboxes, int32_t nPrims, uint32_t flags, void* stream, tyr_bvh_node* nodes_out);
 
 #ifdef __cplusplus
 }

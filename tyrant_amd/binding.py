@@ -22,12 +22,14 @@ TYR_FLAG_COUNT_VISITS = 4
 TYR_FLAG_LIGHT_LIST = 8
 TYR_FLAG_TRIANGLE_COLORS = 16
 TYR_FLAG_DEBUG_BVH = 32
+TYR_FLAG_REFIT = 64
 TYR_ERR_INVALID = -1
 TYR_ERR_NO_DEVICE = -2
 TYR_ERR_NO_SCENE = -3
 TYR_ERR_DEVICE = -6
 TYR_ERR_UNSUPPORTED = -7
 TYR_QUERY_SPHERES = 1
+TYR_REFIT_DEVICE = 1
 TYR_DIST_GATHER, TYR_DIST_REDUCE = 0, 1
 TYR_DIST_ID_BYTES = 128
 KERNEL_NAMES = ("primary", "extend", "shade", "connect", "resolve")
@@ -169,6 +171,7 @@ SYMBOLS = {
     "tyr_query_closest": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P, P, P, P]),
     "tyr_query_any": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
+    "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
 }
 
 _libs: dict = {}
@@ -299,6 +302,7 @@ class Renderer:
         self.W, self.H, self.N = width, height, queue_size
         self.device = device
         self._side = None  # query_* on a stream without a handle of its own (the default stream): see _on_stream
+        self._n_nodes = 0  # length of the node array of the scene uploaded last (refit(want_nodes=True))
         cfg = Config(width, height, queue_size, device, rank, nranks, flags, stream)
         h = P()
         _check(self.L.tyr_create(C.byref(h), C.byref(cfg)), "tyr_create")
@@ -323,6 +327,7 @@ class Renderer:
         nodes = np.ascontiguousarray(nodes)
         prims = np.ascontiguousarray(prims)
         _check(self.L.tyr_scene_upload(self.h, _ptr(nodes), nodes.shape[0], _ptr(prims), prims.shape[0]), "tyr_scene_upload")
+        self._n_nodes = nodes.shape[0] if prims.shape[0] else 0
 
     def set_spheres(self, spheres: np.ndarray | None):
         if spheres is None:
@@ -439,6 +444,7 @@ class Renderer:
         sec = (C.c_double * 3)(0.0, 0.0, 0.0)
         nn = c_i32(0)
         _check(self.L.tyr_scene_build_upload(self.h, _ptr(prims), n, _ptr(bb), None if nodes is None else _ptr(nodes), C.byref(nn), sec), "tyr_scene_build_upload")
+        self._n_nodes = nn.value
         return (None if nodes is None else nodes[: nn.value].copy()), prims, (sec[0], sec[1], sec[2])
 
     def scene_info(self) -> dict:
@@ -491,6 +497,45 @@ class Renderer:
         self._side.wait_stream(s)
         _check(launch(self._side.cuda_stream), "tyr_query")
         s.wait_stream(self._side)
+
+    def refit(self, prims, bboxes=None, stream=None, want_nodes=False):
+        """tyr_scene_refit: new triangle records, in the uploaded (build) order, for the scene this ctx holds -- the tree keeps its
+        shape, its boxes follow the reference's rule.  prims: a TRIANGLE_DTYPE numpy array (host path), or a contiguous torch
+        tensor on this ctx's device holding the 40-byte records (e.g. (n, 10) float32, or (n, 40) uint8), read on `stream`
+        (default: torch's current stream).  bboxes: None (computed from the records), or BBOX_DTYPE numpy / (n, 6) float32
+        tensor alike.  Returns the refitted node array with want_nodes=True, else None.  Raises TyrError as the C call fails."""
+        nodes = np.zeros(self._n_nodes, dtype=scenes.NODE_DTYPE) if want_nodes else None
+        out = None if nodes is None else _ptr(nodes)
+        try:
+            import torch
+        except ImportError:
+            torch = None
+        if torch is not None and isinstance(prims, torch.Tensor):
+            dev = torch.device("cuda", self.device)
+            for a, what, size in ((prims, "prims", 40), (bboxes, "bboxes", 24)):
+                if a is None:
+                    continue
+                if not isinstance(a, torch.Tensor) or a.device != dev or not a.is_contiguous() or a.numel() * a.element_size() % size:
+                    raise ValueError(f"{what}: a contiguous tensor of {size}-byte records on {dev}")
+            n = prims.numel() * prims.element_size() // 40
+            if bboxes is not None and bboxes.numel() * bboxes.element_size() != 24 * n:
+                raise ValueError("bboxes: one 24-byte box per triangle")
+            s = stream if stream is not None else torch.cuda.current_stream(self.device)
+            h = s.cuda_stream
+            if h == 0:  # (0 would name the ctx's stream to the library: a side stream behind the default one carries the wait)
+                if self._side is None:
+                    self._side = torch.cuda.Stream(self.device)
+                self._side.wait_stream(s)
+                h = self._side.cuda_stream
+            bp = None if bboxes is None else bboxes.data_ptr()
+            _check(self.L.tyr_scene_refit(self.h, prims.data_ptr(), bp, n, TYR_REFIT_DEVICE, h, out), "tyr_scene_refit")
+        else:
+            p = np.ascontiguousarray(prims, dtype=scenes.TRIANGLE_DTYPE)
+            bb = None if bboxes is None else np.ascontiguousarray(bboxes, dtype=scenes.BBOX_DTYPE)
+            if bb is not None and bb.shape != p.shape:
+                raise ValueError("bboxes: one box per triangle")
+            _check(self.L.tyr_scene_refit(self.h, _ptr(p), None if bb is None else _ptr(bb), p.shape[0], 0, None, out), "tyr_scene_refit")
+        return nodes
 
     def query_error(self, reset=True) -> int:
         """tyr_query_error: the device-side error bits of this ctx's queries (1: traversal stack overflow); waits for them"""

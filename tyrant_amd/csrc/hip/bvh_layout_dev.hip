@@ -336,7 +336,9 @@ __device__ __forceinline__ uint32_t new_index(const uint32_t* so, const uint32_t
 }
 
 // ---- the records, each written once at its final place (bvh_layout.cpp quad_write) ----
-__global__ void k_lay_quads(const tyr_bvh_node* __restrict__ nodes, const uint32_t* __restrict__ quadIndex, float4* __restrict__ quads, int nNodes, const LayState* __restrict__ S) {
+// (slotNode, may be null: the node behind each slot, for tyr_scene_refit)
+__global__ void k_lay_quads(const tyr_bvh_node* __restrict__ nodes, const uint32_t* __restrict__ quadIndex, float4* __restrict__ quads, int4* __restrict__ slotNode, int nNodes,
+                            const LayState* __restrict__ S) {
 	__shared__ uint32_t so[kStagedNodes], sn[kStagedNodes];
 	const uint32_t nTop = S->nTop;
 	if (threadIdx.x < kStagedNodes) {
@@ -368,7 +370,10 @@ __global__ void k_lay_quads(const tyr_bvh_node* __restrict__ nodes, const uint32
 		const uint32_t r = s.ref[k];
 		refs[k] = (int32_t)r < 0 ? r : (new_index(so, sn, nTop, r) | ((real_meta(nodes, s.node[k]) & 63u) << kQuadOrderShift));
 	}
-	float4* q = quads + 8 * (size_t)new_index(so, sn, nTop, qi);
+	const uint32_t at = new_index(so, sn, nTop, qi);
+	if (slotNode)
+		slotNode[at] = make_int4(s.node[0], s.node[1], s.node[2], s.node[3]);
+	float4* q = quads + 8 * (size_t)at;
 	for (int a = 0; a < 3; ++a) {
 		q[2 * a + 0] = make_float4(lo[0][a], hi[0][a], lo[1][a], hi[1][a]);
 		q[2 * a + 1] = make_float4(lo[2][a], hi[2][a], lo[3][a], hi[3][a]);
@@ -422,7 +427,7 @@ inline unsigned blocks_for(size_t n) { return static_cast<unsigned>((n + kB - 1)
 
 // dNodes / dPrims: DEVICE arrays in the reference's formats.  On TYR_OK out.quads / out.tris are fresh device allocations (hipMalloc)
 // the caller owns.  TYR_ERR_UNSUPPORTED: the host pass has to do this tree (see the head of this file); anything else: a device error.
-int layout_on_device(const tyr_bvh_node* dNodes, int32_t nNodes, const tyr_triangle* dPrims, int32_t nPrims, DeviceTreeLayout& out, hipStream_t st) {
+int layout_on_device(const tyr_bvh_node* dNodes, int32_t nNodes, const tyr_triangle* dPrims, int32_t nPrims, DeviceTreeLayout& out, hipStream_t st, bool wantSlots) {
 #define TYR_L(expr)                                                     \
 	do {                                                                \
 		const hipError_t e_ = (expr);                                   \
@@ -437,6 +442,7 @@ int layout_on_device(const tyr_bvh_node* dNodes, int32_t nNodes, const tyr_trian
 	DevBufL<LayState> dS;
 	DevBufL<uint32_t> dSeen, dList, dQuadIndex, dNodeOfQuad, dNeed, dBlockSums;
 	DevBufL<float4> dTris, dQuads;
+	DevBufL<int4> dSlots;
 	TYR_L(dS.alloc(1));
 	TYR_L(dSeen.alloc(nN));
 	TYR_L(dList.alloc(nN));
@@ -488,9 +494,11 @@ int layout_on_device(const tyr_bvh_node* dNodes, int32_t nNodes, const tyr_trian
 	TYR_L(dNodeOfQuad.alloc(nQuads));
 	TYR_L(dNeed.alloc(nQuads));
 	TYR_L(dQuads.alloc(8 * static_cast<size_t>(nQuads)));
+	if (wantSlots)
+		TYR_L(dSlots.alloc(nQuads));
 	hipLaunchKernelGGL(k_lay_number, dim3(static_cast<unsigned>(nScanBlocks)), dim3(kB), 0, st, dNodes, dSeen.p, dBlockSums.p, dQuadIndex.p, dNodeOfQuad.p, nNodes);
 	hipLaunchKernelGGL(k_lay_top, dim3(1), dim3(64), 0, st, dNodes, dQuadIndex.p, dNodeOfQuad.p, dS.p);
-	hipLaunchKernelGGL(k_lay_quads, dim3(blocks_for(nN)), dim3(kB), 0, st, dNodes, dQuadIndex.p, dQuads.p, nNodes, dS.p);
+	hipLaunchKernelGGL(k_lay_quads, dim3(blocks_for(nN)), dim3(kB), 0, st, dNodes, dQuadIndex.p, dQuads.p, dSlots.p, nNodes, dS.p);
 	for (uint32_t l = nLevels; l-- > 0;) {
 		if (l & 1u)
 			continue; // records sit at even depth
@@ -508,6 +516,7 @@ int layout_on_device(const tyr_bvh_node* dNodes, int32_t nNodes, const tyr_trian
 	std::memcpy(out.rootMax, hS.rootMax, 12);
 	out.quads = dQuads.release();
 	out.tris = dTris.release();
+	out.slotNode = reinterpret_cast<int32_t*>(dSlots.release());
 	return TYR_OK;
 #undef TYR_L
 }

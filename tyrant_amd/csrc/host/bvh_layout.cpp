@@ -166,8 +166,10 @@ struct Range { // the subtree of `begin`: nodes [begin, end)
 
 } // namespace
 
-int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_triangle* prims, int32_t nPrims, DeviceLayout& L, bool wantPairs) {
+int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_triangle* prims, int32_t nPrims, DeviceLayout& L, bool wantPairs, bool wantRefit) {
 	L.pairNodes.clear();
+	L.slotNode.clear();
+	L.pairNode.clear();
 	L.quadNodes.clear();
 	L.tris.clear();
 	L.nPairs = 0;
@@ -459,6 +461,11 @@ int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_tri
 	const uint32_t nQuads = L.nQuads;
 	if (nQuads > kQuadIndexMask)
 		return TYR_ERR_INVALID;
+	if (wantRefit) { // (entries the passes below do not write: synthetic records' slots and empty slots)
+		L.slotNode.assign(static_cast<size_t>(nQuads) * 4, -1);
+		if (wantPairs)
+			L.pairNode.assign(static_cast<size_t>(L.nPairs) * 2, -1);
+	}
 
 	// ---- pair nodes (the counting build and the BVH_DEBUG picture only) ----
 	// reference of a child node; leaves longer than kMaxLeafPrims become a chain of synthetic "left first" pair nodes (axis 3)
@@ -483,6 +490,10 @@ int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_tri
 					continue;
 				const int32_t li = static_cast<int32_t>(i) + 1, ri = n.offset;
 				pair_write(&L.pairNodes[static_cast<size_t>(pairIndex[i]) * 16], nodes[li].bbox, nodes[ri].bbox, child_ref(li), child_ref(ri), n.splitAxis);
+				if (wantRefit) {
+					L.pairNode[static_cast<size_t>(pairIndex[i]) * 2 + 0] = li;
+					L.pairNode[static_cast<size_t>(pairIndex[i]) * 2 + 1] = ri;
+				}
 			}
 		});
 		for (int32_t k : pairOrder) { // the chains, back to front
@@ -493,6 +504,8 @@ int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_tri
 			uint32_t idx = ll.pairHead - (chunks - 2);
 			for (uint32_t j = chunks - 1; j-- > 0; ++idx) {
 				pair_write(&L.pairNodes[static_cast<size_t>(idx) * 16], c.bbox, c.bbox, leaf_ref(off + j * kMaxLeafPrims, kMaxLeafPrims), ref, 3u);
+				if (wantRefit)
+					L.pairNode[static_cast<size_t>(idx) * 2 + 0] = L.pairNode[static_cast<size_t>(idx) * 2 + 1] = ll.node;
 				ref = idx;
 			}
 		}
@@ -646,7 +659,10 @@ int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_tri
 				refs[k] = final_ref(s.ref[k], s.node[k]);
 				boxes[k] = s.node[k] >= 0 ? nodes[s.node[k]].bbox : emptyBox;
 			}
-			quad_write(&L.quadNodes[static_cast<size_t>(new_index(qi)) * 32], boxes, refs, real_meta(pi));
+			const size_t at = new_index(qi);
+			quad_write(&L.quadNodes[at * 32], boxes, refs, real_meta(pi));
+			if (wantRefit)
+				std::memcpy(&L.slotNode[at * 4], s.node, sizeof s.node);
 		}
 	});
 	for (uint32_t k = 0; k < nQuads - nRealQuads; ++k) {

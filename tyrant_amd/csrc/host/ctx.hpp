@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../hip/refit.hpp"
 #include "host.hpp"
 
 using tyr::ConnectCounters;
@@ -101,6 +102,9 @@ struct tyr_ctx {
 	uint32_t* dQuery = nullptr;
 	uint64_t querySeq = 0;
 	std::vector<QueryStream> queryStreams;
+
+	// TYR_FLAG_REFIT: what every scene upload keeps for tyr_scene_refit (host/refit.cpp)
+	tyr::RefitPlan refit{};
 
 	hipEvent_t ev[2][2 * TYR_K_COUNT]{}; // TYR_FLAG_PROFILE: start / stop per stage, two sets (iteration i uses set i & 1: two iterations may be queued)
 	bool evUsed[2][TYR_K_COUNT]{};

@@ -518,6 +518,7 @@ int tyr_destroy(tyr_ctx* c) {
 	dev_free(c->dTris);
 	dev_free(c->dLights);
 	dev_free(c->dPalette);
+	refit_free(c);
 	if (c->ownBlit)
 		dev_free(c->blit);
 	if (c->hK)
@@ -571,6 +572,7 @@ int drop_scene(tyr_ctx* c) {
 	dev_free(c->dQuads);
 	dev_free(c->dTris);
 	dev_free(c->dLights);
+	refit_free(c);
 	c->nLights = 0;
 	c->scene = DevScene{};
 	c->scene.rootRef = kRefDone;
@@ -578,14 +580,16 @@ int drop_scene(tyr_ctx* c) {
 	return TYR_OK;
 }
 
-// a layout made on the device (hip/bvh_layout_dev.hip) becomes the ctx's scene: L's arrays change owner
-int adopt_device_layout(tyr_ctx* c, DeviceTreeLayout& L, int32_t nPrims) {
+// a layout made on the device (hip/bvh_layout_dev.hip) becomes the ctx's scene: L's arrays change owner.  TYR_FLAG_REFIT: the
+// refit plan is made from the reference's node array -- dNodes on the device, hostNodes (may be null) the same on the host
+int adopt_device_layout(tyr_ctx* c, DeviceTreeLayout& L, int32_t nPrims, const tyr_bvh_node* dNodes, const tyr_bvh_node* hostNodes, int32_t nNodes) {
 	int rc = drop_scene(c);
 	if (rc == TYR_OK)
 		rc = dev_alloc(c->dNodes, 4); // (no pair nodes; one element so the pointer is never null)
 	if (rc) {
 		(void)hipFree(L.quads);
 		(void)hipFree(L.tris);
+		dev_free(L.slotNode);
 		L.quads = L.tris = nullptr;
 		return rc;
 	}
@@ -604,6 +608,9 @@ int adopt_device_layout(tyr_ctx* c, DeviceTreeLayout& L, int32_t nPrims) {
 	c->scene.rootRef = 0u; // the pair layout's root (pair 0), as the host pass answers without pair nodes
 	c->scene.nPairs = 0;
 	c->scene.nPrims = static_cast<uint32_t>(nPrims);
+	if (c->cfg.flags & TYR_FLAG_REFIT)
+		return refit_keep(c, hostNodes, dNodes, nNodes, nullptr, L.slotNode, L.nQuads * 4u, nullptr, 0);
+	dev_free(L.slotNode);
 	return TYR_OK;
 }
 
@@ -629,9 +636,9 @@ int scene_upload_device_layout(tyr_ctx* c, const tyr_bvh_node* nodes, int32_t nN
 	HIPCHK(hipMemcpy(dRawPrims, prims, static_cast<size_t>(nPrims) * sizeof(tyr_triangle), hipMemcpyHostToDevice));
 	const auto t1 = std::chrono::steady_clock::now();
 	DeviceTreeLayout L;
-	if ((rc = layout_on_device(dRawNodes, nNodes, dRawPrims, nPrims, L, c->stream)))
+	if ((rc = layout_on_device(dRawNodes, nNodes, dRawPrims, nPrims, L, c->stream, (c->cfg.flags & TYR_FLAG_REFIT) != 0)))
 		return rc;
-	if ((rc = adopt_device_layout(c, L, nPrims)))
+	if ((rc = adopt_device_layout(c, L, nPrims, dRawNodes, nodes, nNodes)))
 		return rc;
 	c->uploadCopyS = std::chrono::duration<double>(t1 - t0).count();
 	c->uploadLayoutS = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
@@ -665,7 +672,7 @@ int tyr_scene_upload(tyr_ctx* c, const tyr_bvh_node* nodes, int32_t nNodes, cons
 	DeviceLayout L;
 	const auto t0 = std::chrono::steady_clock::now();
 	try { // (the layout pass allocates and starts threads: nothing may leave a C entry point as an exception)
-		rc = build_device_layout(nodes, nNodes, prims, nPrims, L, wantPairs);
+		rc = build_device_layout(nodes, nNodes, prims, nPrims, L, wantPairs, (c->cfg.flags & TYR_FLAG_REFIT) != 0);
 	} catch (const std::bad_alloc&) {
 		rc = TYR_ERR_OOM;
 	} catch (...) {
@@ -701,6 +708,11 @@ int tyr_scene_upload(tyr_ctx* c, const tyr_bvh_node* nodes, int32_t nNodes, cons
 	c->scene.rootRef = L.rootRef;
 	c->scene.nPairs = L.nPairs;
 	c->scene.nPrims = static_cast<uint32_t>(nPrims);
+	if (c->cfg.flags & TYR_FLAG_REFIT) {
+		int32_t* noSlots = nullptr;
+		if ((rc = refit_keep(c, nodes, nullptr, nNodes, L.slotNode.data(), noSlots, static_cast<uint32_t>(L.slotNode.size()), L.pairNode.data(), static_cast<uint32_t>(L.pairNode.size()))))
+			return rc;
+	}
 	c->uploadCopyS = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count(); // (hipMemcpy from pageable memory returns when the data is on its way from a staging buffer at the latest; the three arrays, allocation included)
 	return upload_light_list(c, prims, nPrims);
 }
@@ -762,7 +774,7 @@ int tyr_scene_build_upload(tyr_ctx* c, tyr_triangle* prims, int32_t n, const tyr
 			seconds_out3[0] = secs[0];
 		const auto t2 = std::chrono::steady_clock::now();
 		DeviceTreeLayout L;
-		rc = c->tuning.layoutOnDevice != 0 ? layout_on_device(B.nodes, nNodes, B.prims, n, L, c->stream) : TYR_ERR_UNSUPPORTED;
+		rc = c->tuning.layoutOnDevice != 0 ? layout_on_device(B.nodes, nNodes, B.prims, n, L, c->stream, (c->cfg.flags & TYR_FLAG_REFIT) != 0) : TYR_ERR_UNSUPPORTED;
 		if (rc == TYR_ERR_UNSUPPORTED) { // ... or the tree built here and laid out there
 			if (!nodes_out)
 				HIPCHK(hipMemcpy(host_nodes(), B.nodes, static_cast<size_t>(nNodes) * sizeof(tyr_bvh_node), hipMemcpyDeviceToHost));
@@ -770,7 +782,7 @@ int tyr_scene_build_upload(tyr_ctx* c, tyr_triangle* prims, int32_t n, const tyr
 		}
 		if (rc)
 			return rc;
-		if ((rc = adopt_device_layout(c, L, n)))
+		if ((rc = adopt_device_layout(c, L, n, B.nodes, nodes_out, nNodes)))
 			return rc;
 		c->uploadLayoutS = std::chrono::duration<double>(std::chrono::steady_clock::now() - t2).count();
 		c->uploadCopyS = copyS;

@@ -59,6 +59,20 @@ bool merged_render(const tyr_ctx* c);
 int flush_pending_shadow(tyr_ctx* c);
 void stage_end(tyr_ctx* c);
 int check_device_error(const tyr_ctx* c);
+// restores the caller's current device on the way out (tyr_query_*, tyr_scene_refit, as tyr_bvh_build_device does)
+struct DeviceScope {
+	int prev = -1;
+	~DeviceScope() {
+		if (prev >= 0)
+			(void)hipSetDevice(prev);
+	}
+};
+// host/refit.cpp: keep what tyr_scene_refit needs of the scene just uploaded (TYR_FLAG_REFIT).  nodes: the reference's array on
+// the host, or null (then read back from dNodes); dNodes: the same on the device, or null (then copied from nodes); slotNode /
+// pairNode: the layout pass's maps on the host, or dSlotNode on the device (adopted: freed or kept, null on return)
+int refit_keep(tyr_ctx* c, const tyr_bvh_node* nodes, const tyr_bvh_node* dNodes, int32_t nNodes, const int32_t* slotNode, int32_t*& dSlotNode, uint32_t nSlots,
+               const int32_t* pairNode, uint32_t nPairSides);
+void refit_free(tyr_ctx* c);
 // host/query.cpp: wait for the ctx's queries in flight on any stream; free their device words (tyr_destroy)
 int query_wait(tyr_ctx* c);
 void query_free(tyr_ctx* c);

@@ -33,8 +33,10 @@ struct DeviceTreeLayout {
 	float4* tris = nullptr;
 	uint32_t nQuads = 0, nStaged = 0, quadMaxStack = 0, quadRootRef = 0;
 	float rootMin[3] = { 0.f, 0.f, 0.f }, rootMax[3] = { 0.f, 0.f, 0.f };
+	int32_t* slotNode = nullptr; // wantSlots: per quad slot (record * 4 + slot) the node behind it, -1 none (hip/refit.hpp RefitPlan)
 };
-int layout_on_device(const tyr_bvh_node* dNodes, int32_t nNodes, const tyr_triangle* dPrims, int32_t nPrims, DeviceTreeLayout& out, hipStream_t stream);
+int layout_on_device(const tyr_bvh_node* dNodes, int32_t nNodes, const tyr_triangle* dPrims, int32_t nPrims, DeviceTreeLayout& out, hipStream_t stream,
+                     bool wantSlots = false);
 
 // host/bvh_layout.cpp -- flat reference nodes -> device quad nodes (+ pair nodes for the counting build) + 48-byte triangles
 // an array of floats that is NOT zeroed when it is sized: every element is written by the layout's (parallel) passes, and a
@@ -65,11 +67,14 @@ struct DeviceLayout {
 	float rootMin[3], rootMax[3];
 	uint32_t rootRef;
 	uint32_t nPairs;
+	// wantRefit only: the node whose box each quad slot (record * 4 + slot) / pair side (pair * 2 + side) holds, -1 none
+	std::vector<int32_t> slotNode, pairNode;
 };
 // returns TYR_OK or TYR_ERR_INVALID (malformed tree -- the array must be the reference's depth-first layout: first child = index
 // + 1, every subtree a contiguous range, bvh.cpp:195-202 --, non-finite geometry, too many primitives).  wantPairs: also lay out
 // the pair nodes (the counting build, BVH_DEBUG); rootRef and nPairs = 0 otherwise.  Runs on build_threads() threads; the bytes
 // do not depend on their number.
-int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_triangle* prims, int32_t nPrims, DeviceLayout& out, bool wantPairs = true);
+int build_device_layout(const tyr_bvh_node* nodes, int32_t nNodes, const tyr_triangle* prims, int32_t nPrims, DeviceLayout& out, bool wantPairs = true,
+                        bool wantRefit = false);
 
 } // namespace tyr

@@ -24,15 +24,6 @@ constexpr uint32_t kQueryTickets = 64;    // ticket words: streams served withou
 // c->dQuery: the error bits at word 0, ticket word k at (k + 1) * kQueryWordStride
 constexpr size_t kQueryWords = static_cast<size_t>(kQueryTickets + 1) * kQueryWordStride;
 
-// restores the caller's current device on the way out (as tyr_bvh_build_device does)
-struct DeviceScope {
-	int prev = -1;
-	~DeviceScope() {
-		if (prev >= 0)
-			(void)hipSetDevice(prev);
-	}
-};
-
 int query_words(tyr_ctx* c) {
 	if (c->dQuery)
 		return TYR_OK;

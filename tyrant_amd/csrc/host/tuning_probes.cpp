@@ -104,7 +104,8 @@ int tyr_get_scene_info(tyr_ctx* c, tyr_scene_info* out) {
 	out->max_quad_nodes = 1u << kQuadOrderShift;
 	out->max_prim_offset = kMaxPrimOffset;
 	const bool havePairs = (c->cfg.flags & (TYR_FLAG_COUNT_VISITS | TYR_FLAG_DEBUG_BVH)) != 0;
-	out->device_bytes = static_cast<uint64_t>(c->scene.nQuads) * 128 + (havePairs ? static_cast<uint64_t>(c->scene.nPairs) * 64 : 0) + static_cast<uint64_t>(c->scene.nPrims) * 48;
+	out->device_bytes = static_cast<uint64_t>(c->scene.nQuads) * 128 + (havePairs ? static_cast<uint64_t>(c->scene.nPairs) * 64 : 0) + static_cast<uint64_t>(c->scene.nPrims) * 48
+	                    + c->refit.bytes; // TYR_FLAG_REFIT's plan (host/refit.cpp); 0 without the flag
 	out->upload_layout_s = c->uploadLayoutS;
 	out->upload_copy_s = c->uploadCopyS;
 	out->layout_on_device = c->layoutOnDevice ? 1u : 0u;
