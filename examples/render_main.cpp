@@ -3,13 +3,16 @@
 //     camera.update(); launch_kernels(...); std::swap(ray_buffer_work, ray_buffer_next);
 // written against include/tyrant/*.h, i.e. the reference's own names over libtyrant_hip.so.
 //
-//   render_main [device] [frames] [out.ppm] [scene.ply]
+//   render_main [device] [frames] [out.ppm] [scene.ply] [aov-prefix]
+// With aov-prefix: <prefix>.albedo.pfm and <prefix>.normal.pfm, the first-hit guides (tyr_render_aov, 1 spp) of the last
+// frame rendered.
 #define TYRANT_IMPLEMENTATION
 #include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -106,6 +109,28 @@ int main(int argc, char** argv) {
 			}
 			std::fclose(fp);
 		}
+	}
+	if (argc > 5) { // denoiser guides: the camera rays of the last frame's first wavefront, 1 spp
+		const size_t n = static_cast<size_t>(W) * H;
+		float *albedo = nullptr, *normal = nullptr;
+		TYR_CHECK(hipMalloc(reinterpret_cast<void**>(&albedo), sizeof(float) * 3 * n));
+		TYR_CHECK(hipMalloc(reinterpret_cast<void**>(&normal), sizeof(float) * 3 * n));
+		TYR_CHECK(tyr_set_frame(ctx, k.frame > 1 ? k.frame - 1 : 1));
+		tyr_aov_out aov{ albedo, normal, nullptr, nullptr, nullptr };
+		TYR_CHECK(tyr_render_aov(ctx, 1, &aov, nullptr));
+		TYR_CHECK(tyr_sync(ctx));
+		std::vector<float> rgb(3 * n), rgba(4 * n, 1.0f);
+		const std::pair<float*, const char*> outs[2] = { { albedo, ".albedo.pfm" }, { normal, ".normal.pfm" } };
+		for (const auto& o : outs) {
+			TYR_CHECK(hipMemcpy(rgb.data(), o.first, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+			for (size_t i = 0; i < n; ++i)
+				for (int c = 0; c < 3; ++c)
+					rgba[4 * i + c] = rgb[3 * i + c];
+			const std::string path = std::string(argv[5]) + o.second;
+			TYR_CHECK(tyr_write_pfm(path.c_str(), rgba.data(), W, H));
+		}
+		(void)hipFree(albedo);
+		(void)hipFree(normal);
 	}
 	TYR_CHECK(tyr_destroy(ctx));
 	(void)hipFree(blit_buffer);

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -502,6 +502,38 @@ int tyr_query_error(tyr_ctx* ctx, uint32_t* bits_out, int reset);
  *   and reports device_bytes exactly as before. */
 #define TYR_REFIT_DEVICE 1u /* tyr_scene_refit: prims / bboxes are device addresses, ready on `stream` */
 int tyr_scene_refit(tyr_ctx* ctx, const tyr_triangle* prims, const tyr_bbox* bboxes, int32_t nPrims, uint32_t flags, void* stream, tyr_bvh_node* nodes_out);
+
+/* ---- AOV buffers: first-hit guides for denoisers (extension) -------------------------------------------------------------
+ * Per-pixel albedo, normal, depth and ids of the ctx's current camera at its current frame counter (tyr_counters.frame, as
+ * tyr_set_frame sets it); the sun plays no part.
+ *   Samples: with P = width * (rows the ctx owns), sample s (0 <= s < spp) of local pixel p is the camera ray k_primary makes
+ *   for ticket s * P + p with the scan-line cursor at 0 (kernel.cu:247-297: the same seed, rank interleave, stratified jitter
+ *   and thin lens) -- the camera rays of the first wavefront of a render that starts from an empty queue at that frame with
+ *   queue_size >= spp * P.  Each is traced as extend traces it: intersect_scene (kernel.cu:125-140), the seven spheres, then
+ *   the tree (tyr_query_closest with TYR_QUERY_SPHERES and tmax = VERY_FAR).
+ *   Per hit sample: albedo = shade's object colour (a sphere's colour; a triangle's (1, 1, 1), or its palette colour with
+ *   TYR_FLAG_TRIANGLE_COLORS); normal = shade's face-forwarded normal ((hit - position) / radius for a sphere with hit =
+ *   origin + direction * t, normalize(cross(e1, e2)) for a triangle; flipped when dot(n, direction) >= 0); depth = t.  A miss
+ *   adds albedo 0 and normal 0 and no depth.
+ *   Per pixel, each output optional (NULL: skipped): albedo, normal (float32 x 3): the float32 sum over s = 0 .. spp - 1 in
+ *   that order from +0, divided by (float)spp (normals are not renormalised); depth (float32): the sum of t over the hit
+ *   samples in s order divided by (float)hits, VERY_FAR (1e20) where none hit; prim, geom (int32): sample 0's identity in the
+ *   query convention (geom 0 = sphere with prim = its index, 1 = triangle with prim = its build-order index, -1 / -1 = miss).
+ *   Deterministic, bit for bit: no atomics, a fixed summation order.
+ *   Layout: full-frame DEVICE arrays indexed like the blit buffer (y * width + x); a sharded ctx writes only its own rows
+ *   (y % nranks == rank) and leaves every other entry as it was.
+ *   Ordering and state: enqueued on `stream` (NULL: the ctx's stream); the call returns once it is.  It uses the ctx's device,
+ *   restores the caller's, and touches no render state (queues, counters, frame, budget, accumulation, timings).  Like a
+ *   query, a later tyr_scene_refit waits for it, and a traversal stack overflow sets bit 1 of tyr_query_error.
+ *   TYR_ERR_INVALID: out is NULL, every pointer in it is NULL, spp == 0 or spp * P >= 2^32; TYR_ERR_NO_SCENE: nothing uploaded. */
+typedef struct tyr_aov_out {
+	float* albedo;  /* width * height x 3, or NULL */
+	float* normal;  /* width * height x 3, or NULL */
+	float* depth;   /* width * height, or NULL */
+	int32_t* prim;  /* width * height, or NULL */
+	int32_t* geom;  /* width * height, or NULL */
+} tyr_aov_out;
+int tyr_render_aov(tyr_ctx* ctx, uint32_t spp, const tyr_aov_out* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -99,6 +99,12 @@ class LayoutStats(C.Structure):
                 ("hash_pairs", c_u64), ("hash_quads", c_u64), ("hash_tris", c_u64), ("seconds", C.c_double)]
 
 
+class AovOut(C.Structure):
+    """tyr_aov_out: device pointers of the AOV buffers, NULL to skip one"""
+
+    _fields_ = [("albedo", P), ("normal", P), ("depth", P), ("prim", P), ("geom", P)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 5), ("launches", c_u64 * 5)]
 
@@ -172,6 +178,7 @@ SYMBOLS = {
     "tyr_query_any": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
+    "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
 }
 
 _libs: dict = {}
@@ -577,6 +584,30 @@ class Renderer:
         self._on_stream(stream, lambda h: self.L.tyr_query_any(self.h, n, o.data_ptr(), d.data_ptr(), tp, flags, occ.data_ptr(), h), staged)
         self._query_finish()
         return occ
+
+    def render_aov(self, spp, albedo=True, normal=True, depth=True, ids=True, stream=None) -> dict:
+        """tyr_render_aov: first-hit guide buffers of the current camera at the current frame counter, spp camera rays per pixel
+        (the rays of a render's first wavefront from an empty queue).  Returns a dict of torch tensors on this ctx's device:
+        "albedo", "normal" (H, W, 3) float32, "depth" (H, W) float32 (VERY_FAR where no sample hit), "prim", "geom" (H, W) int32
+        (sample 0's identity: geom 0 sphere, 1 triangle, -1 miss) -- those asked for.  Runs on `stream` (default: torch's current
+        stream) and returns once it is done.  A sharded ctx fills its own rows; the others are zero."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        res = {}
+        if albedo:
+            res["albedo"] = torch.zeros((self.H, self.W, 3), dtype=torch.float32, device=dev)
+        if normal:
+            res["normal"] = torch.zeros((self.H, self.W, 3), dtype=torch.float32, device=dev)
+        if depth:
+            res["depth"] = torch.zeros((self.H, self.W), dtype=torch.float32, device=dev)
+        if ids:
+            res["prim"] = torch.zeros((self.H, self.W), dtype=torch.int32, device=dev)
+            res["geom"] = torch.zeros((self.H, self.W), dtype=torch.int32, device=dev)
+        out = AovOut(*(res[k].data_ptr() if k in res else None for k in ("albedo", "normal", "depth", "prim", "geom")))
+        self._on_stream(stream, lambda h: self.L.tyr_render_aov(self.h, spp, C.byref(out), h), True)
+        self._query_finish()
+        return res
 
 
 def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: int = 0) -> np.ndarray:

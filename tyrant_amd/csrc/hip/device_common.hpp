@@ -72,6 +72,47 @@ __device__ __forceinline__ void concentric_sample_disk(float ux, float uy, float
 	dy = r * s;
 }
 
+// primary_rays' camera ray (kernel.cu:258-293): k_primary (hip/frame.hip) and the AOV pass (hip/aov.hip).  CP: a params
+// struct with FrameParams' frame, sharding and camera fields.
+// kernel.cu:258 seeds by the ticket `index`; with pixel sharding (nranks > 1) the ranks' tickets are interleaved so that
+// rows y = yl * R + r, r = 0..R-1, do not share their jitter and lens samples (nranks == 1: the reference's expression)
+template <class CP>
+__device__ __forceinline__ uint32_t camera_seed(const CP& P, uint32_t index) { return (P.frame * 147565741u) * 720898027u * (index * P.nranks + P.rank); }
+struct CameraRay {
+	f3 origin, direction;
+};
+// The ray through pixel (x, y) from its seed: the stratified jitter and the focus point (kernel.cu:266-287), then the thin
+// lens (kernel.cu:288-293) with the camera's position, right and up vectors (O, camRgt, camUpv: ld3 of P.camPos, P.camRight,
+// P.camUp).  Called as camera_lens(P, seed, camera_focus(P, seed, x, y), O, camRgt, camUpv).  (This split is the one that
+// compiles k_primary to the ISA it had with the code inline: a single function sinks the focus point behind the disk map's
+// branch, and lens vectors loaded inside camera_lens swap the operands of its last additions.)
+template <class CP>
+__device__ __forceinline__ f3 camera_focus(const CP& P, uint32_t& seed, int x, int y) {
+	float sx, sy;
+	stratified_sample(seed, sx, sy);
+	const float jitteredX = (float)x - sx; // kernel.cu:268-269 (jitter is subtracted)
+	const float jitteredY = (float)y - sy;
+	const float ndcX = (jitteredX / (float)P.W) - 0.5f;
+	const float ndcY = (((float)P.H - jitteredY) / (float)P.H) - 0.5f;
+
+	const f3 O = ld3(P.camPos), camFwd = ld3(P.camDir), camRgt = ld3(P.camRight), camUpv = ld3(P.camUp);
+	f3 towardFocus = camFwd + ndcX * camRgt + ndcY * camUpv;
+	towardFocus = normalize(towardFocus);
+	const int kFocalScale = 3; // kernel.cu:286 (`ImGui_slider_hack`: the focal distance is always tripled)
+	return O + (P.focalDistance * (float)kFocalScale) * towardFocus;
+}
+template <class CP>
+__device__ __forceinline__ CameraRay camera_lens(const CP& P, uint32_t& seed, f3 focusPoint, f3 O, f3 camRgt, f3 camUpv) {
+	const float l0 = rng_float(seed);
+	const float l1 = rng_float(seed);
+	float dx, dy;
+	concentric_sample_disk(l0, l1, dx, dy);
+	const float pLx = P.lensRadius * dx, pLy = P.lensRadius * dy;
+	const f3 lensPoint = O + camRgt * pLx + camUpv * pLy;
+	const f3 direction = normalize(focusPoint - lensPoint);
+	return CameraRay{ lensPoint, direction };
+}
+
 // kernel.cu:181-189
 __device__ __forceinline__ void orthonormal_basis_naive(f3 w, f3& u, f3& v) {
 	if ((double)fabsf(w.x) > .9)

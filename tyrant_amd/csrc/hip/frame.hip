@@ -18,35 +18,15 @@ __global__ void __launch_bounds__(kBlock) k_primary(const FrameParams P) {
 	const uint32_t nNew = (uint32_t)(room < budget ? room : budget);
 	const bool mine = index < nNew; // (a launch with nothing to generate is one block that only runs the globals below)
 	const uint32_t vslot = index + cnt; // the slot the serial order gives this ray (kernel.cu:254): what seeds its shading
-	// kernel.cu:258 seeds by the ticket `index`; with pixel sharding (nranks > 1) the ranks' tickets are interleaved so that
-	// rows y = yl * R + r, r = 0..R-1, do not share their jitter and lens samples (nranks == 1: the reference's expression)
-	uint32_t seed = (P.frame * 147565741u) * 720898027u * (index * P.nranks + P.rank);
+	uint32_t seed = camera_seed(P, index);
 
 	const uint32_t start = P.k->start_position;
 	const int x = (int)((start + index) % P.W);
 	const int yl = (int)(((start + index) / P.W) % P.localRows);
 	const int y = yl * (int)P.nranks + (int)P.rank; // nranks == 1: kernel.cu:264
 
-	float sx, sy;
-	stratified_sample(seed, sx, sy);
-	const float jitteredX = (float)x - sx; // kernel.cu:268-269 (jitter is subtracted)
-	const float jitteredY = (float)y - sy;
-	const float ndcX = (jitteredX / (float)P.W) - 0.5f;
-	const float ndcY = (((float)P.H - jitteredY) / (float)P.H) - 0.5f;
-
-	const f3 O = ld3(P.camPos), camFwd = ld3(P.camDir), camRgt = ld3(P.camRight), camUpv = ld3(P.camUp);
-	f3 towardFocus = camFwd + ndcX * camRgt + ndcY * camUpv;
-	towardFocus = normalize(towardFocus);
-	const int kFocalScale = 3; // kernel.cu:286 (`ImGui_slider_hack`: the focal distance is always tripled)
-	const f3 focusPoint = O + (P.focalDistance * (float)kFocalScale) * towardFocus;
-
-	const float l0 = rng_float(seed);
-	const float l1 = rng_float(seed);
-	float dx, dy;
-	concentric_sample_disk(l0, l1, dx, dy);
-	const float pLx = P.lensRadius * dx, pLy = P.lensRadius * dy;
-	const f3 lensPoint = O + camRgt * pLx + camUpv * pLy;
-	const f3 direction = normalize(focusPoint - lensPoint);
+	const CameraRay cr = camera_lens(P, seed, camera_focus(P, seed, x, y), ld3(P.camPos), ld3(P.camRight), ld3(P.camUp));
+	const f3 lensPoint = cr.origin, direction = cr.direction;
 
 	// extend's sphere half for this ray, while it is in registers (k_extend_spheres then only has the survivors of the
 	// last iteration to do), and the traversal's own first test (root_ref at the refill of k_trace_flat: same function,

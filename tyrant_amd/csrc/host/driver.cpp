@@ -199,21 +199,25 @@ uint32_t planned_new(const tyr_ctx* c) {
 	return static_cast<uint32_t>(std::min(room, budget));
 }
 
+void camera_basis(const tyr_ctx* c, float right[3], float up[3]) {
+	const f3 dir = ld3(c->cam.direction), camUp = ld3(c->cam.up);
+	// kernel.cu:699-700
+	const f3 r = normalize(cross(dir, camUp)) * 1.5f * (static_cast<float>(c->cfg.width) / static_cast<float>(c->cfg.height));
+	const f3 u = normalize(cross(r, dir)) * 1.5f;
+	right[0] = r.x;
+	right[1] = r.y;
+	right[2] = r.z;
+	up[0] = u.x;
+	up[1] = u.y;
+	up[2] = u.z;
+}
+
 // host prologue of launch_kernels, kernel.cu:671-718
 int stage_begin(tyr_ctx* c) {
 	if (!c->blit)
 		return TYR_ERR_NO_BUFFER;
 	c->firstTime = false;
-	const f3 dir = ld3(c->cam.direction), up = ld3(c->cam.up);
-	// kernel.cu:699-700
-	const f3 right = normalize(cross(dir, up)) * 1.5f * (static_cast<float>(c->cfg.width) / static_cast<float>(c->cfg.height));
-	const f3 upv = normalize(cross(right, dir)) * 1.5f;
-	c->camRight[0] = right.x;
-	c->camRight[1] = right.y;
-	c->camRight[2] = right.z;
-	c->camUp[0] = upv.x;
-	c->camUp[1] = upv.y;
-	c->camUp[2] = upv.z;
+	camera_basis(c, c->camRight, c->camUp);
 	// kernel.cu:702
 	bool reset = false;
 	for (int k = 0; k < 3; ++k)

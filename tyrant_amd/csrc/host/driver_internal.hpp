@@ -75,6 +75,12 @@ int refit_keep(tyr_ctx* c, const tyr_bvh_node* nodes, const tyr_bvh_node* dNodes
 void refit_free(tyr_ctx* c);
 // host/query.cpp: wait for the ctx's queries in flight on any stream; free their device words (tyr_destroy)
 int query_wait(tyr_ctx* c);
+// ... and open a launch of a query-like pass (tyr_query_*, tyr_render_aov) on the caller's `stream` (NULL: the ctx's): s = the
+// stream, qs = its entry (record qs->done behind the launch: tyr_query_error, tyr_scene_refit and tyr_destroy wait for it),
+// ticket = its chunk ticket word, cleared on s.  The ctx's device must be current.
+int query_ticket(tyr_ctx* c, void* stream, hipStream_t& s, tyr_ctx::QueryStream*& qs, uint32_t*& ticket);
+// host/driver.cpp: the camera basis of the staged prologue (kernel.cu:699-700) for the ctx's current camera
+void camera_basis(const tyr_ctx* c, float right[3], float up[3]);
 void query_free(tyr_ctx* c);
 // AoS import / export (host/staged_api.cpp): physical slots that hold a record, per segment counter array `seg` (device pointer)
 int valid_slots(const uint32_t* dSeg, std::vector<uint32_t>& slots, uint32_t* total = nullptr);

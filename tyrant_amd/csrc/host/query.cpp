@@ -73,15 +73,11 @@ int query_launch(tyr_ctx* c, bool any, uint32_t n, const float* origins, const f
 	HIPCHK(hipGetDevice(&scope.prev));
 	if (int rc = use_device(c))
 		return rc;
-	if (int rc = query_words(c))
-		return rc;
-	hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+	hipStream_t s = nullptr;
 	tyr_ctx::QueryStream* qs = nullptr;
-	if (int rc = query_stream(c, s, qs))
+	uint32_t* ticket = nullptr;
+	if (int rc = query_ticket(c, stream, s, qs, ticket))
 		return rc;
-	qs->lastUse = ++c->querySeq;
-	uint32_t* ticket = c->dQuery + (1 + qs->word) * kQueryWordStride;
-	HIPCHK(hipMemsetAsync(ticket, 0, sizeof(uint32_t), s));
 
 	QueryParams P{};
 	P.scene = c->scene;
@@ -108,6 +104,18 @@ int query_launch(tyr_ctx* c, bool any, uint32_t n, const float* origins, const f
 
 namespace tyr {
 namespace drv {
+
+int query_ticket(tyr_ctx* c, void* stream, hipStream_t& s, tyr_ctx::QueryStream*& qs, uint32_t*& ticket) {
+	if (int rc = query_words(c))
+		return rc;
+	s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+	if (int rc = query_stream(c, s, qs))
+		return rc;
+	qs->lastUse = ++c->querySeq;
+	ticket = c->dQuery + (1 + qs->word) * kQueryWordStride;
+	HIPCHK(hipMemsetAsync(ticket, 0, sizeof(uint32_t), s));
+	return TYR_OK;
+}
 
 int query_wait(tyr_ctx* c) {
 	for (const auto& q : c->queryStreams)
