@@ -5,7 +5,7 @@
 //
 //   render_main [device] [frames] [out.ppm] [scene.ply] [aov-prefix]
 // With aov-prefix: <prefix>.albedo.pfm and <prefix>.normal.pfm, the first-hit guides (tyr_render_aov, 1 spp) of the last
-// frame rendered.
+// frame rendered, and <prefix>.denoised.ppm, the accumulated frame filtered by tyr_denoise with those guides and depth.
 #define TYRANT_IMPLEMENTATION
 #include <algorithm>
 #include <chrono>
@@ -112,12 +112,17 @@ int main(int argc, char** argv) {
 	}
 	if (argc > 5) { // denoiser guides: the camera rays of the last frame's first wavefront, 1 spp
 		const size_t n = static_cast<size_t>(W) * H;
-		float *albedo = nullptr, *normal = nullptr;
+		float *albedo = nullptr, *normal = nullptr, *depth = nullptr;
 		TYR_CHECK(hipMalloc(reinterpret_cast<void**>(&albedo), sizeof(float) * 3 * n));
 		TYR_CHECK(hipMalloc(reinterpret_cast<void**>(&normal), sizeof(float) * 3 * n));
+		TYR_CHECK(hipMalloc(reinterpret_cast<void**>(&depth), sizeof(float) * n));
 		TYR_CHECK(tyr_set_frame(ctx, k.frame > 1 ? k.frame - 1 : 1));
-		tyr_aov_out aov{ albedo, normal, nullptr, nullptr, nullptr };
+		tyr_aov_out aov{ albedo, normal, depth, nullptr, nullptr };
 		TYR_CHECK(tyr_render_aov(ctx, 1, &aov, nullptr));
+		// the blit buffer (accum = NULL) filtered with those guides, tone-mapped like the surface above
+		const tyr_denoise_in din{ nullptr, albedo, normal, depth };
+		const tyr_denoise_params dp{ 5, 32.0f, 0.02f, 7, TYR_DENOISE_RESOLVE }; // the defaults, plus the tone map
+		TYR_CHECK(tyr_denoise(ctx, &din, &dp, surface, nullptr));
 		TYR_CHECK(tyr_sync(ctx));
 		std::vector<float> rgb(3 * n), rgba(4 * n, 1.0f);
 		const std::pair<float*, const char*> outs[2] = { { albedo, ".albedo.pfm" }, { normal, ".normal.pfm" } };
@@ -129,8 +134,12 @@ int main(int argc, char** argv) {
 			const std::string path = std::string(argv[5]) + o.second;
 			TYR_CHECK(tyr_write_pfm(path.c_str(), rgba.data(), W, H));
 		}
+		std::vector<float> den(4 * n);
+		TYR_CHECK(hipMemcpy(den.data(), surface, sizeof(float) * 4 * n, hipMemcpyDeviceToHost));
+		TYR_CHECK(tyr_write_ppm((std::string(argv[5]) + ".denoised.ppm").c_str(), den.data(), W, H));
 		(void)hipFree(albedo);
 		(void)hipFree(normal);
+		(void)hipFree(depth);
 	}
 	TYR_CHECK(tyr_destroy(ctx));
 	(void)hipFree(blit_buffer);

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -534,6 +534,50 @@ typedef struct tyr_aov_out {
 	int32_t* geom;  /* width * height, or NULL */
 } tyr_aov_out;
 int tyr_render_aov(tyr_ctx* ctx, uint32_t spp, const tyr_aov_out* out, void* stream);
+
+/* ---- Denoiser: edge-avoiding a-trous filter guided by the AOV buffers (extension) -----------------------------------------
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of the illumination -- the colour with the albedo divided
+ * out -- steered by the tyr_render_aov guides.  Numeric contract as the render's: one binary32 operation per operation below,
+ * in the order written, correctly rounded division, no transcendental function outside TYR_DENOISE_RESOLVE.
+ *   Inputs: full-frame DEVICE arrays indexed y * width + x: accum float4 in the blit buffer's layout (rgb sums, a = sample
+ *   count; NULL: the ctx's blit buffer), albedo and normal float32 x 3, depth float32 (VERY_FAR where no sample hit).
+ *   Preparation, per pixel: A = accum.a; valid = A > 0 && depth < VERY_FAR; c = rgb / A; d_k = albedo_k > 0 ? albedo_k : 1;
+ *   u_k = c_k / d_k; iz = 1 / depth (valid pixels only).
+ *   Pass j = 0 .. passes - 1, step s = 2^j, for each valid centre p (u: the previous pass's result; normals, depths and
+ *   validity never change): kc_j = kc * 4^j with kc = 1 / (sigma_color * sigma_color) and kz = 1 / (sigma_depth *
+ *   sigma_depth), both float32 on the host.  Taps dy = -2..2 (outer), dx = -2..2 (inner) at q = (x + dx s, y + dy s); q outside
+ *   the frame or not valid is skipped (no clamping, no mirroring).  Per tap: h = H[dx+2] * H[dy+2], H = {1/16, 1/4, 3/8, 1/4,
+ *   1/16}; e = u_q - u_p, dc2 = e.x*e.x + e.y*e.y + e.z*e.z; g = max(0, n_p . n_q) (x, y, z left to right) squared
+ *   normal_power_log2 times; r = (z_q - z_p) * iz_p, xz = (r*r) * kz; den = (1 + dc2*kc_j) * (1 + xz); w = (h*g) / den;
+ *   S_k += w * u_q_k, Wsum += w from +0 in tap order.  The result is S / Wsum when Wsum > 0, else u_p.
+ *   A background pixel (A > 0, no sample hit) passes every pass unchanged and is never a tap; A == 0 gives (0, 0, 0, 0).
+ *   Output: float4 per pixel, out_k = v_k * d_k with v the last pass's result and out.a = 1 -- a frame in the blit buffer's
+ *   layout with one sample per pixel.  With TYR_DENOISE_RESOLVE every pixel with A > 0 gets tyr_resolve's tone map of that
+ *   frame instead (bit for bit what tyr_resolve writes for a ctx whose blit buffer holds it).
+ *   Parameters (NULL: the defaults): passes 1..8 (5), sigma_color (32), sigma_depth (0.02), normal_power_log2 0..10 (7);
+ *   the sigmas were chosen on the Cornell box (DESIGN.md "Denoiser").
+ *   Ordering and state: enqueued on `stream` (NULL: the ctx's stream); the call returns once it is.  It uses the ctx's device,
+ *   restores the caller's, needs no scene and touches no render state (queues, counters, frame, budget, accumulation,
+ *   timings); the ctx's sharding plays no part (a sharded caller gathers whole frames first).  The ctx owns the scratch (48
+ *   bytes per pixel, allocated by the first call, freed by tyr_destroy, not in tyr_scene_info's device_bytes); calls on one
+ *   ctx are therefore ordered with each other whatever their streams.
+ *   TYR_ERR_INVALID: in, a guide or device_rgba_out is NULL; passes or normal_power_log2 out of range; an unknown flag; a sigma
+ *   not positive and finite, or kc * 4^(passes - 1) or kz not finite.  TYR_ERR_NO_BUFFER: accum is NULL and no blit buffer. */
+typedef struct tyr_denoise_in {
+	const float* accum;  /* width * height x 4, or NULL: the ctx's blit buffer */
+	const float* albedo; /* width * height x 3 */
+	const float* normal; /* width * height x 3 */
+	const float* depth;  /* width * height */
+} tyr_denoise_in;
+#define TYR_DENOISE_RESOLVE 1u /* tyr_denoise_params.flags: tone-map the output as tyr_resolve does */
+typedef struct tyr_denoise_params {
+	uint32_t passes;
+	float sigma_color;
+	float sigma_depth;
+	uint32_t normal_power_log2;
+	uint32_t flags;
+} tyr_denoise_params;
+int tyr_denoise(tyr_ctx* ctx, const tyr_denoise_in* in, const tyr_denoise_params* params, void* device_rgba_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,9 @@ TYR_ERR_DEVICE = -6
 TYR_ERR_UNSUPPORTED = -7
 TYR_QUERY_SPHERES = 1
 TYR_REFIT_DEVICE = 1
+TYR_DENOISE_RESOLVE = 1
+# tyr_denoise's defaults (host/denoise.cpp)
+DENOISE_PASSES, DENOISE_SIGMA_COLOR, DENOISE_SIGMA_DEPTH, DENOISE_NORMAL_POWER_LOG2 = 5, 32.0, 0.02, 7
 TYR_DIST_GATHER, TYR_DIST_REDUCE = 0, 1
 TYR_DIST_ID_BYTES = 128
 KERNEL_NAMES = ("primary", "extend", "shade", "connect", "resolve")
@@ -103,6 +106,16 @@ class AovOut(C.Structure):
     """tyr_aov_out: device pointers of the AOV buffers, NULL to skip one"""
 
     _fields_ = [("albedo", P), ("normal", P), ("depth", P), ("prim", P), ("geom", P)]
+
+
+class DenoiseIn(C.Structure):
+    """tyr_denoise_in: device pointers of the frame (NULL: the ctx's blit buffer) and its guides"""
+
+    _fields_ = [("accum", P), ("albedo", P), ("normal", P), ("depth", P)]
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("passes", c_u32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("normal_power_log2", c_u32), ("flags", c_u32)]
 
 
 class Timings(C.Structure):
@@ -179,6 +192,7 @@ SYMBOLS = {
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
+    "tyr_denoise": (C.c_int, [P, P, P, P, P]),
 }
 
 _libs: dict = {}
@@ -608,6 +622,31 @@ class Renderer:
         self._on_stream(stream, lambda h: self.L.tyr_render_aov(self.h, spp, C.byref(out), h), True)
         self._query_finish()
         return res
+
+    def denoise(self, albedo, normal, depth, accum=None, passes=DENOISE_PASSES, sigma_color=DENOISE_SIGMA_COLOR, sigma_depth=DENOISE_SIGMA_DEPTH,
+                normal_power_log2=DENOISE_NORMAL_POWER_LOG2, resolve=False, stream=None):
+        """tyr_denoise: the edge-avoiding a-trous filter of a frame guided by render_aov's buffers.  albedo, normal (H, W, 3),
+        depth (H, W) and accum (H, W, 4; None: this ctx's blit buffer) are contiguous float32 tensors on this ctx's device.
+        Returns an (H, W, 4) float32 tensor: the filtered frame in the blit buffer's layout with one sample per pixel, or
+        with resolve=True tone-mapped as resolve_into writes it.  Runs on `stream` (default: torch's current stream) and
+        returns without waiting for it."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n = self.H * self.W
+        ins = {"albedo": (albedo, 3 * n), "normal": (normal, 3 * n), "depth": (depth, n), "accum": (accum, 4 * n)}
+        for what, (t, size) in ins.items():
+            if t is None and what == "accum":
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != size:
+                raise ValueError(f"{what}: a contiguous float32 tensor of {size} values on {dev}")
+        out = torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev)
+        din = DenoiseIn(None if accum is None else accum.data_ptr(), albedo.data_ptr(), normal.data_ptr(), depth.data_ptr())
+        prm = DenoiseParams(passes, sigma_color, sigma_depth, normal_power_log2, TYR_DENOISE_RESOLVE if resolve else 0)
+        self._on_stream(stream, lambda h: self.L.tyr_denoise(self.h, C.byref(din), C.byref(prm), out.data_ptr(), h), True)
+        if stream is not None:
+            out.record_stream(stream)  # written there: the allocator must not hand its memory out before that stream is done
+        return out
 
 
 def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: int = 0) -> np.ndarray:

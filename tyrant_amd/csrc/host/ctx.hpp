@@ -103,6 +103,11 @@ struct tyr_ctx {
 	uint64_t querySeq = 0;
 	std::vector<QueryStream> queryStreams;
 
+	// tyr_denoise (host/denoise.cpp): scratch for width * height pixels -- two illumination buffers, then the packed guide --
+	// allocated by the first call, and the event behind the last call (the next one waits for it, on whatever stream)
+	float4* dDenoise = nullptr;
+	hipEvent_t denoiseDone = nullptr;
+
 	// TYR_FLAG_REFIT: what every scene upload keeps for tyr_scene_refit (host/refit.cpp)
 	tyr::RefitPlan refit{};
 

@@ -501,6 +501,7 @@ int tyr_destroy(tyr_ctx* c) {
 	if (c->stream)
 		(void)hipStreamSynchronize(c->stream);
 	query_free(c);
+	denoise_free(c);
 	free_rayq(c->q[0]);
 	free_rayq(c->q[1]);
 	for (auto& sq : c->shadow) {
