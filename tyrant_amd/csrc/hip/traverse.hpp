@@ -327,6 +327,70 @@ struct LdsStack {
 		}
 		return true;
 	}
+	// The flat descent's pop as selects: a lane that must pop (`popping`) takes its top entry if the entry's distance is
+	// below `bound` (the pop-time half of Bbox.h:61), stays at kRefPop if not, and is done when its stack is empty; other
+	// lanes keep `ref`.  While no popping lane has entries outside LDS (the common case) every lane reads one LDS entry --
+	// its top when it pops, row 0 otherwise -- and keeps or drops it with selects: the branch form (`if (ref == kRefPop)
+	// { if (pop(..)) { if (t < bound) .. } else .. }`) cost the descent trip three exec-mask save / branch / restore
+	// sequences around one ds_read.
+	__device__ __forceinline__ void pop_select(bool popping, uint32_t& ref, float bound) {
+		if (LDS_DEPTH > 0 && __builtin_amdgcn_ballot_w64(popping && n > LDS_DEPTH) == 0ull) {
+			const bool take = popping && n > 0;
+			uint32_t r;
+			float t;
+			lds_get(take ? n - 1 : 0, r, t);
+			ref = popping ? (n == 0 ? kRefDone : (t < bound ? r : kRefPop)) : ref;
+			n = take ? n - 1 : n;
+			return;
+		}
+		if (popping) { // (pop's own path for a wave with a lane in the private part)
+			if (n == 0) {
+				ref = kRefDone;
+			} else {
+				--n;
+				uint32_t r;
+				float t;
+				if (LDS_DEPTH > 0 && n < LDS_DEPTH) {
+					lds_get(n, r, t);
+				} else {
+					r = spillRef[n - LDS_DEPTH];
+					t = WITH_T ? spillT[n - LDS_DEPTH] : -__builtin_inff();
+				}
+				if (t < bound)
+					ref = r;
+			}
+		}
+	}
+	// The pushes of one quad step from its slots in NODE order and each slot's visit rank (quad_ranks; hr = the hit slots'
+	// ranks as a bit set, first = the lowest): every hit slot but the first goes onto the stack, farthest first (push3's
+	// order).  In LDS the depth of each entry is known up front -- n + the number of hits ranked after it -- so the four
+	// slots are written in place, in any order, and no value is moved into visit order: that reordering (four references,
+	// four distances, four hit masks through two levels of selects) was a third of a descent trip's instructions.
+	__device__ __forceinline__ void push_ranked(const uint32_t* ref, const float* t, const unsigned long long* hit, const uint32_t* rank, uint32_t hr, uint32_t first) {
+		if (LDS_DEPTH >= 3 && __builtin_amdgcn_ballot_w64(n > LDS_DEPTH - 3) == 0ull) {
+			const uint32_t after = hr >> 1; // bit k: rank k + 1 was hit
+#pragma unroll
+			for (int s = 0; s < 4; ++s)
+				if (__builtin_amdgcn_inverse_ballot_w64(hit[s]) && rank[s] != first)
+					lds_put(n + (int)__popc(after >> rank[s]), ref[s], t[s]);
+			n += (int)__popc(hr) - (hr != 0u ? 1 : 0);
+			return;
+		}
+		// a lane may leave the LDS part: one push at a time, in visit order (a wave's first few trips at most, on deep trees)
+		uint32_t oref[4];
+		float ot[4];
+#pragma unroll
+		for (uint32_t k = 1; k < 4; ++k) {
+			oref[k] = rank[0] == k ? ref[0] : rank[1] == k ? ref[1] : rank[2] == k ? ref[2] : ref[3];
+			ot[k] = rank[0] == k ? t[0] : rank[1] == k ? t[1] : rank[2] == k ? t[2] : t[3];
+		}
+		if ((hr & 8u) && (hr & 7u))
+			push(oref[3], ot[3]);
+		if ((hr & 4u) && (hr & 3u))
+			push(oref[2], ot[2]);
+		if ((hr & 2u) && (hr & 1u))
+			push(oref[1], ot[1]);
+	}
 	// up to three pushes of one quad step (a first, c last); mX = the lanes that push entry X
 	__device__ __forceinline__ void push3(unsigned long long ma, uint32_t ra, float ta, unsigned long long mb, uint32_t rb, float tb, unsigned long long mc, uint32_t rc, float tc) {
 		if (LDS_DEPTH >= 3 && __builtin_amdgcn_ballot_w64(n > LDS_DEPTH - 3) == 0ull) {
@@ -478,7 +542,7 @@ __device__ __forceinline__ lanemask lanes_where(bool p) { return __builtin_amdgc
 __device__ __forceinline__ bool lane_in(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 __device__ __forceinline__ lanemask mask_select(lanemask sel, lanemask a, lanemask b) { return (sel & a) | (~sel & b); }
 
-struct QuadHits { // in visit order
+struct QuadHits { // in visit order (ORDERED) or in node order (not ORDERED; quad_ranks gives each slot's place in the visit order)
 	uint32_t ref[4];
 	float t[4];
 	lanemask hit[4];
@@ -493,7 +557,9 @@ __device__ __forceinline__ lanemask slab_any(const RayConst& r, float lox, float
 
 // FAST: every lane of the wave has a finite 1/d (the caller decides once per wave, not per box: a
 // per-lane choice made the compiler emit both paths with exec juggling around each of the four tests).
-// ORDERED: closest-hit needs the reference's visit order; any-hit (bvh.h:213-256) does not depend on it.
+// ORDERED: the slots come back reordered into the reference's visit order; not ORDERED: in node order, for callers that
+// need no reordering (any hit, bvh.h:213-256, does not depend on the order) or that take the order as ranks (quad_ranks:
+// k_trace_flat's descent, closest hit included, pushes each slot straight to its place).
 template <bool FAST, bool ORDERED, bool STAGED = false, int STAGE_STRIDE = (int)kStagedNodes>
 __device__ __forceinline__ QuadHits test_quad(const float4* __restrict__ quads, uint32_t ref, const RayConst& r, float dist, const float4* staged = nullptr, uint32_t nStaged = 0) {
 	const uint32_t idx = ref & kQuadIndexMask;
@@ -565,6 +631,22 @@ __device__ __forceinline__ QuadHits test_quad(const float4* __restrict__ quads, 
 	o.hit[2] = mask_select(BT, LH0, RH0);
 	o.hit[3] = mask_select(BT, LH1, RH1);
 	return o;
+}
+
+// The reference's visit order of a quad node's four slots as RANKS (0 = visited first), for code that does not need the
+// slots' values reordered (test_quad<.., ORDERED = false> returns them in node order): near group first, near slot first
+// inside each group, i.e. rank(slot) = slot ^ (2 bT + bG) with bT / bG = "the ray runs against the split axis" of the node /
+// of the slot's group (the order bits of an interior reference: kQuadOrderShift + 0 / + 2 / + 4; test_quad's selects).
+// signBits: bit a = the ray's direction is negative along axis a (bit 3, the synthetic nodes' axis code, is clear).
+__device__ __forceinline__ void quad_ranks(uint32_t ref, uint32_t signBits, uint32_t* rank) {
+	const uint32_t bT = __builtin_amdgcn_ubfe(signBits, __builtin_amdgcn_ubfe(ref, kQuadOrderShift, 2u), 1u);
+	const uint32_t bL = __builtin_amdgcn_ubfe(signBits, __builtin_amdgcn_ubfe(ref, kQuadOrderShift + 2u, 2u), 1u);
+	const uint32_t bR = __builtin_amdgcn_ubfe(signBits, __builtin_amdgcn_ubfe(ref, kQuadOrderShift + 4u, 2u), 1u);
+	const uint32_t xL = (bT << 1) | bL, xR = (bT << 1) | bR;
+	rank[0] = xL;
+	rank[1] = xL ^ 1u;
+	rank[2] = xR ^ 2u;
+	rank[3] = xR ^ 3u;
 }
 
 struct VisitCount {

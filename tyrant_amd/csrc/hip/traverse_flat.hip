@@ -495,41 +495,49 @@ __device__ __forceinline__ uint32_t quad_or(uint32_t v) {
 }
 template <int K>
 __device__ __forceinline__ float quad_bcast_f(float v) { return __uint_as_float(quad_perm_u<K * 0x55>(__float_as_uint(v))); }
-// wide_drain is a function of its own (below): its pointer arguments arrive as GENERIC pointers, and a load through one is
-// a flat load -- it counts on vmcnt AND lgkmcnt, so that every wait for a stack entry in LDS also waits for the records in
-// flight.  These say what the kernel knows: the scene and the queues are global memory.
+// wide_drain is a function of its own (below).  What it reads and writes in global memory it reaches through the kernel's
+// argument segment, whose address the kernel passes (a function called from a kernel is not given that address:
+// __builtin_amdgcn_kernarg_segment_ptr() answers 0 there), made wave-uniform with readfirstlane so that the arguments are
+// scalar loads, and with explicitly GLOBAL pointers: a generic pointer makes a flat access, which counts on vmcnt AND
+// lgkmcnt -- every wait for a stack entry in LDS would also wait for the records in flight -- and a pointer that arrives as
+// a function argument sits in vector registers, so that every address is 64-bit vector arithmetic.  A uniform base plus a
+// 32-bit byte offset is one global_load with the base in scalar registers.
 #define TYR_GLOBAL __attribute__((address_space(1)))
 typedef float v2f_t __attribute__((ext_vector_type(2)));
 typedef float v4f_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float2 gload_f2(const float* p) {
-	const v2f_t v = *(const TYR_GLOBAL v2f_t*)p;
+__device__ __forceinline__ const TYR_GLOBAL char* gbytes(const void* base, uint32_t byteOffset) { return (const TYR_GLOBAL char*)base + byteOffset; }
+__device__ __forceinline__ float2 gload_f2(const void* base, uint32_t byteOffset) {
+	const v2f_t v = *(const TYR_GLOBAL v2f_t*)gbytes(base, byteOffset);
 	return make_float2(v.x, v.y);
 }
-__device__ __forceinline__ float4 gload_f4(const float4* p) {
-	const v4f_t v = *(const TYR_GLOBAL v4f_t*)p;
+__device__ __forceinline__ float4 gload_f4(const void* base, uint32_t byteOffset) {
+	const v4f_t v = *(const TYR_GLOBAL v4f_t*)gbytes(base, byteOffset);
 	return make_float4(v.x, v.y, v.z, v.w);
 }
-__device__ __forceinline__ uint32_t gload_u(const float* p) { return *(const TYR_GLOBAL uint32_t*)p; }
+__device__ __forceinline__ uint32_t gload_u(const void* base, uint32_t byteOffset) { return *(const TYR_GLOBAL uint32_t*)gbytes(base, byteOffset); }
+// (a primitive offset is below kMaxPrimOffset = 2^26, so its 48-byte record lies within the first 3 GiB: a 32-bit byte offset)
 __device__ __forceinline__ TriData triangle_gload(const float4* tris, uint32_t prim) {
+	const uint32_t at = prim * 48u;
 	TriData d;
-	d.a = gload_f4(tris + 3 * prim + 0);
-	d.b = gload_f4(tris + 3 * prim + 1);
-	d.c = make_float4(__uint_as_float(gload_u(reinterpret_cast<const float*>(tris + 3 * prim + 2))), 0.0f, 0.0f, 0.0f); // (the tests read c.x only)
+	d.a = gload_f4(tris, at);
+	d.b = gload_f4(tris, at + 16u);
+	d.c = make_float4(__uint_as_float(gload_u(tris, at + 32u)), 0.0f, 0.0f, 0.0f); // (the tests read c.x only)
 	return d;
 }
 constexpr uint32_t kWideRays = 16;        // a wave switches to four lanes per ray once it holds at most this many
 constexpr int kWideStackEntries = 4 * 12; // the four lanes' LDS columns of a group, as one stack
 
 // ==== the drain, four lanes to a ray ====
-		// Once the queue is used up a wave finishes its last rays a few lanes wide while every step still costs a full wave's
-	// instructions: ~330 per quad step (four box tests, ordering, up to three pushes, the leaf's primitives one trip each),
-	// five such waves to a SIMD -- the first third of a launch's drain is bound by exactly that.  Here the wave's (at most
-	// 16) rays are dealt one to each aligned group of four lanes: a lane tests ONE child box of the quad node (and one
-	// primitive of a leaf), the four answers meet through DPP quad_perm moves, every lane of the group derives the same
-	// visit order test_quad derives, and the group's stack is its four LDS columns taken as one.  Same boxes, same order,
-	// same accept rule, same answers -- at a quarter of the instructions per step.
+// Once the queue is used up a wave finishes its last rays a few lanes wide while every step still costs a full wave's
+// instructions: ~330 per quad step (four box tests, ordering, up to three pushes, the leaf's primitives one trip each),
+// five such waves to a SIMD -- the first third of a launch's drain is bound by exactly that.  Here the wave's (at most
+// 16) rays are dealt one to each aligned group of four lanes: a lane tests ONE child box of the quad node (and one
+// primitive of a leaf), the four answers meet through DPP quad_perm moves, every lane of the group derives the same
+// visit order test_quad derives, and the group's stack is its four LDS columns taken as one.  Same boxes, same order,
+// same accept rule, same answers -- at a quarter of the instructions per step.
 // (A function of its own, not inlined: inside k_trace_flat its scalar registers competed with the feed loop's -- 35 instead
-// of 16 spilled there, 2.5 % of a render whether or not a wave ever got here.)
+// of 16 spilled there, 2.5 % of a render whether or not a wave ever got here.)  The ray's state arrives as separate values,
+// in registers: as one by-value struct it went through the stack (scratch stores in the kernel, scratch loads here).
 #ifdef TYR_LAUNCH_ANATOMY
 #define TYR_WIDE_STEPS_PARAM , uint32_t& wideSteps
 #define TYR_WIDE_STEPS_ARG , wideSteps
@@ -537,23 +545,16 @@ constexpr int kWideStackEntries = 4 * 12; // the four lanes' LDS columns of a gr
 #define TYR_WIDE_STEPS_PARAM
 #define TYR_WIDE_STEPS_ARG
 #endif
-struct WideState {
-	float rox, roy, roz, rdx, rdy, rdz, rix, riy, riz, dist;
-	uint32_t ref, slot, flags; // flags: 1 regular, 2 hitTri, 4 isShadow, 8 occluded, 16 live
-	int prim, n;
-};
+constexpr uint32_t kWideRegular = 1u, kWideHitTri = 2u, kWideShadow = 4u, kWideOccluded = 8u, kWideLive = 16u; // wide_drain's flags
 template <int STACK_LDS>
-__device__ __attribute__((noinline, cold)) uint32_t wide_drain(const float4* __restrict__ quads, const float4* __restrict__ tris, const float4* __restrict__ shadowColor, const float4* __restrict__ shadowDyzCdIx,
-                                                         float2* __restrict__ workHit, float4* __restrict__ blit, typename LdsStack<STACK_LDS, true>::entry_t* smem_, WideState w, uint32_t passes TYR_WIDE_STEPS_PARAM) {
+__device__ __attribute__((noinline, cold)) uint32_t wide_drain(unsigned long long kernarg, typename LdsStack<STACK_LDS, true>::lds_column_t smem_, float rox, float roy, float roz, float rdx, float rdy, float rdz, float rix, float riy, float riz, float dist,
+                                                         uint32_t ref, uint32_t slot, int prim, uint32_t flags, int n, uint32_t passes TYR_WIDE_STEPS_PARAM) {
+	const unsigned long long ka = (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)kernarg) | ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(kernarg >> 32)) << 32);
+	const FrameParams& P = *(const FrameParams*)(const __attribute__((address_space(4))) FrameParams*)ka;
 	const uint32_t lane = lane_id();
 	const unsigned long long below = (1ull << lane) - 1ull;
-	float rox = w.rox, roy = w.roy, roz = w.roz, rdx = w.rdx, rdy = w.rdy, rdz = w.rdz, rix = w.rix, riy = w.riy, riz = w.riz, dist = w.dist;
-	uint32_t ref = w.ref, slot = w.slot;
-	int prim = w.prim;
-	bool regular = (w.flags & 1u) != 0u, hitTri = (w.flags & 2u) != 0u, isShadow = (w.flags & 4u) != 0u, occluded = (w.flags & 8u) != 0u;
-	const bool live = (w.flags & 16u) != 0u;
+	const bool live = (flags & kWideLive) != 0u;
 	uint32_t visible = 0;
-	struct { int n; } st = { w.n };
 	const uint32_t sub = lane & 3u, grp = lane >> 2;
 	const unsigned long long lm = __ballot(live);
 	const uint32_t nl = (uint32_t)__popcll(lm);
@@ -574,13 +575,15 @@ __device__ __attribute__((noinline, cold)) uint32_t wide_drain(const float4* __r
 	ref = pull_u(ref);
 	slot = pull_u(slot);
 	prim = (int)pull_u((uint32_t)prim);
-	const uint32_t fl = pull_u((regular ? 1u : 0u) | (hitTri ? 2u : 0u) | (isShadow ? 4u : 0u) | (occluded ? 8u : 0u));
-	regular = (fl & 1u) != 0u, hitTri = (fl & 2u) != 0u, isShadow = (fl & 4u) != 0u, occluded = (fl & 8u) != 0u;
-	int n = (int)pull_u((uint32_t)st.n);
+	const uint32_t fl = pull_u(flags);
+	const bool regular = (fl & kWideRegular) != 0u, isShadow = (fl & kWideShadow) != 0u;
+	bool hitTri = (fl & kWideHitTri) != 0u, occluded = (fl & kWideOccluded) != 0u;
+	n = (int)pull_u((uint32_t)n);
 	// the ray's stack (at most STACK_LDS entries, all in its old lane's LDS column) moves into the group's four columns:
 	// entry e at row e / 4 of lane e % 4
 	typedef typename LdsStack<STACK_LDS, true>::entry_t entry_t;
-	entry_t* const column0 = smem_ + (threadIdx.x >> 8) * (STACK_LDS * kBlock) + (threadIdx.x & 255u & ~63u); // row 0 of this wave's lane 0 (a block is one or more 256-thread parts, each with its own [STACK_LDS][256] stack array)
+	typedef typename LdsStack<STACK_LDS, true>::lds_column_t lds_ptr_t;
+	const lds_ptr_t column0 = smem_ + (threadIdx.x >> 8) * (STACK_LDS * kBlock) + (threadIdx.x & 255u & ~63u); // row 0 of this wave's lane 0 (a block is one or more 256-thread parts, each with its own [STACK_LDS][256] stack array)
 	entry_t moved[STACK_LDS / 4];
 #pragma unroll
 	for (int row = 0; row < STACK_LDS / 4; ++row) {
@@ -593,10 +596,15 @@ __device__ __attribute__((noinline, cold)) uint32_t wide_drain(const float4* __r
 		if (gActive && 4 * row + (int)sub < n)
 			column0[row * kBlock + lane] = moved[row];
 	wave_lds_order();
-	entry_t* const gstack = column0 + (lane & ~3u); // entry e: gstack[(e >> 2) * kBlock + (e & 3)]
+	const lds_ptr_t gstack = column0 + (lane & ~3u); // entry e: gstack[(e >> 2) * kBlock + (e & 3)]
+	auto entry_at = [&](int e) { return gstack + (((uint32_t)e >> 2) * kBlock + ((uint32_t)e & 3u)); };
 	const RayConst r = { mk3(rox, roy, roz), mk3(rdx, rdy, rdz), mk3(rix, riy, riz), rix < 0, riy < 0, riz < 0 };
 	const uint32_t signBits = (r.nx ? 1u : 0u) | (r.ny ? 2u : 0u) | (r.nz ? 4u : 0u);
-	bool wideOverflow = false;
+	// this lane's child slot of a quad node: its box planes' byte offset in the record (x at +0, y at +32, z at +64), its
+	// reference's (+96), and where the order bits of its group sit in an interior reference (kQuadOrderShift + 2 / + 4)
+	const uint32_t boxAt = (sub >> 1) * 16u + (sub & 1u) * 8u, refAt = 96u + 4u * sub, groupBits = kQuadOrderShift + 2u + 2u * (sub >> 1);
+	const float4* const quads = P.scene.quads;
+	const float4* const tris = P.scene.tris;
 	// The loop below is written with SELECTS, not branches.  A SIMD issues one scalar instruction per four cycles whichever of
 	// its waves it comes from; the first form of this loop (lane-varying `if`s: pop / node / leaf / four accepts per leaf /
 	// fast or generic box test) compiled to ~300 scalar instructions per step -- exec-mask save, branch, restore around
@@ -605,8 +613,15 @@ __device__ __attribute__((noinline, cold)) uint32_t wide_drain(const float4* __r
 	// bound by the scalar pipe, not by memory latency and not by the vector pipe.  Here every lane runs every block a wave
 	// needs at all (wave-uniform branches on ballots), state changes are selects, loads of lanes that have nothing to load
 	// go to record 0.  A lane that turns a node into a leaf tests the leaf in the same trip.
-	const bool allRegular = __ballot(gActive && !regular) == 0ull; // (the generic box test is exact for regular rays too: one path for the wave)
-	while (__ballot(gActive) != 0ull) {
+	// The state a ray carries from trip to trip and tests as a whole (active, took a triangle, occluded) is held as wave-wide
+	// lane masks in scalar registers: as `bool`s that live across the loop's back edge each became an exec-style mask whose
+	// every update was merged with and-not / and / or sequences at each join of the loop body, and the ballot of one went
+	// through a 0/1 vector register and a second comparison.
+	const lanemask shadowM = __ballot(isShadow);
+	lanemask act = __ballot(gActive), hitM = __ballot(hitTri), occM = __ballot(occluded);
+	bool wideOverflow = false;
+	const bool allRegular = (act & ~__ballot(regular)) == 0ull; // (the generic box test is exact for regular rays too: one path for the wave)
+	while (act != 0ull) {
 		if (kGuardPasses && ++passes > kMaxPasses)
 			break;
 #ifdef TYR_LAUNCH_ANATOMY
@@ -614,89 +629,95 @@ __device__ __attribute__((noinline, cold)) uint32_t wide_drain(const float4* __r
 #endif
 		// ---- pop: the group's top entry (entry 0 when it has none) ----
 		{
-			const bool popping = gActive && ref == kRefPop;
+			const bool popping = lane_in(act & lanes_where(ref == kRefPop));
 			const bool has = n > 0;
-			const int top = has ? n - 1 : 0;
-			const entry_t e = gstack[(top >> 2) * kBlock + (top & 3)];
+			const entry_t e = *entry_at(has ? n - 1 : 0);
 			const uint32_t popped = !has ? kRefDone : (__uint_as_float(e.y) < dist ? e.x : kRefPop); // the pop-time half of Bbox.h:61
 			ref = popping ? popped : ref;
 			n = (popping && has) ? n - 1 : n;
 		}
 		// ---- one quad node: this lane's child box ----
-		const bool atNode = gActive && (int)ref >= 0;
-		if (__ballot(atNode) != 0ull) {
-			const uint32_t idx = atNode ? (ref & kQuadIndexMask) : 0u, meta = ref >> kQuadOrderShift;
-			const float* qf = reinterpret_cast<const float*>(quads + 8 * idx);
-			const uint32_t at = (sub >> 1) * 4u + (sub & 1u) * 2u;
-			const float2 bx = gload_f2(qf + at);
-			const float2 by = gload_f2(qf + 8 + at);
-			const float2 bz = gload_f2(qf + 16 + at);
-			const uint32_t cref = gload_u(qf + 24 + sub);
+		const lanemask nodeM = act & lanes_where((int)ref >= 0);
+		if (nodeM != 0ull) {
+			const bool atNode = lane_in(nodeM);
+			const uint32_t node = (atNode ? (ref & kQuadIndexMask) : 0u) * 128u; // (2^25 records of 128 bytes: a 32-bit byte offset)
+			const float2 bx = gload_f2(quads, node + boxAt);
+			const float2 by = gload_f2(quads, node + boxAt + 32u);
+			const float2 bz = gload_f2(quads, node + boxAt + 64u);
+			const uint32_t cref = gload_u(quads, node + refAt);
 			float t;
-			bool h;
+			lanemask H;
 			if (allRegular)
-				h = slab_fast(r, bx.x, bx.y, by.x, by.y, bz.x, bz.y, dist, t);
+				H = slab_fast_mask(r, bx.x, bx.y, by.x, by.y, bz.x, bz.y, dist, t);
 			else
-				h = slab_test(r, r.nx ? bx.y : bx.x, r.nx ? bx.x : bx.y, r.ny ? by.y : by.x, r.ny ? by.x : by.y, r.nz ? bz.y : bz.x, r.nz ? bz.x : bz.y, dist, t);
-			h = h && atNode;
-			// this slot's place in the reference's visit order (test_quad: near slot first inside each group, near group first)
-			const uint32_t aT = meta & 3u, aL = (meta >> 2) & 3u, aR = (meta >> 4) & 3u;
-			const uint32_t bT = (signBits >> aT) & 1u, bG = (signBits >> ((sub >> 1) ? aR : aL)) & 1u;
-			const uint32_t rank = 2u * ((sub >> 1) ^ bT) + ((sub & 1u) ^ bG);
+				H = lanes_where(slab_test(r, r.nx ? bx.y : bx.x, r.nx ? bx.x : bx.y, r.ny ? by.y : by.x, r.ny ? by.x : by.y, r.nz ? bz.y : bz.x, r.nz ? bz.x : bz.y, dist, t));
+			const bool h = lane_in(H & nodeM);
+			// this slot's place in the reference's visit order (test_quad: near slot first inside each group, near group first):
+			// rank = slot ^ (2 bT + bG), bT / bG = "the ray runs against the split axis" of the node / of this slot's group
+			const uint32_t bT = __builtin_amdgcn_ubfe(signBits, __builtin_amdgcn_ubfe(ref, kQuadOrderShift, 2u), 1u);
+			const uint32_t bG = __builtin_amdgcn_ubfe(signBits, __builtin_amdgcn_ubfe(ref, groupBits, 2u), 1u);
+			const uint32_t rank = sub ^ ((bT << 1) | bG);
 			const uint32_t hr = quad_or(h ? (1u << rank) : 0u); // the group's hits, in visit order
-			const uint32_t first = (uint32_t)__ffs((int)(hr | 16u)) - 1u; // (4 when nothing was hit: no lane's rank)
+			const bool nearest = h && (hr & (0u - hr)) == (1u << rank); // this lane holds the group's first hit in visit order
 			// the others go onto the stack farthest first, so that the nearest pops first (push3's order)
-			const int e = n + (int)__popc(hr >> (rank + 1u));
-			if (h && rank != first && e < kWideStackEntries)
-				gstack[(e >> 2) * kBlock + (e & 3)] = make_uint2(cref, __float_as_uint(t));
-			int n2 = n + (int)__popc(hr) - (hr != 0u ? 1 : 0);
-			wideOverflow = wideOverflow || (atNode && n2 > kWideStackEntries);
-			n2 = n2 > kWideStackEntries ? kWideStackEntries : n2;
-			const uint32_t nearest = quad_or((h && rank == first) ? cref : 0u);
-			ref = atNode ? (hr == 0u ? kRefPop : nearest) : ref;
-			n = atNode ? n2 : n;
+			const int e = n + (int)__popc(hr >> rank >> 1);
+			if (h && !nearest && e < kWideStackEntries)
+				*entry_at(e) = make_uint2(cref, __float_as_uint(t));
+			const int n2 = n + (int)__popc(hr) - (hr != 0u ? 1 : 0);
+			wideOverflow = wideOverflow || (nodeM & lanes_where(n2 > kWideStackEntries)) != 0ull;
+			const uint32_t next = quad_or(nearest ? cref : 0u);
+			ref = atNode ? (hr == 0u ? kRefPop : next) : ref;
+			n = atNode ? (n2 > kWideStackEntries ? kWideStackEntries : n2) : n;
 		}
 		// ---- a leaf: four primitives per round, accepted in array order (bvh.h:129-140 / 229-238) ----
-		const bool atLeaf = gActive && ref_is_leaf(ref);
-		if (__ballot(atLeaf) != 0ull) {
+		// The accept rule of both kinds of ray is t > eps && dist - t > eps; the closest-hit rule's third term, t < dist, is
+		// implied (a rounded difference is positive only if the exact one is), and a lane past the leaf's end tested nothing
+		// (t = 0).  A closest-hit ray takes each accepted distance in turn; a shadow ray only notes that one was.
+		const lanemask leafM = act & lanes_at_leaf(ref);
+		if (leafM != 0ull) {
+			const bool atLeaf = lane_in(leafM);
 			const uint32_t off = ref & (kMaxPrimOffset - 1);
 			const uint32_t cnt = atLeaf ? ((ref >> 26) & 31u) + 1u : 0u;
-			bool found = false;
+			lanemask inM = 0ull;
 			for (uint32_t base = 0; __ballot(base < cnt) != 0ull; base += 4u) {
 				const uint32_t i = base + sub;
 				const bool mine = i < cnt;
 				const TriData td = triangle_gload(tris, mine ? off + i : 0u);
 				float tm = triangle_test_select(td, r);
 				tm = mine ? tm : 0.0f;
-				const float t0 = quad_bcast_f<0>(tm), t1 = quad_bcast_f<1>(tm), t2 = quad_bcast_f<2>(tm), t3 = quad_bcast_f<3>(tm);
-				const float tk[4] = { t0, t1, t2, t3 };
+				const float tk[4] = { quad_bcast_f<0>(tm), quad_bcast_f<1>(tm), quad_bcast_f<2>(tm), quad_bcast_f<3>(tm) };
+				uint32_t took = 4u; // the last candidate of this round a closest-hit ray took (4: none)
 #pragma unroll
 				for (uint32_t k = 0; k < 4u; ++k) {
 					const float t = tk[k];
-					const bool in = (base + k < cnt) && t > kEpsilon && ((dist - t) > kEpsilon);
-					found = found || (in && isShadow);                 // bvh.h:232-236
-					const bool closer = in && !isShadow && t < dist;    // bvh.h:133-137
-					prim = closer ? (int)(off + base + k) : prim;
-					hitTri = hitTri || closer;
-					dist = closer ? t : dist;
+					const lanemask in = lanes_where(t > kEpsilon) & lanes_where((dist - t) > kEpsilon); // bvh.h:134 / 232-236
+					const lanemask closer = in & ~shadowM;                                                  // bvh.h:135-137
+					inM |= in;
+					hitM |= closer;
+					dist = lane_in(closer) ? t : dist;
+					took = lane_in(closer) ? k : took;
 				}
+				prim = took != 4u ? (int)(off + base + took) : prim;
 			}
-			occluded = occluded || found;
-			ref = atLeaf ? (found ? kRefDone : kRefPop) : ref;
+			const lanemask foundM = inM & shadowM & leafM;
+			occM |= foundM;
+			ref = atLeaf ? (lane_in(foundM) ? kRefDone : kRefPop) : ref;
 		}
-		if (gActive && ref == kRefDone) {
-			if (sub == 0u) {
+		// ---- finished rays ----
+		const lanemask finM = act & lanes_where(ref == kRefDone);
+		if (finM != 0ull) {
+			if (lane_in(finM) && sub == 0u) {
 				if (isShadow) {
-					if (!occluded) { // kernel.cu:640-644
-						const float4 c = shadowColor[slot];
-						accumulate_pixel(blit, __float_as_int(shadowDyzCdIx[slot].w), mk3(c.x, c.y, c.z), 0);
+					if (!lane_in(occM)) { // kernel.cu:640-644
+						const v4f_t c = ((const TYR_GLOBAL v4f_t*)P.shadowPrev.color)[slot];
+						accumulate_pixel(P.blit, __float_as_int(((const TYR_GLOBAL v4f_t*)P.shadowPrev.dyz_cd_ix)[slot].w), mk3(c.x, c.y, c.z), 0);
 						visible += 1;
 					}
-				} else {
-					finish_extend_ray(workHit, slot, hitTri, dist, prim);
+				} else if (lane_in(hitM)) { // a triangle hit replaces the sphere answer of the pre-pass (kernel.cu:138-140)
+					((TYR_GLOBAL v2f_t*)P.work.hit)[slot] = v2f_t{ dist, __uint_as_float((uint32_t)prim) };
 				}
 			}
-			gActive = false;
+			act &= ~finM;
 		}
 	}
 	return visible | (wideOverflow ? 0x80000000u : 0u) | (kGuardPasses && passes > kMaxPasses ? 0x40000000u : 0u);
@@ -903,6 +924,7 @@ __global__ void __launch_bounds__(kTraceBlock, (kTraceBlock == kTraceBlockWide ?
 		}
 		allRegular = (__ballot(live && !regular) == 0ull);
 		const RayConst r = { mk3(rox, roy, roz), mk3(rdx, rdy, rdz), mk3(rix, riy, riz), rix < 0, riy < 0, riz < 0 }; // bvh.h:120-121
+		const uint32_t signBits = (r.nx ? 1u : 0u) | (r.ny ? 2u : 0u) | (r.nz ? 4u : 0u);
 		// ---- descent: one pop attempt + one quad test per lane per trip (the same for both kinds of ray) ----
 		for (;;) {
 			const uint32_t nTrav = __popcll(lanes_traversing(ref));
@@ -918,25 +940,23 @@ __global__ void __launch_bounds__(kTraceBlock, (kTraceBlock == kTraceBlockWide ?
 				tripsAfter += 1;
 			if (kAnatomy && !exhausted)
 				tripsFeed += 1;
-			if (ref == kRefPop) {
+			if (kLoopStats && ref == kRefPop) {
 				TYR_DBG(2)
-				uint32_t pr;
-				float pt;
-				if (st.pop(pr, pt)) {
-					if (pt < dist) // the pop-time half of Bbox.h:61 (always true for a shadow ray: its bound never shrinks)
-						ref = pr;
-				} else {
-					ref = kRefDone;
-				}
 			}
+			st.pop_select(ref == kRefPop, ref, dist); // (the entry-distance check is always true for a shadow ray: its bound never shrinks)
 			if ((int)ref >= 0) {
 				TYR_DBG(0)
 				if (kLoopStats)
 					steps += 1;
-				const QuadHits q = allRegular ? test_quad<true, true, true>(sc.quads, ref, r, dist, stagedNodes, nStaged) : test_quad<false, true, true>(sc.quads, ref, r, dist, stagedNodes, nStaged);
-				const lanemask any01 = q.hit[0] | q.hit[1], any012 = any01 | q.hit[2];
-				st.push3(q.hit[3] & any012, q.ref[3], q.t[3], q.hit[2] & any01, q.ref[2], q.t[2], q.hit[1] & q.hit[0], q.ref[1], q.t[1]);
-				ref = lane_in(q.hit[0]) ? q.ref[0] : lane_in(q.hit[1]) ? q.ref[1] : lane_in(q.hit[2]) ? q.ref[2] : lane_in(q.hit[3]) ? q.ref[3] : kRefPop;
+				// the four slots in node order, each with its rank in the reference's visit order (quad_ranks): the pushes go
+				// straight to their depths and the next node is the slot ranked first among the hits
+				const QuadHits q = allRegular ? test_quad<true, false, true>(sc.quads, ref, r, dist, stagedNodes, nStaged) : test_quad<false, false, true>(sc.quads, ref, r, dist, stagedNodes, nStaged);
+				uint32_t rank[4];
+				quad_ranks(ref, signBits, rank);
+				const uint32_t hr = (lane_in(q.hit[0]) ? 1u << rank[0] : 0u) | (lane_in(q.hit[1]) ? 1u << rank[1] : 0u) | (lane_in(q.hit[2]) ? 1u << rank[2] : 0u) | (lane_in(q.hit[3]) ? 1u << rank[3] : 0u);
+				const uint32_t first = (uint32_t)__ffs((int)hr) - 1u; // (~0 when nothing was hit: no slot's rank)
+				st.push_ranked(q.ref, q.t, q.hit, rank, hr, first);
+				ref = rank[0] == first ? q.ref[0] : rank[1] == first ? q.ref[1] : rank[2] == first ? q.ref[2] : rank[3] == first ? q.ref[3] : kRefPop;
 			}
 		}
 		// ---- leaves: bvh.h:129-140 (closest hit) / bvh.h:229-238 (any hit) ----
@@ -1057,11 +1077,10 @@ __global__ void __launch_bounds__(kTraceBlock, (kTraceBlock == kTraceBlockWide ?
 	flush_visible();
 	TYR_TRACE_VIEW(PE) // what the kernel's end reads (not held through the loop)
 	if (wide) {
-		WideState w;
-		w.rox = rox, w.roy = roy, w.roz = roz, w.rdx = rdx, w.rdy = rdy, w.rdz = rdz, w.rix = rix, w.riy = riy, w.riz = riz, w.dist = dist;
-		w.ref = ref, w.slot = slot, w.prim = prim, w.n = st.n;
-		w.flags = (regular ? 1u : 0u) | (hitTri ? 2u : 0u) | (isShadow ? 4u : 0u) | (occluded ? 8u : 0u) | (live ? 16u : 0u);
-		const uint32_t res = wide_drain<STACK_LDS>(PE.scene.quads, PE.scene.tris, PE.shadowPrev.color, PE.shadowPrev.dyz_cd_ix, PE.work.hit, PE.blit, smem_, w, passes TYR_WIDE_STEPS_ARG);
+		const uint32_t flags = (regular ? kWideRegular : 0u) | (hitTri ? kWideHitTri : 0u) | (isShadow ? kWideShadow : 0u) | (occluded ? kWideOccluded : 0u) | (live ? kWideLive : 0u);
+		// (the address of the argument segment itself, straight from the builtin: wide_drain reads it as constant memory, which a
+		// copy of the arguments in private memory is not)
+		const uint32_t res = wide_drain<STACK_LDS>((unsigned long long)__builtin_amdgcn_kernarg_segment_ptr(), (typename LdsStack<STACK_LDS, true>::lds_column_t)smem_, rox, roy, roz, rdx, rdy, rdz, rix, riy, riz, dist, ref, slot, prim, flags, st.n, passes TYR_WIDE_STEPS_ARG);
 		visible += res & 0x3fffffffu;
 		overflow = overflow || (res & 0x80000000u) != 0u;
 		if (res & 0x40000000u)
