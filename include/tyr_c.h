@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -578,6 +578,91 @@ typedef struct tyr_denoise_params {
 	uint32_t flags;
 } tyr_denoise_params;
 int tyr_denoise(tyr_ctx* ctx, const tyr_denoise_in* in, const tyr_denoise_params* params, void* device_rgba_out, void* stream);
+
+/* ---- Motion vectors: where each pixel's surface was in the previous frame (extension) -------------------------------------
+ * For local pixel p of the ctx's current camera and frame counter -- the rows and tickets of tyr_render_aov, sample 0 --
+ * the motion to the previous frame and the depth the previous frame's AOV pass would read there.  One binary32 operation per
+ * operation below, in the order written (dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; length(a) = sqrt(dot(a, a)), correctly
+ * rounded).
+ *   Inputs: prim, geom: full-frame DEVICE int32 arrays (y * width + x) as tyr_render_aov wrote them at this camera and
+ *   frame.  prev_camera: the previous frame's camera (host record).  prev_prims: NULL (the geometry did not move), or the
+ *   DEVICE address of the previous frame's 40-byte records in the uploaded build order with the uploaded count -- what a
+ *   caller held before its last tyr_scene_refit.
+ *   Hit point X: sample 0's camera ray (origin o, direction d: camera_seed / camera_focus / camera_lens of ticket p, as
+ *   tyr_render_aov makes it).  geom 1 with 0 <= prim < the uploaded count: Moller-Trumbore against triangle prim alone
+ *   (loader.h:21-46's operations) gives u, v, and X = (vert + u * e1) + v * e2 of the uploaded record; X' the same of the
+ *   prev_prims record, or X' = X without prev_prims.  geom 0 with 0 <= prim < 7: t = Sphere::intersect (kernel.cu:83-93) of
+ *   sphere prim, X = o + d * t, X' = X (spheres do not move).  Anything else, or a test that misses: no point.
+ *   Projection of a point Y through a camera (position O, direction F, R and U by the render's rule, kernel.cu:699-700, at the
+ *   ctx's width W and height H; F.F, R.R and U.U computed in float32 on the host): w = Y - O; f = dot(w, F);
+ *   a = (dot(w, R) * FF) / (f * RR); b = (dot(w, U) * FF) / (f * UU); xi = (a + 0.5) * W; yi = (0.5 - b) * H -- the inverse
+ *   of camera_focus' ndcX / ndcY through O (a pixel's jittered coordinates x - sx, y - sy).
+ *   Outputs, each optional (NULL: skipped; not both): motion (float32 x 2) = (xi' - xi, yi' - yi) with (xi, yi) of X through
+ *   the current camera and (xi', yi') of X' through prev_camera: the previous position of pixel (x, y) is (x, y) + motion.
+ *   prev_depth (float32) = length(X' - O_prev): the previous frame's AOV depth there for a lens radius of 0.  No point, f <= 0
+ *   for either camera, or a non-finite motion or prev_depth give motion (0, 0) and prev_depth VERY_FAR.  With prev_camera
+ *   equal to the current camera and prev_prims NULL or equal to the uploaded records, motion is exactly (0, 0) on every pixel.
+ *   Layout, sharding, ordering and state as tyr_render_aov's: a sharded ctx writes only its own rows; enqueued on `stream`
+ *   (NULL: the ctx's stream); no render state is touched; a later tyr_scene_refit waits for it (the caller keeps prev_prims
+ *   alive until the pass is done).
+ *   TYR_ERR_INVALID: in, out, prim, geom or prev_camera NULL, or both outputs NULL; TYR_ERR_NO_SCENE: nothing uploaded. */
+typedef struct tyr_motion_in {
+	const int32_t* prim;              /* width * height */
+	const int32_t* geom;              /* width * height */
+	const tyr_camera* prev_camera;    /* host */
+	const tyr_triangle* prev_prims;   /* device, the uploaded count, or NULL */
+} tyr_motion_in;
+typedef struct tyr_motion_out {
+	float* motion;      /* width * height x 2, or NULL */
+	float* prev_depth;  /* width * height, or NULL */
+} tyr_motion_out;
+int tyr_render_motion(tyr_ctx* ctx, const tyr_motion_in* in, const tyr_motion_out* out, void* stream);
+
+/* ---- Temporal reprojection: a running mean of frames over a reprojected history (extension) --------------------------------
+ * The first stage of SVGF (Schied et al. 2017): each valid pixel blends its current illumination into the ctx's history,
+ * sampled bilinearly where tyr_render_motion says the surface was.  Numeric contract as tyr_denoise's: one binary32 operation
+ * per operation below, in the order written, correctly rounded division.
+ *   Inputs: full-frame DEVICE arrays indexed y * width + x: accum float4 in the blit buffer's layout (NULL: the ctx's blit
+ *   buffer), albedo, normal (float32 x 3), depth from tyr_render_aov; motion (float32 x 2), prev_depth from tyr_render_motion.
+ *   Per pixel p = (x, y): A = accum.a; valid = A > 0 && depth < VERY_FAR; c = rgb / A; d_k = albedo_k > 0 ? albedo_k : 1;
+ *   u_k = c_k / d_k (tyr_denoise's preparation).  For a valid p with a history: qx = (float)x + motion.x, qy likewise; when
+ *   prev_depth_p < VERY_FAR and -1 < qx < width and -1 < qy < height: x0 = floor(qx), fx = qx - x0, gx = 1 - fx (y alike);
+ *   taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) in that order with weights gx*gy, fx*gy, gx*fy, fx*fy.  A tap
+ *   q is accepted when it is inside the frame, its history length len_q > 0, |hist_depth_q - prev_depth_p| <=
+ *   depth_tolerance * prev_depth_p and dot(hist_normal_q, normal_p) >= normal_cos.  Over the accepted taps in order, from
+ *   +0: S_k += w * hu_q_k, L += w * len_q, Wb += w.  When Wb > 0: h_k = S_k / Wb; n = min(L / Wb + 1, max_history);
+ *   v_k = h_k + (1 / n) * (u_k - h_k) when n > 1, v = u when n == 1.  Otherwise (no history, no accepted tap): n = 1, v = u.  Up to the cap this is the
+ *   exact running mean of the pixel's frames.
+ *   Outputs: device_rgba_out float4 per pixel: (v_k * d_k, 1) for a valid pixel, (c, 1) for a background pixel (A != 0, not
+ *   valid), (0, 0, 0, 0) where A == 0 -- a frame in the blit buffer's layout with one sample per pixel, tyr_denoise's
+ *   in.accum.  history_len_out (float32, may be NULL): n, 0 on pixels that are not valid.
+ *   History: the call stores (v, n) and (normal_p, depth_p) of every pixel as the next call's history (length 0 on pixels
+ *   that are not valid).  The first call on a ctx, and a call with TYR_TEMPORAL_RESET, has no history.
+ *   Parameters (NULL: the defaults): max_history 1..1024 (16), depth_tolerance > 0 and finite (0.05), normal_cos in [-1, 1]
+ *   (0.9); the defaults are discussed in DESIGN.md "Temporal reprojection".
+ *   Ordering and state: enqueued on `stream` (NULL: the ctx's stream); the call returns once it is.  It uses the ctx's device,
+ *   restores the caller's, needs no scene and touches no render state; the ctx's sharding plays no part (whole frames).  The
+ *   ctx owns the history (64 bytes per pixel: two ping-ponged copies of 32; allocated by the first call, freed by
+ *   tyr_destroy, not in tyr_scene_info's device_bytes); calls on one ctx are therefore ordered with each other whatever
+ *   their streams.
+ *   TYR_ERR_INVALID: in, a guide, motion, prev_depth or device_rgba_out is NULL; a parameter out of range; an unknown flag.
+ *   TYR_ERR_NO_BUFFER: accum is NULL and no blit buffer. */
+typedef struct tyr_temporal_in {
+	const float* accum;      /* width * height x 4, or NULL: the ctx's blit buffer */
+	const float* albedo;     /* width * height x 3 */
+	const float* normal;     /* width * height x 3 */
+	const float* depth;      /* width * height */
+	const float* motion;     /* width * height x 2 */
+	const float* prev_depth; /* width * height */
+} tyr_temporal_in;
+#define TYR_TEMPORAL_RESET 1u /* tyr_temporal_params.flags: discard the history before this frame */
+typedef struct tyr_temporal_params {
+	uint32_t max_history;
+	float depth_tolerance;
+	float normal_cos;
+	uint32_t flags;
+} tyr_temporal_params;
+int tyr_temporal(tyr_ctx* ctx, const tyr_temporal_in* in, const tyr_temporal_params* params, void* device_rgba_out, float* history_len_out, void* stream);
 
 #ifdef __cplusplus
 }

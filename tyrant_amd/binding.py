@@ -33,6 +33,9 @@ TYR_REFIT_DEVICE = 1
 TYR_DENOISE_RESOLVE = 1
 # tyr_denoise's defaults (host/denoise.cpp)
 DENOISE_PASSES, DENOISE_SIGMA_COLOR, DENOISE_SIGMA_DEPTH, DENOISE_NORMAL_POWER_LOG2 = 5, 32.0, 0.02, 7
+TYR_TEMPORAL_RESET = 1
+# tyr_temporal's defaults (host/temporal.cpp)
+TEMPORAL_MAX_HISTORY, TEMPORAL_DEPTH_TOLERANCE, TEMPORAL_NORMAL_COS = 16, 0.05, 0.9
 TYR_DIST_GATHER, TYR_DIST_REDUCE = 0, 1
 TYR_DIST_ID_BYTES = 128
 KERNEL_NAMES = ("primary", "extend", "shade", "connect", "resolve")
@@ -118,6 +121,26 @@ class DenoiseParams(C.Structure):
     _fields_ = [("passes", c_u32), ("sigma_color", C.c_float), ("sigma_depth", C.c_float), ("normal_power_log2", c_u32), ("flags", c_u32)]
 
 
+class MotionIn(C.Structure):
+    """tyr_motion_in: device ids from render_aov, the previous camera (host record), the previous triangle records (device, or NULL)"""
+
+    _fields_ = [("prim", P), ("geom", P), ("prev_camera", P), ("prev_prims", P)]
+
+
+class MotionOut(C.Structure):
+    _fields_ = [("motion", P), ("prev_depth", P)]
+
+
+class TemporalIn(C.Structure):
+    """tyr_temporal_in: device pointers of the frame (NULL: the ctx's blit buffer), its guides and its motion"""
+
+    _fields_ = [("accum", P), ("albedo", P), ("normal", P), ("depth", P), ("motion", P), ("prev_depth", P)]
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", c_u32), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float), ("flags", c_u32)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 5), ("launches", c_u64 * 5)]
 
@@ -193,6 +216,8 @@ SYMBOLS = {
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
     "tyr_denoise": (C.c_int, [P, P, P, P, P]),
+    "tyr_render_motion": (C.c_int, [P, P, P, P]),
+    "tyr_temporal": (C.c_int, [P, P, P, P, P, P]),
 }
 
 _libs: dict = {}
@@ -647,6 +672,74 @@ class Renderer:
         if stream is not None:
             out.record_stream(stream)  # written there: the allocator must not hand its memory out before that stream is done
         return out
+
+    def _frame_tensors(self, ins):
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        for what, (t, dtype, size) in ins.items():
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != size:
+                raise ValueError(f"{what}: a contiguous {dtype} tensor of {size} values on {dev}")
+        return dev
+
+    def render_motion(self, prim, geom, prev_camera, prev_prims=None, stream=None) -> dict:
+        """tyr_render_motion: per pixel the motion to the previous frame and the depth expected there, from render_aov's sample-0
+        ids (prim, geom: (H, W) int32 tensors on this ctx's device) at the current camera and frame.  prev_camera: the previous
+        frame's camera (fields as set_camera takes them).  prev_prims: None (the geometry did not move), or the records held
+        before the last refit in the uploaded order -- a contiguous tensor of 40-byte records on this device, or a TRIANGLE_DTYPE
+        numpy array (copied over on the current stream).  Returns a dict of torch tensors: "motion" (H, W, 2), "prev_depth"
+        (H, W).  Runs on `stream` (default: torch's current stream) and returns once it is enqueued.  A sharded ctx fills its own
+        rows; the others are zero."""
+        import torch
+
+        n = self.H * self.W
+        dev = self._frame_tensors({"prim": (prim, torch.int32, n), "geom": (geom, torch.int32, n)})
+        f3 = lambda x: (c_f * 3)(*[float(v) for v in x])  # noqa: E731
+        cam = CameraC(f3(prev_camera.position), f3(prev_camera.direction), f3(prev_camera.up), prev_camera.focalDistance, prev_camera.lensRadius)
+        pp = None
+        if prev_prims is not None:
+            if not isinstance(prev_prims, torch.Tensor):
+                a = np.ascontiguousarray(prev_prims, dtype=scenes.TRIANGLE_DTYPE)
+                prev_prims = torch.from_numpy(a.view(np.uint8).reshape(-1)).to(dev)
+            if prev_prims.device != dev or not prev_prims.is_contiguous() or prev_prims.numel() * prev_prims.element_size() % 40:
+                raise ValueError(f"prev_prims: a contiguous tensor of 40-byte records on {dev}")
+            pp = prev_prims.data_ptr()
+        res = {"motion": torch.zeros((self.H, self.W, 2), dtype=torch.float32, device=dev), "prev_depth": torch.zeros((self.H, self.W), dtype=torch.float32, device=dev)}
+        mi = MotionIn(prim.data_ptr(), geom.data_ptr(), C.cast(C.pointer(cam), P), pp)
+        mo = MotionOut(res["motion"].data_ptr(), res["prev_depth"].data_ptr())
+        self._on_stream(stream, lambda h: self.L.tyr_render_motion(self.h, C.byref(mi), C.byref(mo), h), True)
+        if stream is not None:
+            for t in res.values():
+                t.record_stream(stream)
+            if pp is not None:
+                prev_prims.record_stream(stream)
+        return res
+
+    def temporal(self, albedo, normal, depth, motion, prev_depth, accum=None, max_history=TEMPORAL_MAX_HISTORY, depth_tolerance=TEMPORAL_DEPTH_TOLERANCE,
+                 normal_cos=TEMPORAL_NORMAL_COS, reset=False, want_history_len=False, stream=None):
+        """tyr_temporal: blend this frame into the ctx's reprojected history.  albedo, normal (H, W, 3), depth (H, W) from
+        render_aov, motion (H, W, 2), prev_depth (H, W) from render_motion, accum (H, W, 4; None: this ctx's blit buffer):
+        contiguous float32 tensors on this ctx's device.  Returns the (H, W, 4) float32 frame in the blit buffer's layout with one
+        sample per pixel (denoise's accum), and with want_history_len=True also the (H, W) history lengths.  reset=True discards
+        the history first.  Runs on `stream` (default: torch's current stream) and returns without waiting for it."""
+        import torch
+
+        n = self.H * self.W
+        f = torch.float32
+        ins = {"albedo": (albedo, f, 3 * n), "normal": (normal, f, 3 * n), "depth": (depth, f, n), "motion": (motion, f, 2 * n), "prev_depth": (prev_depth, f, n)}
+        if accum is not None:
+            ins["accum"] = (accum, f, 4 * n)
+        dev = self._frame_tensors(ins)
+        out = torch.empty((self.H, self.W, 4), dtype=f, device=dev)
+        hl = torch.empty((self.H, self.W), dtype=f, device=dev) if want_history_len else None
+        tin = TemporalIn(None if accum is None else accum.data_ptr(), albedo.data_ptr(), normal.data_ptr(), depth.data_ptr(), motion.data_ptr(), prev_depth.data_ptr())
+        prm = TemporalParams(max_history, depth_tolerance, normal_cos, TYR_TEMPORAL_RESET if reset else 0)
+        self._on_stream(stream, lambda h: self.L.tyr_temporal(self.h, C.byref(tin), C.byref(prm), out.data_ptr(), None if hl is None else hl.data_ptr(), h), True)
+        if stream is not None:
+            out.record_stream(stream)
+            if hl is not None:
+                hl.record_stream(stream)
+        return (out, hl) if want_history_len else out
 
 
 def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: int = 0) -> np.ndarray:

@@ -146,6 +146,30 @@ __device__ __forceinline__ float triangle_test(const TriData& d, const RayConst&
 		return 0.0f;
 	return dot(e2, qvec) * invDet;
 }
+// triangle_test's sibling that also hands back the barycentrics u, v of a hit (untouched on a miss): the same operations in
+// the same order (hip/temporal.hip's motion kernel)
+__device__ __forceinline__ float triangle_test_uv(const TriData& d, const RayConst& r, float& uOut, float& vOut) {
+	const float4 a = d.a, b = d.b, c = d.c;
+	const f3 vert = mk3(a.x, a.y, a.z);
+	const f3 e1 = mk3(a.w, b.x, b.y);
+	const f3 e2 = mk3(b.z, b.w, c.x);
+	const f3 pvec = cross(r.d, e2);
+	const float det = dot(e1, pvec);
+	if (det < 0.0000001f)
+		return 0.0f;
+	const float invDet = 1 / det;
+	const f3 tvec = r.o - vert;
+	const float u = dot(tvec, pvec) * invDet;
+	if (u < 0 || u > 1)
+		return 0.0f;
+	const f3 qvec = cross(tvec, e1);
+	const float v = dot(r.d, qvec) * invDet;
+	if (v < 0 || u + v > 1)
+		return 0.0f;
+	uOut = u;
+	vOut = v;
+	return dot(e2, qvec) * invDet;
+}
 
 // The same test without a branch: every operation of loader.h:21-46 in its order, the three early-outs folded into one
 // select at the end (identical results: a lane that would have left early computes values nobody reads -- 1 / det may be

@@ -108,6 +108,14 @@ struct tyr_ctx {
 	float4* dDenoise = nullptr;
 	hipEvent_t denoiseDone = nullptr;
 
+	// tyr_temporal (host/temporal.cpp): two histories of width * height pixels, each a (u.xyz, length) plane then a (normal.xyz,
+	// depth) plane, allocated by the first call; history temporalCur is the last call's output (valid only when temporalHave),
+	// temporalDone the event behind that call
+	float4* dTemporal = nullptr;
+	hipEvent_t temporalDone = nullptr;
+	uint32_t temporalCur = 0;
+	bool temporalHave = false;
+
 	// TYR_FLAG_REFIT: what every scene upload keeps for tyr_scene_refit (host/refit.cpp)
 	tyr::RefitPlan refit{};
 

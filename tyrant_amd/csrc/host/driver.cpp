@@ -199,8 +199,10 @@ uint32_t planned_new(const tyr_ctx* c) {
 	return static_cast<uint32_t>(std::min(room, budget));
 }
 
-void camera_basis(const tyr_ctx* c, float right[3], float up[3]) {
-	const f3 dir = ld3(c->cam.direction), camUp = ld3(c->cam.up);
+void camera_basis(const tyr_ctx* c, float right[3], float up[3]) { camera_basis(c, c->cam, right, up); }
+
+void camera_basis(const tyr_ctx* c, const tyr_camera& cam, float right[3], float up[3]) {
+	const f3 dir = ld3(cam.direction), camUp = ld3(cam.up);
 	// kernel.cu:699-700
 	const f3 r = normalize(cross(dir, camUp)) * 1.5f * (static_cast<float>(c->cfg.width) / static_cast<float>(c->cfg.height));
 	const f3 u = normalize(cross(r, dir)) * 1.5f;
@@ -502,6 +504,7 @@ int tyr_destroy(tyr_ctx* c) {
 		(void)hipStreamSynchronize(c->stream);
 	query_free(c);
 	denoise_free(c);
+	temporal_free(c);
 	free_rayq(c->q[0]);
 	free_rayq(c->q[1]);
 	for (auto& sq : c->shadow) {

@@ -81,9 +81,13 @@ int query_wait(tyr_ctx* c);
 int query_ticket(tyr_ctx* c, void* stream, hipStream_t& s, tyr_ctx::QueryStream*& qs, uint32_t*& ticket);
 // host/driver.cpp: the camera basis of the staged prologue (kernel.cu:699-700) for the ctx's current camera
 void camera_basis(const tyr_ctx* c, float right[3], float up[3]);
+// ... and for any camera at the ctx's width and height (tyr_render_motion's previous camera)
+void camera_basis(const tyr_ctx* c, const tyr_camera& cam, float right[3], float up[3]);
 void query_free(tyr_ctx* c);
 // host/denoise.cpp: wait for the last tyr_denoise call; free its scratch and event (tyr_destroy)
 void denoise_free(tyr_ctx* c);
+// host/temporal.cpp: wait for the last tyr_temporal call; free its history and event (tyr_destroy)
+void temporal_free(tyr_ctx* c);
 // AoS import / export (host/staged_api.cpp): physical slots that hold a record, per segment counter array `seg` (device pointer)
 int valid_slots(const uint32_t* dSeg, std::vector<uint32_t>& slots, uint32_t* total = nullptr);
 void dense_counts(uint32_t n, uint32_t* cnt /* [kSegs * kSegStride] */);
