@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -663,6 +663,70 @@ typedef struct tyr_temporal_params {
 	uint32_t flags;
 } tyr_temporal_params;
 int tyr_temporal(tyr_ctx* ctx, const tyr_temporal_in* in, const tyr_temporal_params* params, void* device_rgba_out, float* history_len_out, void* stream);
+
+/* ---- SVGF: variance-guided spatiotemporal filtering (extension) -----------------------------------------------------------
+ * Spatiotemporal variance-guided filtering (Schied et al. 2017): tyr_temporal's reprojected running mean, extended to the
+ * luminance moments, feeds a per-pixel variance that scales the luminance term of an a-trous filter; the filter's first pass is
+ * the next frame's colour history.  Numeric contract as tyr_denoise's: one binary32 operation per operation below, in the
+ * order written, correctly rounded division, no transcendental function outside TYR_SVGF_RESOLVE.  max(0, t) is t when t > 0,
+ * else +0.
+ *   Inputs: those of tyr_temporal (accum NULL: the ctx's blit buffer).
+ *   Preparation, per pixel p = (x, y): A, valid, c, d and u as tyr_temporal's; l = (0.2126*u.x + 0.7152*u.y) + 0.0722*u.z.
+ *   Temporal stage, valid p: tyr_temporal's taps, acceptance tests and weights against this call's own history; over the
+ *   accepted taps in order, from +0: S_k += w * hu_q_k, L += w * len_q, M1 += w * m1_q, M2 += w * m2_q, Wb += w.  When Wb > 0:
+ *   h_k = S_k / Wb, h1 = M1 / Wb, h2 = M2 / Wb; n = min(L / Wb + 1, max_history); when n > 1, with k = 1 / n:
+ *   v_k = h_k + k * (u_k - h_k), m1 = h1 + k * (l - h1), m2 = h2 + k * (l*l - h2).  Otherwise (no history, no accepted tap,
+ *   or n == 1): n = 1, v = u, m1 = l, m2 = l*l.
+ *   Variance, valid p: n >= 4: var = max(0, m2 - m1*m1).  n < 4: taps dy = -3..3 (outer), dx = -3..3 (inner) at q = (x + dx,
+ *   y + dy), skipping q outside the frame or not valid; the centre's weight is 1, any other tap's w = g / (1 + xz) with g and
+ *   xz tyr_denoise's normal and depth terms of (p, q); from +0: S1 += w * m1_q, S2 += w * m2_q, Ws += w; M1 = S1 / Ws,
+ *   M2 = S2 / Ws; var = max(0, M2 - M1*M1) * (4 / n).  variance_out (float32, may be NULL): var, 0 on pixels that are not
+ *   valid.
+ *   Pass j = 0 .. passes - 1, step s = 2^j, for each valid centre p, on (u, var) = (v, var) before pass 0 and the previous
+ *   pass's result after it (normals, depths and validity never change).  Prefilter: taps dy = -1..1 (outer), dx = -1..1
+ *   (inner) at step 1, skipping q outside the frame or not valid; k = G[dx+1] * G[dy+1], G = {1/4, 1/2, 1/4}; from +0:
+ *   gs += k * var_q, gw += k; gv = gs / gw; kl = 1 / (sl2 * gv + 1e-10) with sl2 = sigma_luminance * sigma_luminance (float32
+ *   on the host); lp = the luminance of u_p (the formula of l).  Then tyr_denoise's 25 taps, order, skipping rules, h, g, r, xz
+ *   and kz, with dl = (luminance of u_q) - lp; den = (1 + (dl*dl) * kl) * (1 + xz); w = (h*g) / den; from +0: S_k += w * u_q_k,
+ *   V += (w*w) * var_q, Wsum += w.  The result is u' = S / Wsum, var' = V / (Wsum * Wsum) when Wsum > 0, else (u_p, var_p).
+ *   Output: device_rgba_out float4 per pixel: (out_k = v_k * d_k, 1) with v the last pass's u' for a valid pixel, (c, 1) for a
+ *   background pixel (A != 0, not valid), (0, 0, 0, 0) where A == 0.  With TYR_SVGF_RESOLVE every pixel with A != 0 gets
+ *   tyr_resolve's tone map of that frame instead.
+ *   History: the call stores, for every pixel, (u'_0, n) with u'_0 pass 0's result, (normal_p, depth_p) and (m1, m2) -- the
+ *   moments unfiltered -- as the next call's history (length 0 on pixels that are not valid).  The first call on a ctx, and a
+ *   call with TYR_SVGF_RESET, has no history.  The history is the call's own: it neither reads nor writes tyr_temporal's
+ *   history or tyr_denoise's scratch.
+ *   Parameters (NULL: the defaults): max_history 1..1024 (8), depth_tolerance > 0 and finite (0.05), normal_cos in [-1, 1]
+ *   (0.9), passes 1..8 (3), sigma_luminance (2) and sigma_depth (0.02) positive and finite with sl2 and 1 / (sigma_depth *
+ *   sigma_depth) finite and positive, normal_power_log2 0..10 (7); the defaults are discussed in DESIGN.md "SVGF".
+ *   Ordering and state: enqueued on `stream` (NULL: the ctx's stream); the call returns once it is.  It uses the ctx's device,
+ *   restores the caller's, needs no scene and touches no render state; the ctx's sharding plays no part (whole frames).  The
+ *   ctx owns the history (80 bytes per pixel: two ping-ponged copies of 40) and the passes' scratch (32 bytes per pixel), both
+ *   allocated by the first call, freed by tyr_destroy, not in tyr_scene_info's device_bytes; calls on one ctx are therefore
+ *   ordered with each other whatever their streams.
+ *   TYR_ERR_INVALID: in, a guide, motion, prev_depth or device_rgba_out is NULL; a parameter out of range; an unknown flag.
+ *   TYR_ERR_NO_BUFFER: accum is NULL and no blit buffer. */
+typedef struct tyr_svgf_in {
+	const float* accum;      /* width * height x 4, or NULL: the ctx's blit buffer */
+	const float* albedo;     /* width * height x 3 */
+	const float* normal;     /* width * height x 3 */
+	const float* depth;      /* width * height */
+	const float* motion;     /* width * height x 2 */
+	const float* prev_depth; /* width * height */
+} tyr_svgf_in;
+#define TYR_SVGF_RESET 1u   /* tyr_svgf_params.flags: discard the SVGF history before this frame */
+#define TYR_SVGF_RESOLVE 2u /* tyr_svgf_params.flags: tone-map the output as tyr_resolve does */
+typedef struct tyr_svgf_params {
+	uint32_t max_history;
+	float depth_tolerance;
+	float normal_cos;
+	uint32_t passes;
+	float sigma_luminance;
+	float sigma_depth;
+	uint32_t normal_power_log2;
+	uint32_t flags;
+} tyr_svgf_params;
+int tyr_svgf(tyr_ctx* ctx, const tyr_svgf_in* in, const tyr_svgf_params* params, void* device_rgba_out, float* variance_out, void* stream);
 
 #ifdef __cplusplus
 }

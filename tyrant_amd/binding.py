@@ -36,6 +36,10 @@ DENOISE_PASSES, DENOISE_SIGMA_COLOR, DENOISE_SIGMA_DEPTH, DENOISE_NORMAL_POWER_L
 TYR_TEMPORAL_RESET = 1
 # tyr_temporal's defaults (host/temporal.cpp)
 TEMPORAL_MAX_HISTORY, TEMPORAL_DEPTH_TOLERANCE, TEMPORAL_NORMAL_COS = 16, 0.05, 0.9
+TYR_SVGF_RESET, TYR_SVGF_RESOLVE = 1, 2
+# tyr_svgf's defaults (host/svgf.cpp)
+SVGF_MAX_HISTORY, SVGF_DEPTH_TOLERANCE, SVGF_NORMAL_COS = 8, 0.05, 0.9
+SVGF_PASSES, SVGF_SIGMA_LUMINANCE, SVGF_SIGMA_DEPTH, SVGF_NORMAL_POWER_LOG2 = 3, 2.0, 0.02, 7
 TYR_DIST_GATHER, TYR_DIST_REDUCE = 0, 1
 TYR_DIST_ID_BYTES = 128
 KERNEL_NAMES = ("primary", "extend", "shade", "connect", "resolve")
@@ -141,6 +145,17 @@ class TemporalParams(C.Structure):
     _fields_ = [("max_history", c_u32), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float), ("flags", c_u32)]
 
 
+class SvgfIn(C.Structure):
+    """tyr_svgf_in: the inputs of tyr_temporal_in"""
+
+    _fields_ = [("accum", P), ("albedo", P), ("normal", P), ("depth", P), ("motion", P), ("prev_depth", P)]
+
+
+class SvgfParams(C.Structure):
+    _fields_ = [("max_history", c_u32), ("depth_tolerance", C.c_float), ("normal_cos", C.c_float), ("passes", c_u32), ("sigma_luminance", C.c_float),
+                ("sigma_depth", C.c_float), ("normal_power_log2", c_u32), ("flags", c_u32)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 5), ("launches", c_u64 * 5)]
 
@@ -218,6 +233,7 @@ SYMBOLS = {
     "tyr_denoise": (C.c_int, [P, P, P, P, P]),
     "tyr_render_motion": (C.c_int, [P, P, P, P]),
     "tyr_temporal": (C.c_int, [P, P, P, P, P, P]),
+    "tyr_svgf": (C.c_int, [P, P, P, P, P, P]),
 }
 
 _libs: dict = {}
@@ -740,6 +756,35 @@ class Renderer:
             if hl is not None:
                 hl.record_stream(stream)
         return (out, hl) if want_history_len else out
+
+    def svgf(self, albedo, normal, depth, motion, prev_depth, accum=None, max_history=SVGF_MAX_HISTORY, depth_tolerance=SVGF_DEPTH_TOLERANCE,
+             normal_cos=SVGF_NORMAL_COS, passes=SVGF_PASSES, sigma_luminance=SVGF_SIGMA_LUMINANCE, sigma_depth=SVGF_SIGMA_DEPTH,
+             normal_power_log2=SVGF_NORMAL_POWER_LOG2, reset=False, resolve=False, want_variance=False, stream=None):
+        """tyr_svgf: variance-guided spatiotemporal filtering of this frame against the ctx's own SVGF history.  The inputs are
+        temporal's: albedo, normal (H, W, 3), depth (H, W) from render_aov, motion (H, W, 2), prev_depth (H, W) from
+        render_motion, accum (H, W, 4; None: this ctx's blit buffer), contiguous float32 tensors on this ctx's device.  Returns
+        the (H, W, 4) float32 filtered frame in the blit buffer's layout with one sample per pixel (with resolve=True tone-mapped
+        as resolve_into writes it), and with want_variance=True also the (H, W) variance estimate.  reset=True discards the
+        history first.  Runs on `stream` (default: torch's current stream) and returns without waiting for it."""
+        import torch
+
+        n = self.H * self.W
+        f = torch.float32
+        ins = {"albedo": (albedo, f, 3 * n), "normal": (normal, f, 3 * n), "depth": (depth, f, n), "motion": (motion, f, 2 * n), "prev_depth": (prev_depth, f, n)}
+        if accum is not None:
+            ins["accum"] = (accum, f, 4 * n)
+        dev = self._frame_tensors(ins)
+        out = torch.empty((self.H, self.W, 4), dtype=f, device=dev)
+        var = torch.empty((self.H, self.W), dtype=f, device=dev) if want_variance else None
+        sin = SvgfIn(None if accum is None else accum.data_ptr(), albedo.data_ptr(), normal.data_ptr(), depth.data_ptr(), motion.data_ptr(), prev_depth.data_ptr())
+        flags = (TYR_SVGF_RESET if reset else 0) | (TYR_SVGF_RESOLVE if resolve else 0)
+        prm = SvgfParams(max_history, depth_tolerance, normal_cos, passes, sigma_luminance, sigma_depth, normal_power_log2, flags)
+        self._on_stream(stream, lambda h: self.L.tyr_svgf(self.h, C.byref(sin), C.byref(prm), out.data_ptr(), None if var is None else var.data_ptr(), h), True)
+        if stream is not None:
+            out.record_stream(stream)
+            if var is not None:
+                var.record_stream(stream)
+        return (out, var) if want_variance else out
 
 
 def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: int = 0) -> np.ndarray:

@@ -116,6 +116,17 @@ struct tyr_ctx {
 	uint32_t temporalCur = 0;
 	bool temporalHave = false;
 
+	// tyr_svgf (host/svgf.cpp): two histories of width * height pixels, each a (u.xyz, length) plane then a (normal.xyz, depth)
+	// plane (dSvgfHist), and a (m1, m2) plane (dSvgfMom); history svgfCur is the last call's output (valid only when
+	// svgfHave).  dSvgfIllum: the a-trous passes' two (u.xyz, variance) buffers.  All allocated by the first call; svgfDone is
+	// the event behind the last call
+	float4* dSvgfHist = nullptr;
+	float2* dSvgfMom = nullptr;
+	float4* dSvgfIllum = nullptr;
+	hipEvent_t svgfDone = nullptr;
+	uint32_t svgfCur = 0;
+	bool svgfHave = false;
+
 	// TYR_FLAG_REFIT: what every scene upload keeps for tyr_scene_refit (host/refit.cpp)
 	tyr::RefitPlan refit{};
 

@@ -505,6 +505,7 @@ int tyr_destroy(tyr_ctx* c) {
 	query_free(c);
 	denoise_free(c);
 	temporal_free(c);
+	svgf_free(c);
 	free_rayq(c->q[0]);
 	free_rayq(c->q[1]);
 	for (auto& sq : c->shadow) {

@@ -88,6 +88,8 @@ void query_free(tyr_ctx* c);
 void denoise_free(tyr_ctx* c);
 // host/temporal.cpp: wait for the last tyr_temporal call; free its history and event (tyr_destroy)
 void temporal_free(tyr_ctx* c);
+// host/svgf.cpp: wait for the last tyr_svgf call; free its history, scratch and event (tyr_destroy)
+void svgf_free(tyr_ctx* c);
 // AoS import / export (host/staged_api.cpp): physical slots that hold a record, per segment counter array `seg` (device pointer)
 int valid_slots(const uint32_t* dSeg, std::vector<uint32_t>& slots, uint32_t* total = nullptr);
 void dense_counts(uint32_t n, uint32_t* cnt /* [kSegs * kSegStride] */);
