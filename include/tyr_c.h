@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -191,7 +191,7 @@ typedef struct tyr_counters {
 	uint32_t shadow_ray_cnt;  /* kernel.cu:224 */
 	uint32_t n_live;          /* rays in the work queue after top-up (== queue_size in the reference) */
 	uint32_t frame;           /* kernel.cu:667 */
-	uint32_t device_error;    /* non-zero: TYR_ERR_DEVICE detail bits: 1 traversal stack overflow, 4 (builds with -DTYR_GUARD_PASSES only) a traversal wave gave up after 2^24 passes without finishing, 8 a queue segment ran out of room (the records beyond it were dropped; the segments are sized so that no set of rays can do it -- a check, not an expected outcome) */
+	uint32_t device_error;    /* non-zero: TYR_ERR_DEVICE detail bits: 1 traversal stack overflow, 4 (builds with -DTYR_GUARD_PASSES only) a traversal wave gave up after 2^24 passes without finishing, 8 a queue segment ran out of room (the records beyond it were dropped; the segments are sized so that no set of rays can do it -- a check, not an expected outcome), 16 a mapped camera ray's ticket fell outside the sample map's list (budget above T; unreachable through this ABI -- a check) */
 	uint64_t budget_remaining;
 	uint64_t total_extend_rays; /* sum of n_live over iterations */
 	uint64_t total_shadow_rays; /* sum of shadow_ray_cnt over iterations */
@@ -727,6 +727,60 @@ typedef struct tyr_svgf_params {
 	uint32_t flags;
 } tyr_svgf_params;
 int tyr_svgf(tyr_ctx* ctx, const tyr_svgf_in* in, const tyr_svgf_params* params, void* device_rgba_out, float* variance_out, void* stream);
+
+/* ---- Adaptive sampling (extension; INTEGRATION.md 4h, DESIGN.md "Adaptive sampling") ------------------
+ * A render normally gives every pixel the same spp.  A SAMPLE MAP gives pixel p exactly c[p] camera rays instead: uint32
+ * counts (width * height, indexed y * width + x like the blit buffer; a sharded ctx reads only its own rows, y = yl * nranks +
+ * rank).  Everything downstream divides by the count channel, so it needs no change.
+ *   Tickets.  Every camera ray of a render is a ticket.  The map defines a SAMPLE-MAJOR ticket list L over the ctx's local
+ *   pixels: pass s = 0, 1, 2, ... lists, in increasing order, the local pixels p with c[p] > s; L is the passes end to end,
+ *   T = sum of c[p] tickets.  In MAPPED MODE the new camera ray at launch index i of a launch that starts with budget_remaining
+ *   = b has ticket t = T - b + i and goes through local pixel L[t].  Nothing else changes: its seed (camera_seed(frame, i),
+ *   kernel.cu:258's launch index), the jitter and the lens, its virtual slot, retire-sky, the queue classes and segments,
+ *   set_wavefront_globals (start_position still advances by the rays made, mod P; mapped mode does not read it), frame++,
+ *   shade, connect and the accumulation.  Hence: a uniform map c = k with start_position == 0 renders exactly tyr_render(k)
+ *   (queues, counters, count channel: L[t] = t mod P); a render cut short by max_iterations has given every pixel its first
+ *   sample before any pixel gets a second; and with min(c) >= 1, queue_size >= P and an empty queue, tickets 0 .. P - 1 are
+ *   pixels 0 .. P - 1 at launch indices 0 .. P - 1 -- the rays tyr_render_aov and tyr_render_motion regenerate.  A render that
+ *   runs to completion adds exactly c[p] to every pixel's count channel.
+ *   Mode.  Mapped mode lasts until tyr_set_budget or tyr_render set a budget of their own, or another map replaces it.  While
+ *   it lasts every path that makes camera rays takes its pixels from L: tyr_launch_kernels, tyr_stage_primary,
+ *   tyr_render_adaptive, the TYR_FLAG_DEBUG_BVH picture.
+ *
+ * tyr_set_sample_map: build the ticket list of a device map and enter mapped mode with budget_remaining = T.
+ *   The map is read after all work queued on `stream` (NULL: the ctx's stream), as tyr_scene_refit's device path reads its
+ *   arrays.  The list lives in a buffer the ctx owns (4 bytes per ticket, grown as needed, freed by tyr_destroy); the call
+ *   returns once T is known on the host and the list is built -- the caller may free the map then.  total_out (optional): T.
+ *   T == 0 is allowed (nothing to render).  TYR_ERR_INVALID: ctx or map NULL, a count above 65535, or T >= 2^32;
+ *   TYR_ERR_OOM: the list could not be allocated.  After either the ctx is unchanged: budget, mode and counters. */
+int tyr_set_sample_map(tyr_ctx* ctx, const uint32_t* spp_map, void* stream, uint64_t* total_out);
+/* tyr_render_adaptive: tyr_set_sample_map, then tyr_render's loop on that budget (no budget reset), with tyr_render's
+ *   max_iterations / iterations_out rules.  An all-zero map behaves like tyr_render(ctx, 0, ...).  Errors: those of
+ *   tyr_set_sample_map, then TYR_ERR_NO_SCENE as tyr_render returns it, then the render's own. */
+int tyr_render_adaptive(tyr_ctx* ctx, const uint32_t* spp_map, void* stream, uint32_t max_iterations, uint32_t* iterations_out);
+
+/* tyr_allocate_samples: turn a per-pixel error estimate (width * height floats, the blit buffer's indexing) into a sample map
+ * with an exact total, by an order-independent rule over the local pixels p in increasing order:
+ *   1. v_p = error[p] if it is finite and > 0, else 0;  2. m = max v_p;
+ *   3. m > 0: s = 1048576.0f / m (one binary32 division), q_p = min((uint32)floorf(v_p * s), 1048576) -- where s overflows to
+ *      +inf (m below ~3.1e-33), q_p = 1048576 for v_p > 0 and 0 for v_p == 0; m == 0: every q_p = 1;
+ *   4. Q_p = the inclusive prefix sums of q in exact 64-bit integers, Q = Q_{P-1};
+ *   5. E = total - min_spp * P when that is positive, else 0;
+ *   6. extra_p = floor(E * Q_p / Q) - floor(E * Q_{p-1} / Q) in exact (128-bit) integers, Q_{-1} = 0;
+ *   7. c_p = min(min_spp + extra_p, max_spp).
+ *   The extras add up to exactly E: unless a pixel reaches max_spp the map spends exactly max(total, min_spp * P) samples.
+ *   total_out (optional): sum of c_p; when it is given the call waits for `stream`, otherwise it returns once the work is queued.
+ *   Enqueued on `stream` (NULL: the ctx's), needs no scene, writes only the ctx's rows of spp_map_out.  Its scratch (8 bytes
+ *   per pixel and a few words) belongs to the ctx -- allocated by the first call, freed by tyr_destroy -- so calls on one ctx are
+ *   ordered with each other whatever their streams.  TYR_ERR_INVALID: ctx, error, params or spp_map_out NULL, min_spp >
+ *   max_spp, max_spp outside 1 .. 65535, total >= 2^32.
+ *   Typical errors: the per-pixel distance between the means of two independent half renders of a still camera (proportional
+ *   to the per-pixel standard deviation: the allocation that minimises the expected MSE), or tyr_svgf's variance_out. */
+typedef struct tyr_allocate_params {
+	uint64_t total;
+	uint32_t min_spp, max_spp;
+} tyr_allocate_params;
+int tyr_allocate_samples(tyr_ctx* ctx, const float* error, const tyr_allocate_params* params, uint32_t* spp_map_out, uint64_t* total_out, void* stream);
 
 #ifdef __cplusplus
 }

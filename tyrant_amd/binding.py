@@ -40,6 +40,9 @@ TYR_SVGF_RESET, TYR_SVGF_RESOLVE = 1, 2
 # tyr_svgf's defaults (host/svgf.cpp)
 SVGF_MAX_HISTORY, SVGF_DEPTH_TOLERANCE, SVGF_NORMAL_COS = 8, 0.05, 0.9
 SVGF_PASSES, SVGF_SIGMA_LUMINANCE, SVGF_SIGMA_DEPTH, SVGF_NORMAL_POWER_LOG2 = 3, 2.0, 0.02, 7
+# Renderer.allocate_samples' defaults (DESIGN.md "Adaptive sampling", profiles/adaptive_bench_c3.json): every pixel keeps one
+# sample (the AOV / motion rays stay sample 0), and no pixel takes more than this many
+ADAPTIVE_MIN_SPP, ADAPTIVE_MAX_SPP = 1, 256
 TYR_DIST_GATHER, TYR_DIST_REDUCE = 0, 1
 TYR_DIST_ID_BYTES = 128
 KERNEL_NAMES = ("primary", "extend", "shade", "connect", "resolve")
@@ -156,6 +159,10 @@ class SvgfParams(C.Structure):
                 ("sigma_depth", C.c_float), ("normal_power_log2", c_u32), ("flags", c_u32)]
 
 
+class AllocateParams(C.Structure):
+    _fields_ = [("total", c_u64), ("min_spp", c_u32), ("max_spp", c_u32)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 5), ("launches", c_u64 * 5)]
 
@@ -234,6 +241,9 @@ SYMBOLS = {
     "tyr_render_motion": (C.c_int, [P, P, P, P]),
     "tyr_temporal": (C.c_int, [P, P, P, P, P, P]),
     "tyr_svgf": (C.c_int, [P, P, P, P, P, P]),
+    "tyr_set_sample_map": (C.c_int, [P, P, P, C.POINTER(c_u64)]),
+    "tyr_render_adaptive": (C.c_int, [P, P, P, c_u32, C.POINTER(c_u32)]),
+    "tyr_allocate_samples": (C.c_int, [P, P, P, P, C.POINTER(c_u64), P]),
 }
 
 _libs: dict = {}
@@ -542,7 +552,7 @@ class Renderer:
         t = take(tmax, "tmax", (n,)) if tmax is not None else None
         return dev, n, o, d, t, staged
 
-    def _on_stream(self, stream, launch, staged):
+    def _on_stream(self, stream, launch, staged, what="tyr_query"):
         """launch(handle) on `stream` (default: torch's current stream).  The default stream has no handle of its own (0 means
         the ctx's stream to the library): the work then goes to a side stream ordered after it and before what follows on it."""
         import torch
@@ -552,12 +562,12 @@ class Renderer:
         if staged and s != cur:
             s.wait_stream(cur)  # the copies of numpy inputs were made on the current stream
         if s.cuda_stream != 0:
-            _check(launch(s.cuda_stream), "tyr_query")
+            _check(launch(s.cuda_stream), what)
             return
         if self._side is None:
             self._side = torch.cuda.Stream(self.device)
         self._side.wait_stream(s)
-        _check(launch(self._side.cuda_stream), "tyr_query")
+        _check(launch(self._side.cuda_stream), what)
         s.wait_stream(self._side)
 
     def refit(self, prims, bboxes=None, stream=None, want_nodes=False):
@@ -785,6 +795,53 @@ class Renderer:
             if var is not None:
                 var.record_stream(stream)
         return (out, var) if want_variance else out
+
+    # ---- adaptive sampling (include/tyr_c.h "Adaptive sampling") ----
+
+    def _frame_map(self, a, dtype, what):
+        """a (H, W) map as a contiguous tensor of `dtype` on this ctx's device: torch tensors of that dtype are taken as they are,
+        numpy arrays are copied over on the current stream"""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        if not isinstance(a, torch.Tensor):
+            a = torch.from_numpy(np.ascontiguousarray(np.asarray(a).astype(np.int32 if dtype == torch.int32 else np.float32, copy=False))).to(dev)
+        if a.dtype != dtype or a.device != dev or not a.is_contiguous() or a.numel() != self.H * self.W:
+            raise ValueError(f"{what}: a contiguous ({self.H}, {self.W}) {dtype} tensor on {dev}")
+        return a
+
+    def set_sample_map(self, spp_map, stream=None) -> int:
+        """tyr_set_sample_map: build the ticket list of an (H, W) int32 sample map (torch tensor on this ctx's device, or numpy)
+        and enter mapped mode (budget = the map's sum T over this ctx's rows).  The map is read after the work on `stream`
+        (default: torch's current stream).  Returns T."""
+        import torch
+
+        m = self._frame_map(spp_map, torch.int32, "spp_map")
+        total = c_u64(0)
+        self._on_stream(stream, lambda h: self.L.tyr_set_sample_map(self.h, m.data_ptr(), h, C.byref(total)), True, "tyr_set_sample_map")
+        return total.value
+
+    def render_adaptive(self, spp_map, max_iterations=0xFFFFFFFF, stream=None) -> int:
+        """tyr_render_adaptive: set_sample_map(spp_map), then render's loop on that budget.  Returns the iterations."""
+        import torch
+
+        m = self._frame_map(spp_map, torch.int32, "spp_map")
+        it = c_u32(0)
+        self._on_stream(stream, lambda h: self.L.tyr_render_adaptive(self.h, m.data_ptr(), h, max_iterations, C.byref(it)), True, "tyr_render_adaptive")
+        return it.value
+
+    def allocate_samples(self, error, total, min_spp=ADAPTIVE_MIN_SPP, max_spp=ADAPTIVE_MAX_SPP, stream=None):
+        """tyr_allocate_samples: an (H, W) float32 error estimate (torch tensor on this ctx's device, or numpy) -> (sample map, its
+        sum): an (H, W) int32 tensor (a sharded ctx writes its own rows; the others are 0) and the sum over this ctx's rows.
+        The map spends exactly max(total, min_spp * P) samples unless some pixel reaches max_spp."""
+        import torch
+
+        e = self._frame_map(error, torch.float32, "error")
+        out = torch.zeros((self.H, self.W), dtype=torch.int32, device=e.device)
+        got = c_u64(0)
+        prm = AllocateParams(int(total), int(min_spp), int(max_spp))
+        self._on_stream(stream, lambda h: self.L.tyr_allocate_samples(self.h, e.data_ptr(), C.byref(prm), out.data_ptr(), C.byref(got), h), True, "tyr_allocate_samples")
+        return out, got.value
 
 
 def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: int = 0) -> np.ndarray:

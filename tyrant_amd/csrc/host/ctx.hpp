@@ -127,6 +127,18 @@ struct tyr_ctx {
 	uint32_t svgfCur = 0;
 	bool svgfHave = false;
 
+	// tyr_set_sample_map / tyr_allocate_samples (host/adaptive.cpp): the sample map's ticket list (4 bytes per ticket, grown as needed),
+	// its length T and whether the camera rays take their pixels from it (mapped mode: until tyr_set_budget / tyr_render set a
+	// budget of their own); the list build's scratch -- the map at the local pixels, the summary + histogram the host reads back,
+	// the compaction's block counts -- and the allocator's (two 64-bit scans and three words), with the event behind its last call
+	uint32_t* dTickets = nullptr;
+	uint64_t ticketCap = 0;
+	uint32_t ticketTotal = 0;
+	bool mapped = false;
+	uint32_t* dMapScratch = nullptr;
+	unsigned long long* dAllocScratch = nullptr;
+	hipEvent_t allocDone = nullptr;
+
 	// TYR_FLAG_REFIT: what every scene upload keeps for tyr_scene_refit (host/refit.cpp)
 	tyr::RefitPlan refit{};
 

@@ -19,6 +19,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "../hip/adaptive.hpp"
 #include "driver_internal.hpp"
 
 using namespace tyr;
@@ -248,7 +249,10 @@ int stage_begin(tyr_ctx* c) {
 void enqueue_primary(tyr_ctx* c, const FrameParams& P, uint32_t nNew) {
 	{
 		KernelTimer t(c, TYR_K_PRIMARY);
-		launch_primary(P, nNew, c->stream);
+		if (c->mapped) // tyr_set_sample_map: the pixels come from the map's ticket list
+			launch_primary_mapped(P, MappedPrimary{ c->dTickets, c->ticketTotal }, nNew, c->stream);
+		else
+			launch_primary(P, nNew, c->stream);
 	}
 }
 // nSurvivors: how many of the nLive rays were in the queue before this iteration's primary rays (they still need their
@@ -506,6 +510,7 @@ int tyr_destroy(tyr_ctx* c) {
 	denoise_free(c);
 	temporal_free(c);
 	svgf_free(c);
+	adaptive_free(c);
 	free_rayq(c->q[0]);
 	free_rayq(c->q[1]);
 	for (auto& sq : c->shadow) {
@@ -899,6 +904,7 @@ int tyr_set_budget(tyr_ctx* c, uint64_t primary_rays) {
 	if ((rc = sync_counters(c)))
 		return rc;
 	c->hK->budget_remaining = primary_rays;
+	c->mapped = false; // a budget of its own ends mapped mode (tyr_set_sample_map)
 	return push_counters(c);
 }
 

@@ -90,6 +90,8 @@ void denoise_free(tyr_ctx* c);
 void temporal_free(tyr_ctx* c);
 // host/svgf.cpp: wait for the last tyr_svgf call; free its history, scratch and event (tyr_destroy)
 void svgf_free(tyr_ctx* c);
+// host/adaptive.cpp: wait for the last tyr_allocate_samples call; free the ticket list and the scratch (tyr_destroy)
+void adaptive_free(tyr_ctx* c);
 // AoS import / export (host/staged_api.cpp): physical slots that hold a record, per segment counter array `seg` (device pointer)
 int valid_slots(const uint32_t* dSeg, std::vector<uint32_t>& slots, uint32_t* total = nullptr);
 void dense_counts(uint32_t n, uint32_t* cnt /* [kSegs * kSegStride] */);

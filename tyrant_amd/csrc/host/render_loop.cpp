@@ -419,14 +419,9 @@ static int render_run_ahead(tyr_ctx* c, uint32_t max_iterations, uint32_t& it) {
 	}
 }
 
-int tyr_render(tyr_ctx* c, uint32_t spp, uint32_t max_iterations, uint32_t* iterations_out) {
-	if (!c)
-		return TYR_ERR_INVALID;
-	int rc = tyr_set_budget(c, static_cast<uint64_t>(spp) * c->localPixels);
-	if (rc)
-		return rc;
-	if (!c->haveScene)
-		return TYR_ERR_NO_SCENE;
+// tyr_render's loop on the budget the ctx holds (tyr_render: spp per pixel; tyr_render_adaptive: a sample map's tickets)
+static int render_budget(tyr_ctx* c, uint32_t max_iterations, uint32_t* iterations_out) {
+	int rc = TYR_OK;
 	uint32_t it = 0;
 	c->unboundedRender = max_iterations == 0xFFFFFFFFu;
 	if (run_ahead_eligible(c)) {
@@ -465,6 +460,28 @@ int tyr_render(tyr_ctx* c, uint32_t spp, uint32_t max_iterations, uint32_t* iter
 	if (iterations_out)
 		*iterations_out = it;
 	return rc;
+}
+
+int tyr_render(tyr_ctx* c, uint32_t spp, uint32_t max_iterations, uint32_t* iterations_out) {
+	if (!c)
+		return TYR_ERR_INVALID;
+	int rc = tyr_set_budget(c, static_cast<uint64_t>(spp) * c->localPixels);
+	if (rc)
+		return rc;
+	if (!c->haveScene)
+		return TYR_ERR_NO_SCENE;
+	return render_budget(c, max_iterations, iterations_out);
+}
+
+int tyr_render_adaptive(tyr_ctx* c, const uint32_t* spp_map, void* stream, uint32_t max_iterations, uint32_t* iterations_out) {
+	if (!c)
+		return TYR_ERR_INVALID;
+	int rc = tyr_set_sample_map(c, spp_map, stream, nullptr); // budget_remaining = T, mapped mode
+	if (rc)
+		return rc;
+	if (!c->haveScene)
+		return TYR_ERR_NO_SCENE;
+	return render_budget(c, max_iterations, iterations_out);
 }
 
 } // extern "C"
