@@ -201,6 +201,9 @@ void orc_default_spheres(orc_sphere out[ORC_NUM_SPHERES]); /* kernel.cu:674-680 
 void orc_set_camera(orc_ctx* c, const orc_camera* cam);
 void orc_set_sun_position(orc_ctx* c, float x, float y);
 void orc_set_budget(orc_ctx* c, uint64_t primary_rays);
+/* the frame counter every seed is built from (tyr_set_frame): the next iteration runs at `frame`; 0 is ignored (the reference
+ * never has it, kernel.cu:736-739) */
+void orc_set_frame(orc_ctx* c, uint32_t frame);
 /* one wavefront iteration == one launch_kernels call + the caller's swap (kernel.cu:664-748, main.cpp:168-169) */
 int orc_launch_kernels(orc_ctx* c);
 /* iterate until spp * local_pixels primaries were generated and the queue drained; returns iterations */

@@ -182,6 +182,12 @@ void orc_set_sun_position(orc_ctx* c, float x, float y) {
 	c->sun_position_changed = 1;
 }
 void orc_set_budget(orc_ctx* c, uint64_t primary_rays) { c->k.budget_remaining = primary_rays; }
+void orc_set_frame(orc_ctx* c, uint32_t frame) {
+	if (frame == 0)
+		return;
+	c->frame = frame;
+	c->k.frame = frame;
+}
 void orc_get_counters(const orc_ctx* c, orc_counters* out) { *out = c->k; }
 const float* orc_blit_buffer(const orc_ctx* c) { return c->blit_buffer; }
 const orc_ray* orc_ray_queue(const orc_ctx* c, int which) { return which == 0 ? c->ray_buffer : c->ray_buffer_next; }

@@ -143,6 +143,7 @@ def lib() -> C.CDLL:
         L.orc_set_camera.argtypes = [P, C.POINTER(CameraC)]
         L.orc_set_sun_position.argtypes = [P, c_f, c_f]
         L.orc_set_budget.argtypes = [P, c_u64]
+        L.orc_set_frame.argtypes = [P, c_u32]
         L.orc_launch_kernels.restype = c_i
         L.orc_launch_kernels.argtypes = [P]
         L.orc_render.restype = c_i
@@ -303,6 +304,9 @@ class Oracle:
 
     def set_budget(self, n):
         self.L.orc_set_budget(self.h, n)
+
+    def set_frame(self, frame):
+        self.L.orc_set_frame(self.h, frame)
 
     def load_scene(self, scene, nodes, prims):
         self.upload(nodes, prims)

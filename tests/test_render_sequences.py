@@ -74,7 +74,7 @@ class Sides:
     """an oracle ctx and (with `hip`) a HIP ctx on the same scene; every operation goes to both and is followed by a comparison.
     `log` keeps, per operation, the oracle's counters before and after it and what it returned."""
 
-    def __init__(self, orc, hip, scene, W, H, N, rank=0, nranks=1, profile="default"):
+    def __init__(self, orc, hip, scene, W, H, N, rank=0, nranks=1, profile="default", hip_flags=0):
         sc, nodes, prims = scene
         flags = (1 if sc.triangle_materials else 0) | (8 if sc.light_list else 0) | (16 if sc.triangle_colors else 0)
         self.sc, self.W, self.H, self.N, self.rank, self.nranks = sc, W, H, N, rank, nranks
@@ -83,7 +83,7 @@ class Sides:
         self.o.load_scene(sc, nodes, prims)
         self.g = None
         if hip is not None:
-            self.g = hip.Renderer(W, H, N, rank=rank, nranks=nranks, flags=flags | (FLAG_PROFILE if profile in COUNTED else 0))
+            self.g = hip.Renderer(W, H, N, rank=rank, nranks=nranks, flags=flags | hip_flags | (FLAG_PROFILE if profile in COUNTED else 0))
             self.g.load_scene(sc, nodes, prims)
             self.g.set_tuning(**PROFILES[profile])
         self.donor = orc.Oracle(W, H, N, rank=rank, nranks=nranks, flags=flags)  # a second ctx whose survivors import_work_queue hands over
