@@ -165,6 +165,10 @@ int orc_bvh_intersect(const orc_node* nodes, const orc_triangle* prims, orc_ray*
 void orc_bvh_intersect_batch(const orc_node* nodes, const orc_triangle* prims, orc_ray* rays, int n, int* hit_out);
 int orc_bvh_intersect_simple(const orc_node* nodes, const orc_triangle* prims, const orc_shadow* ray, float closestAllowed, uint64_t* counters);
 float orc_sphere_intersect(const orc_sphere* s, const float origin[3], const float direction[3]); /* kernel.cu:83-93 */
+/* order-free comparator for the tests of the visit-order rule: brute force over all nPrims triangles, nearest t with
+ * t > epsilon && tmax - t > epsilon, first (last_on_ties: last) index on equal t; a miss gives t_out = tmax, id_out = -1 */
+void orc_brute_closest_batch(const orc_triangle* prims, int nPrims, const float* origin, const float* direction, const float* tmax, int n,
+                             int last_on_ties, float* t_out, int32_t* id_out);
 
 void orc_bbox_host_ops(const float* vertices, int n, orc_bbox* bbox_out, float* out2); /* Bbox.h:8-36 */
 /* the v3 helpers of orc_internal.h (glm's evaluation order) over arrays of float3: op codes of oracle/ref_harness.cpp ref_glm */

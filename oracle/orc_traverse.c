@@ -113,6 +113,31 @@ void orc_bvh_intersect_batch(const orc_node* nodes, const orc_triangle* prims, o
 		hit_out[i] = orc_bvh_intersect(nodes, prims, &rays[i], NULL);
 }
 
+/* The ORDER-FREE comparator (no restatement of anything in the reference): every triangle in array order through
+ * Triangle::intersect above, the smallest t with t > epsilon && tmax - t > epsilon kept -- the first index on equal t, or the
+ * last with last_on_ties.  bvh.h:134 is a left fold in visit order ((dist - t) > epsilon lets the hit tested first keep
+ * its place against a nearer one less than epsilon ahead); a ray is "order-sensitive" when the tree's answer is not this. */
+void orc_brute_closest_batch(const orc_triangle* prims, int nPrims, const float* origin, const float* direction, const float* tmax, int n,
+                             int last_on_ties, float* t_out, int32_t* id_out) {
+	for (int r = 0; r < n; ++r) {
+		const float* o = origin + 3 * r;
+		const float* d = direction + 3 * r;
+		float best = tmax[r];
+		int32_t id = -1;
+		for (int i = 0; i < nPrims; ++i) {
+			float t = orc_triangle_intersect(&prims[i], o, d);
+			if (!(t > ORC_EPSILON && (tmax[r] - t) > ORC_EPSILON))
+				continue;
+			if (id < 0 || t < best || (last_on_ties && t == best)) {
+				best = t;
+				id = i;
+			}
+		}
+		t_out[r] = best;
+		id_out[r] = id;
+	}
+}
+
 /* bvh.h:213-256 */
 int orc_bvh_intersect_simple(const orc_node* nodes, const orc_triangle* prims, const orc_shadow* ray, float closestAllowed, uint64_t* counters) {
 	float closestIntersection = closestAllowed;

@@ -129,6 +129,7 @@ def lib() -> C.CDLL:
         L.orc_bvh_intersect_batch.argtypes = [P, P, P, c_i, P]
         L.orc_bvh_intersect_simple.restype = c_i
         L.orc_bvh_intersect_simple.argtypes = [P, P, P, c_f, C.POINTER(c_u64)]
+        L.orc_brute_closest_batch.argtypes = [P, c_i, P, P, P, c_i, c_i, P, P]
         L.orc_sphere_intersect.restype = c_f
         L.orc_sphere_intersect.argtypes = [P, fp, fp]
         L.orc_create.restype = P
@@ -233,6 +234,19 @@ def bvh_build(tris: np.ndarray, bboxes: np.ndarray, algo: int = 2):
     if nn < 0:
         raise RuntimeError(f"orc_bvh_build failed: {nn}")
     return nodes[:nn].copy(), prims
+
+
+def brute_closest(prims: np.ndarray, origin, direction, tmax, last_on_ties: bool = False):
+    """(t, id) of the order-free comparator (orc_brute_closest_batch): the nearest accepted triangle of ALL of prims"""
+    prims = np.ascontiguousarray(prims)
+    o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    tm = np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, dtype=np.float32), (n,)))
+    t = np.zeros(n, dtype=np.float32)
+    ident = np.zeros(n, dtype=np.int32)
+    lib().orc_brute_closest_batch(_ptr(prims), prims.shape[0], _ptr(o), _ptr(d), _ptr(tm), n, int(last_on_ties), _ptr(t), _ptr(ident))
+    return t, ident
 
 
 def sun_setup(sun_position=(0.05, 0.3)) -> SunParams:

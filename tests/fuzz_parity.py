@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""tests/fuzz_parity.py [n] [seed] -- randomised end-to-end parity: random scenes (triangle soups and height-field meshes of
+"""tests/fuzz_parity.py [n] [seed] [layers] -- randomised end-to-end parity: random scenes (triangle soups and height-field meshes of
 random size, with and without per-triangle materials, emissive triangles and colour palettes), random resolutions, pixel shards (rank / nranks), queue sizes, cameras and
 launch-shape knobs (merged / separate traversal launches, run-ahead, work distribution);
 each render is compared with the oracle's: identical iteration and ray counts, queues of the last iteration bit-exact,
-radiance within 1e-5 relative.  A checker like the tests (it is the only other place that drives the oracle), not collected by pytest (run time grows with n); prints one line per case."""
+radiance within 1e-5 relative.  A checker like the tests (it is the only other place that drives the oracle); prints one line per case.
+As a script its run time grows with n; tests/test_visit_order.py runs a seeded slice of it (draw_case / run_case) with `layers`:
+a third of the cases then wrap the drawn scene in layered_scenes.layered, so that hits depend on the reference's visit order."""
 import os
 import sys
 
@@ -13,10 +15,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import pyorc  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 12
-rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 1)
-bad = 0
-for case in range(n_cases):
+
+def draw_case(rng, case=0, layers=False):
+    """one random case: every draw of the script's loop, in its order (so that a seed names the same cases as before); with
+    `layers` every third case has its scene wrapped in layered_scenes.layered(...)"""
     kind = rng.integers(0, 3)
     if kind == 0:
         sc = scenes.cornell_soup(int(rng.integers(50, 6000)), seed=int(rng.integers(1, 1 << 30)))
@@ -47,19 +49,32 @@ for case in range(n_cases):
         sc.palette_color = rng.uniform(0.05, 1.0, (256, 3)).astype(np.float32)
         sc.palette_emission = rng.uniform(0.0, 6.0, (256, 3)).astype(np.float32)
         sc.name += "+colors"
+    layout_on_device = int(rng.integers(0, 2))  # where tyr_scene_upload's layout pass runs: the same bytes either way
+    build_upload = bool(rng.random() < 0.25)  # ... or the tree built and laid out on the device in one call (tyr_scene_build_upload): the same scene again
+    sun = (float(rng.uniform(0, 1)), float(rng.uniform(0.05, 0.49)))
+    if layers and case % 3 == 0:  # (no draw of `rng`: the other cases stay what they are without `layers`)
+        import layered_scenes
+
+        sc.triangles = layered_scenes.layered(sc.triangles, layered_scenes.OFFSETS, 1000 + case)
+        sc.name += "+layers"
+    return dict(case=case, sc=sc, W=W, H=H, rank=rank, nranks=nranks, N=N, spp=spp, cam=cam, knobs=knobs, layout_on_device=layout_on_device, build_upload=build_upload, sun=sun)
+
+
+def run_case(c):
+    """(ok, why, line): the case rendered by the oracle and by the library, compared as the module docstring says"""
+    sc, W, H, N, rank, nranks, spp, cam, knobs = c["sc"], c["W"], c["H"], c["N"], c["rank"], c["nranks"], c["spp"], c["cam"], c["knobs"]
     flags = (1 if sc.triangle_materials else 0) | (8 if sc.light_list else 0) | (16 if sc.triangle_colors else 0)
     bb = scenes.triangle_bboxes(sc.triangles)
     nodes, prims = pyorc.bvh_build(sc.triangles, bb)
     o = pyorc.Oracle(W, H, N, rank=rank, nranks=nranks, flags=flags)
     g = binding.Renderer(W, H, N, rank=rank, nranks=nranks, flags=flags)
-    g.set_tuning(layout_on_device=int(rng.integers(0, 2)))  # where tyr_scene_upload's layout pass runs: the same bytes either way
+    g.set_tuning(layout_on_device=c["layout_on_device"])
     for r in (o, g):
         r.load_scene(sc, nodes, prims)
         r.set_camera(cam)
-    if rng.random() < 0.25:  # ... or the tree built and laid out on the device in one call (tyr_scene_build_upload): the same scene again
+    if c["build_upload"]:
         g.build_upload(sc.triangles, bb, want_nodes=False)
-    sun = (float(rng.uniform(0, 1)), float(rng.uniform(0.05, 0.49)))
-    o.set_sun_position(*sun), g.set_sun_position(*sun)
+    o.set_sun_position(*c["sun"]), g.set_sun_position(*c["sun"])
     g.set_tuning(**knobs)
     ok, why = True, ""
     try:
@@ -84,8 +99,24 @@ for case in range(n_cases):
             ok, why = False, why + " queues differ"
     except Exception as e:  # noqa: BLE001
         ok, why = False, repr(e)
-    bad += not ok
-    print(f"case {case:3d} {sc.name:26s} {len(sc.triangles):7d} tris {W:3d}x{H:<3d} rank {rank}/{nranks} N={N:5d} spp={spp} lens={cam.lensRadius:.2f} {knobs} -> {'ok' if ok else 'FAIL ' + why}", flush=True)
+    line = f"case {c['case']:3d} {sc.name:26s} {len(sc.triangles):7d} tris {W:3d}x{H:<3d} rank {rank}/{nranks} N={N:5d} spp={spp} lens={cam.lensRadius:.2f} {knobs} -> {'ok' if ok else 'FAIL ' + why}"
     g.close()
-print("failures:", bad)
-sys.exit(1 if bad else 0)
+    o.close()
+    return ok, why, line
+
+
+def main(argv):
+    n_cases = int(argv[1]) if len(argv) > 1 else 12
+    rng = np.random.default_rng(int(argv[2]) if len(argv) > 2 else 1)
+    layers = len(argv) > 3 and argv[3] == "layers"
+    bad = 0
+    for case in range(n_cases):
+        ok, _, line = run_case(draw_case(rng, case, layers))
+        bad += not ok
+        print(line, flush=True)
+    print("failures:", bad)
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main(sys.argv))

@@ -10,6 +10,11 @@ loader.h where they lie (oracle/ref_harness.cpp):
     traversals                         CachedBVH::intersect_debug  bvh.h:164-209
     anyhit                             CachedBVH::intersectSimple  bvh.h:213-256
 The fixtures are data only: inputs and expected outputs.
+
+`layered` (tests/layered_scenes.py: layered_soup300, nine copies of every triangle within 0 .. 2.5 epsilon of each other) is the
+one fixture on which the answer depends on the reference's VISIT ORDER (bvh.h:134's `(dist - t) > epsilon`): on the other
+three the reference's answer is the nearest accepted hit for every ray.  Its any-hit limits sit within 2 ulp of
+float32(t* + epsilon) for the rays that hit, the edge of bvh.h:231.
 """
 import ctypes as C
 import os
@@ -19,9 +24,12 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import pyorc  # noqa: E402
 from tyrant_amd import scenes  # noqa: E402
+
+import layered_scenes  # noqa: E402
 
 
 def ray_set(sc, n, seed):
@@ -43,13 +51,31 @@ def ray_set(sc, n, seed):
     return rays, rng.uniform(5, 250, size=n).astype(np.float32)
 
 
+def layered_ray_set(sc, nodes, prims, n, seed, R):
+    """layered_scenes.ray_set's rays; every 7th pre-shortened as above; any-hit limits at the accept rule's edge"""
+    o, d = layered_scenes.ray_set(sc, nodes, n, seed)
+    rng = np.random.default_rng(seed + 1)
+    rays = np.zeros(n, dtype=scenes.RAY_DTYPE)
+    rays["origin"], rays["direction"], rays["distance"], rays["identifier"] = o, d, 1e20, -7
+    first = rays.copy()
+    hit = np.zeros(n, dtype=np.int32)
+    R.ref_bvh_intersect(nodes.ctypes.data, prims.ctypes.data, first.ctypes.data, n, hit.ctypes.data_as(C.POINTER(C.c_int)), None)
+    closest = rng.uniform(5, 250, size=n).astype(np.float32)
+    h = hit != 0
+    edge = (first["distance"] + np.float32(1e-3)).astype(np.float32)
+    closest[h] = (edge.view(np.int32) + (np.arange(n, dtype=np.int32) % 5 - 2)).view(np.float32)[h]
+    rays["distance"][::7] = rng.uniform(20, 200, size=len(rays["distance"][::7])).astype(np.float32)
+    return rays, closest
+
+
 def main():
     R = pyorc.ref()
     assert R is not None, "build oracle/_ref first (make -C oracle ref)"
     ip = C.POINTER(C.c_int)
-    for name, sc, n in (("cornell36", scenes.cornell_box(), 2048), ("soup2k", scenes.cornell_soup(2000), 4096), ("mesh32", scenes.mesh_scene(32), 4096)):
+    for name, sc, n in (("cornell36", scenes.cornell_box(), 2048), ("soup2k", scenes.cornell_soup(2000), 4096), ("mesh32", scenes.mesh_scene(32), 4096),
+                        ("layered", layered_scenes.MAKERS["layered_soup300"](), 4096)):
         nodes, prims = pyorc.bvh_build(sc.triangles, scenes.triangle_bboxes(sc.triangles))
-        rays, closest = ray_set(sc, n, 20261003)
+        rays, closest = layered_ray_set(sc, nodes, prims, n, 20261016, R) if name == "layered" else ray_set(sc, n, 20261003)
         out = rays.copy()
         hit = np.zeros(n, dtype=np.int32)
         trav = np.zeros(n, dtype=np.int32)

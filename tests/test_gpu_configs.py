@@ -167,7 +167,7 @@ def test_resolve_is_bit_exact(orc, hip):
     g.close()
 
 
-@pytest.mark.parametrize("name", ["cornell36", "soup2k", "mesh32"])
+@pytest.mark.parametrize("name", ["cornell36", "soup2k", "mesh32", "layered"])
 def test_reference_anyhit_fixture_through_the_connect_kernel(hip, name):
     """the committed answers of the reference's CachedBVH::intersectSimple (bvh.h:213-256), reproduced by the HIP connect
     kernel: the fixture's rays go in as ShadowQueue records with colour (1, 1, 1) and one pixel each; a pixel receives

@@ -181,7 +181,7 @@ def test_reference_traversal_fixture_through_the_abi(orc, hip):
     from conftest import GOLDEN
     from tyrant_amd import scenes
 
-    for name in ("cornell36", "soup2k", "mesh32"):
+    for name in ("cornell36", "soup2k", "mesh32", "layered"):
         z = np.load(os.path.join(GOLDEN, f"ref_traverse_{name}.npz"))
         nodes = np.ascontiguousarray(z["nodes"]).view(scenes.NODE_DTYPE).reshape(-1)
         prims = np.ascontiguousarray(z["prims"]).view(scenes.TRIANGLE_DTYPE).reshape(-1)

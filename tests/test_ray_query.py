@@ -166,7 +166,7 @@ def test_reference_fixtures_closest_and_any(hip):
     """tests/golden/ref_traverse_*.npz -- the reference's own bvh.h answers -- for every ray, the pre-shortened ones included"""
     from tyrant_amd import scenes
 
-    for name in ("cornell36", "soup2k", "mesh32"):
+    for name in ("cornell36", "soup2k", "mesh32", "layered"):
         z = np.load(os.path.join(GOLDEN, f"ref_traverse_{name}.npz"))
         nodes = np.ascontiguousarray(z["nodes"]).view(scenes.NODE_DTYPE).reshape(-1)
         prims = np.ascontiguousarray(z["prims"]).view(scenes.TRIANGLE_DTYPE).reshape(-1)
