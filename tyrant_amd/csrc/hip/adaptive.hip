@@ -486,7 +486,7 @@ __global__ void __launch_bounds__(kBlock) k_alloc_map(const AllocateArgs A) {
 
 void launch_primary_mapped(const FrameParams& P, const MappedPrimary& M, uint32_t maxNew, hipStream_t stream) {
 	// always launched: its last block is set_wavefront_globals
-	hipLaunchKernelGGL(k_primary_mapped, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), 0, stream, P, M);
+	launch_in_stage(k_primary_mapped, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), stream, P, M);
 }
 void launch_map_hist(const SampleMapArgs& A, uint32_t localPixels, hipStream_t stream) {
 	hipLaunchKernelGGL(k_map_hist, dim3(blocks_for(localPixels)), dim3(kBlock), 0, stream, A, localPixels);

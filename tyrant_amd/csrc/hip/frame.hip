@@ -184,6 +184,27 @@ __global__ void __launch_bounds__(kBlock) k_pad_holes(const FrameParams P, uint3
 	}
 }
 
+// the counter words the host changes between stages (kernels.hpp "CounterPoke"): one block, plain stores -- the launch is alone on the stream
+__global__ void __launch_bounds__(kBlock) k_poke_counters(DevCounters* __restrict__ k, const CounterPoke p) {
+	if (p.what & kPokeResetQueue) {
+		uint32_t* const seg = &k->seg[p.queue & 1u][0][0];
+		for (uint32_t i = threadIdx.x; i < kClasses * kSegs * kSegStride; i += kBlock)
+			seg[i] = 0u;
+		if (threadIdx.x < kClasses * kSegs)
+			(&k->segSurv[0][0])[threadIdx.x] = 0u;
+		if (threadIdx.x == 0)
+			k->primary_ray_cnt = 0u;
+	}
+	if (threadIdx.x == 0) {
+		if (p.what & kPokeBudget)
+			k->budget_remaining = p.budget;
+		if (p.what & kPokeLiveShadow) {
+			k->n_live = p.nLive;
+			k->shadow_ray_cnt = p.shadows;
+		}
+	}
+}
+
 // connect pre-pass: the sphere half of intersect_scene_simple (kernel.cu:168-172).  Any-hit does not
 // depend on test order, so spheres go first and an occluded ray never enters the BVH.
 // color.w (unused by the reference's 44-byte record) carries the flag.
@@ -472,17 +493,24 @@ __global__ void __launch_bounds__(kBlock) k_extend_debug(const FrameParams P) {
 // ---- launch wrappers ---------------------------------------------------------------------
 
 constexpr uint32_t kPrepassMaxBlocks = 8192; // 8 waves of 256 threads per SIMD of a 256-CU part: enough to stream at full rate
+StageEvents*& open_stage_events() {
+	static thread_local StageEvents* open = nullptr;
+	return open;
+}
+void launch_poke_counters(DevCounters* k, const CounterPoke& p, hipStream_t stream) {
+	hipLaunchKernelGGL(k_poke_counters, dim3(1), dim3(kBlock), 0, stream, k, p);
+}
 void launch_pad_holes(const FrameParams& P, bool workQueue, bool shadowQueue, hipStream_t stream, bool resetTickets) {
-	hipLaunchKernelGGL(k_pad_holes, dim3(2 * kSegs), dim3(kBlock), 0, stream, P, workQueue ? 1u : 0u, shadowQueue ? 1u : 0u, resetTickets ? 1u : 0u);
+	launch_in_stage(k_pad_holes, dim3(2 * kSegs), dim3(kBlock), stream, P, workQueue ? 1u : 0u, shadowQueue ? 1u : 0u, resetTickets ? 1u : 0u);
 }
 void launch_primary(const FrameParams& P, uint32_t maxNew, hipStream_t stream) {
 	// always launched: its last block is set_wavefront_globals
-	hipLaunchKernelGGL(k_primary, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), 0, stream, P);
+	launch_in_stage(k_primary, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), stream, P);
 }
 void launch_scan(const FrameParams& P, uint32_t maxLive, hipStream_t stream) {
 	if (maxLive == 0)
 		return;
-	hipLaunchKernelGGL(k_scan_words, dim3((maxLive + kScanBlockSlots - 1) / kScanBlockSlots), dim3(kBlock), 0, stream, P);
+	launch_in_stage(k_scan_words, dim3((maxLive + kScanBlockSlots - 1) / kScanBlockSlots), dim3(kBlock), stream, P);
 }
 void launch_vecmath_probe(int op, const float* a, const float* b, const float* c, uint32_t n, float* out, hipStream_t stream) {
 	hipLaunchKernelGGL(k_vecmath_probe, dim3(blocks_for(n ? n : 1)), dim3(kBlock), 0, stream, op, a, b, c, n, out);
@@ -492,20 +520,20 @@ void launch_sunsky_probe(const SunParams& S, int which, const float* dirs, uint3
 }
 void launch_extend_debug(const FrameParams& P, uint32_t maxLive, hipStream_t stream) {
 	if (maxLive != 0)
-		hipLaunchKernelGGL(k_extend_debug, dim3(blocks_for(maxLive)), dim3(kBlock), 0, stream, P);
+		launch_in_stage(k_extend_debug, dim3(blocks_for(maxLive)), dim3(kBlock), stream, P);
 }
 void launch_extend_spheres(const FrameParams& P, uint32_t nSurvivors, hipStream_t stream, uint32_t maxLive) {
 	// the grid also covers the hole padding at the ends of class 0's segments, which walks up to the extent of ALL this
 	// iteration's rays: a handful of survivors in front of a full top-up must not leave that walk to a single block
 	const uint32_t walk = std::max(nSurvivors, maxLive);
 	if (nSurvivors != 0)
-		hipLaunchKernelGGL(k_extend_spheres, dim3(std::min(blocks_for(walk), kPrepassMaxBlocks)), dim3(kBlock), 0, stream, P);
+		launch_in_stage(k_extend_spheres, dim3(std::min(blocks_for(walk), kPrepassMaxBlocks)), dim3(kBlock), stream, P);
 }
 void launch_connect_spheres(const FrameParams& P, uint32_t maxShadow, hipStream_t stream) {
-	hipLaunchKernelGGL(k_connect_spheres, dim3(std::min(blocks_for(maxShadow), kPrepassMaxBlocks)), dim3(kBlock), 0, stream, P);
+	launch_in_stage(k_connect_spheres, dim3(std::min(blocks_for(maxShadow), kPrepassMaxBlocks)), dim3(kBlock), stream, P);
 }
 void launch_resolve(const float4* blit, float4* out, uint32_t nPixels, hipStream_t stream) {
-	hipLaunchKernelGGL(k_resolve, dim3(blocks_for(nPixels)), dim3(kBlock), 0, stream, blit, out, nPixels);
+	launch_in_stage(k_resolve, dim3(blocks_for(nPixels)), dim3(kBlock), stream, blit, out, nPixels);
 }
 
 } // namespace tyr

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include "../../../include/tyr_c.h"
@@ -180,7 +181,7 @@ struct FrameParams {
 	uint32_t retireSky;           // k_primary: finish the camera rays that hit nothing (no sphere, not the root box) on the spot instead of queueing them for shade (tyr_render's merged path; the stage API keeps the reference's full queue)
 	uint32_t foldNextPrologue;    // k_scan_words: its last block also opens the NEXT iteration (set_wavefront_globals + the hole padding in front of its traversal launch): tyr_render one iteration ahead of the counts, once the budget is spent (no top-up can follow)
 	uint32_t prologueDone;        // the traversal launchers: the previous iteration's k_scan_words did that (no k_primary launch, no k_pad_holes)
-	uint32_t shadeOpensNext;      // k_shade: its last block opens the NEXT iteration (what foldNextPrologue has k_scan_words do) and keeps this iteration's n_live in scan_live[]: the scan is then left to the next traversal launch (scanPrevInTrace; TYR_TUNE_SCAN_IN_TRACE)
+	uint32_t shadeOpensNext;      // k_shade: its last block opens the NEXT iteration (what foldNextPrologue has k_scan_words do) and keeps this iteration's n_live in scan_live[]: the scan is then left to the next traversal launch (scanPrevInTrace; TYR_TUNE_SCAN_IN_TRACE).  2: the iteration ends the render -- its last block pads the shadow queue's segment ends and resets the traversal tickets for the launch that traces its shadow rays, which also does the scan; no iteration is opened
 	uint32_t scanSet;             // ... scan_live[scanSet & 1]: the iteration's parity
 	HostSnap* hostSnap;           // k_shade: its last block writes what the host's render loop steers by here (pinned host memory) -- no copy and no event between this launch and the next (TYR_TUNE_KERNEL_SNAPSHOT)
 	uint32_t snapSeq;             // ... stamped with this number, written last
@@ -215,6 +216,7 @@ struct Tuning {
 	int foldPrologue = 1;     // tyr_render one iteration ahead of the counts: once the budget is spent, an iteration's last kernel opens the next one (set_wavefront_globals, hole padding): two launches and two gaps fewer per iteration
 	int layoutOnDevice = 1;   // tyr_scene_upload: the reference's arrays go to the device as they are and hip/bvh_layout_dev.hip makes the records there (the same bytes); 0 = host/bvh_layout.cpp makes them and they are copied
 	int scanInTrace = 1;      // tyr_render one iteration ahead, the next iteration known to come without a top-up: no k_scan_words launch -- k_shade's last block opens that iteration and its traversal launch's waves do the slot scan on their way in (hip/scan_wave.hpp)
+	int stageTiming = 0;      // TYR_FLAG_PROFILE: 0 = a hipEventRecord in front of and behind every stage; 1 = a stage's events ride on its own launches (no packet between two kernels, but a timed dispatch costs as much: profiles/boundary_idle_ab.txt)
 	int kernelSnapshot = 1;   // tyr_render one iteration ahead: the counts the host waits for are written to pinned host memory by k_shade's last block instead of copied behind it and signalled by an event (two packets in the stream between this iteration's shade and the next traversal launch)
 	int foldSpheres = 1;      // merged path of tyr_render: shade does the sphere pre-passes' work for the rays it emits ; 0: k_extend_spheres / k_connect_spheres re-read them
 };
@@ -228,6 +230,45 @@ enum { kLcShade = 0, kLcTrace, kLcQuery, kLcKinds }; // kLcQuery: [any * 2 + sph
 struct LaunchCache {
 	int perCU[kLcKinds][6] = {};
 };
+
+// The counter words an entry point changes without running a stage (tyr_reset_accum, tyr_set_budget, the undo of an iteration that
+// tyr_render queued ahead for nothing): the host writes its mirror itself and sends only these words, in stream order, by one
+// one-block launch -- no copy of the whole struct in either direction and nothing for the host to wait for.
+enum : uint32_t {
+	kPokeResetQueue = 1u, // primary_ray_cnt = 0, seg[queue] = 0, segSurv = 0 (kernel.cu:712-718: the survivors go with the accumulation)
+	kPokeBudget = 2u,     // budget_remaining = budget
+	kPokeLiveShadow = 4u, // n_live = nLive, shadow_ray_cnt = shadows
+};
+struct CounterPoke {
+	uint32_t what = 0u; // kPoke* bits
+	uint32_t queue = 0u;
+	uint32_t nLive = 0u, shadows = 0u;
+	unsigned long long budget = 0ull;
+};
+void launch_poke_counters(DevCounters* k, const CounterPoke& p, hipStream_t stream);
+
+// TYR_FLAG_PROFILE with TYR_TUNE_STAGE_TIMING: the launches of the stage that is open on this thread carry the stage's start / stop
+// events themselves (hipExtLaunchKernelGGL: the time stamps of the dispatch's own completion signal) -- `start` rides on the
+// stage's first launch, `stop` on every launch, so that it ends up on the last one -- and the stream between two kernels holds
+// no marker packet.  Null: plain launches.
+struct StageEvents {
+	hipEvent_t start = nullptr, stop = nullptr;
+	uint32_t launches = 0u;
+};
+StageEvents*& open_stage_events();
+#if defined(__HIPCC__)
+// every kernel of a stage goes through this
+template <class... KArgs, class... Args>
+inline void launch_in_stage(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t stream, Args&&... args) {
+	StageEvents* const se = open_stage_events();
+	if (!se) {
+		hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<Args&&>(args)...);
+		return;
+	}
+	hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, se->launches == 0u ? se->start : nullptr, se->stop, 0, static_cast<Args&&>(args)...);
+	se->launches++;
+}
+#endif
 
 // launches (all on `stream`); grids are sized by the host from upper bounds, kernels bound-check
 // against the device counters

@@ -757,7 +757,19 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 			sh[17] = survivors;
 		}
 		__syncthreads();
-		if (sh[16] != 0u) {
+		if (sh[16] != 0u && PE.shadeOpensNext == 2u) {
+			// the iteration the host knows to end the render: no iteration follows, only the launch that traces this one's shadow rays.  Its
+			// two small launches are done here -- the holes at the ends of the shadow queue's segments, the traversal kernel's tickets -- and
+			// the slot scan is left to that launch like any other (scan_live[]); nothing of the next iteration is opened
+			if (tid < kSegs)
+				sh[kSegs + tid] = __hip_atomic_load(&PE.kc->seg[tid * kSegStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			if (tid < kTicketWords)
+				PE.k->extend_chunks[tid * 32] = 0;
+			if (tid == 0)
+				PE.k->scan_live[PE.scanSet & 1u] = PE.k->n_live;
+			__syncthreads();
+			pad_shadow_holes_counts(PE.shadow, sh + kSegs);
+		} else if (sh[16] != 0u) {
 			if (tid < kSegs)
 				sh[tid] = __hip_atomic_load(&PE.segNext[tid * kSegStride], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // class 0 of the next work queue
 			else if (tid < 2u * kSegs)
@@ -803,9 +815,9 @@ void launch_shade(const FrameParams& P0, uint32_t maxSlots, int numCUs, LaunchCa
 	FrameParams P = P0;
 	P.shadeBlocks = shade_grid(P, maxSlots, numCUs, lc);
 	if (P.flags & TYR_FLAG_LIGHT_LIST)
-		hipLaunchKernelGGL((k_shade<true>), dim3(P.shadeBlocks), dim3(kBlock), 0, stream, P);
+		launch_in_stage((k_shade<true>), dim3(P.shadeBlocks), dim3(kBlock), stream, P);
 	else
-		hipLaunchKernelGGL((k_shade<false>), dim3(P.shadeBlocks), dim3(kBlock), 0, stream, P);
+		launch_in_stage((k_shade<false>), dim3(P.shadeBlocks), dim3(kBlock), stream, P);
 }
 
 } // namespace tyr

@@ -1127,9 +1127,9 @@ void launch_trace(const FrameParams& P, uint32_t maxLive, uint32_t nSurvivors, u
 }
 void launch_trace_kernel(const FrameParams& P, uint32_t items, const Tuning& t, int numCUs, LaunchCache& lc, hipStream_t stream) {
 	if (t.wideBlockMinItems >= 0 && items >= (uint32_t)t.wideBlockMinItems)
-		hipLaunchKernelGGL((k_trace_flat<TYR_TRACE_STACK, kTraceBlockWide>), dim3(persistent_blocks(k_trace_flat<TYR_TRACE_STACK, kTraceBlockWide>, items, t, numCUs, lc.perCU[kLcTrace][1], kTraceBlockWide)), dim3(kTraceBlockWide), 0, stream, P);
+		launch_in_stage((k_trace_flat<TYR_TRACE_STACK, kTraceBlockWide>), dim3(persistent_blocks(k_trace_flat<TYR_TRACE_STACK, kTraceBlockWide>, items, t, numCUs, lc.perCU[kLcTrace][1], kTraceBlockWide)), dim3(kTraceBlockWide), stream, P);
 	else
-		hipLaunchKernelGGL((k_trace_flat<TYR_TRACE_STACK, (uint32_t)kBlock>), dim3(persistent_blocks(k_trace_flat<TYR_TRACE_STACK, (uint32_t)kBlock>, items, t, numCUs, lc.perCU[kLcTrace][0])), dim3(kBlock), 0, stream, P);
+		launch_in_stage((k_trace_flat<TYR_TRACE_STACK, (uint32_t)kBlock>), dim3(persistent_blocks(k_trace_flat<TYR_TRACE_STACK, (uint32_t)kBlock>, items, t, numCUs, lc.perCU[kLcTrace][0])), dim3(kBlock), stream, P);
 }
 void launch_trace_prepasses(const FrameParams& P, uint32_t nSurvivors, uint32_t maxShadowPrev, hipStream_t stream, uint32_t maxLive) {
 	FrameParams Pc = P;
@@ -1162,7 +1162,7 @@ void launch_extend(const FrameParams& P0, uint32_t maxLive, uint32_t nSurvivors,
 		launch_extend_spheres(P, nSurvivors, stream, maxLive);
 		P.raysPerBlock = kCountRaysPerBlock;
 		const uint32_t blocks = (P.segCap * kSegs + kCountRaysPerBlock - 1) / kCountRaysPerBlock; // every physical slot a record could lie in
-		hipLaunchKernelGGL((k_extend_count<12>), dim3(blocks), dim3(kBlock), 0, stream, P);
+		launch_in_stage((k_extend_count<12>), dim3(blocks), dim3(kBlock), stream, P);
 		return;
 	}
 	P.traceShadow = 0u;
@@ -1176,7 +1176,7 @@ void launch_connect(const FrameParams& P0, uint32_t maxShadow, bool countVisits,
 		launch_connect_spheres(P, maxShadow, stream);
 		P.raysPerBlock = kCountRaysPerBlock;
 		const uint32_t blocks = (P.segCap * kSegs + kCountRaysPerBlock - 1) / kCountRaysPerBlock;
-		hipLaunchKernelGGL((k_connect_count<12>), dim3(blocks), dim3(kBlock), 0, stream, P);
+		launch_in_stage((k_connect_count<12>), dim3(blocks), dim3(kBlock), stream, P);
 		return;
 	}
 	P.kcPrev = P.kc; // the rays of THIS iteration's shadow queue

@@ -144,6 +144,7 @@ struct tyr_ctx {
 
 	hipEvent_t ev[2][2 * TYR_K_COUNT]{}; // TYR_FLAG_PROFILE: start / stop per stage, two sets (iteration i uses set i & 1: two iterations may be queued)
 	bool evUsed[2][TYR_K_COUNT]{};
+	bool evEmpty[2][TYR_K_COUNT]{}; // TYR_TUNE_STAGE_TIMING: the stage launched nothing, its events are bound to no launch
 	tyr_timings timings{};
 };
 

@@ -8,6 +8,7 @@
 // (The render loop, the staged test hooks and the tuning / probe entry points are host/render_loop.cpp, host/staged_api.cpp and
 // host/tuning_probes.cpp; what they share is host/driver_internal.hpp.)
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -88,6 +89,8 @@ int sync_counters(tyr_ctx* c) {
 	HIPCHK(hipStreamSynchronize(c->stream));
 	return TYR_OK;
 }
+// the whole struct, ticket words included: only with an idle stream behind sync_counters (the imports, tyr_set_sample_map); an entry point that
+// changes a word or two sends those alone, in stream order (launch_poke_counters)
 int push_counters(tyr_ctx* c) {
 	HIPCHK(hipMemcpyAsync(c->dK, c->hK, sizeof(DevCounters), hipMemcpyHostToDevice, c->stream));
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -152,18 +155,33 @@ FrameParams make_params(const tyr_ctx* c) {
 	return P;
 }
 
+// Times one stage of a TYR_FLAG_PROFILE ctx between the start of its first launch and the end of its last one.
+// TYR_TUNE_STAGE_TIMING 1: the launches carry the two events themselves (kernels.hpp "StageEvents"); 0: an event record in front of
+// and behind the stage, each a packet of its own between two kernels.
 struct KernelTimer {
 	tyr_ctx* c;
 	int k;
-	bool on;
-	KernelTimer(tyr_ctx* c_, int k_) : c(c_), k(k_), on((c_->cfg.flags & TYR_FLAG_PROFILE) != 0 && ((c_->tuning.profileMask >> k_) & 1) != 0) {
-		if (on)
+	bool on, attached;
+	tyr::StageEvents se;
+	KernelTimer(tyr_ctx* c_, int k_) : c(c_), k(k_), on((c_->cfg.flags & TYR_FLAG_PROFILE) != 0 && ((c_->tuning.profileMask >> k_) & 1) != 0), attached(on && c_->tuning.stageTiming != 0) {
+		if (attached) {
+			assert(tyr::open_stage_events() == nullptr); // stages do not nest: one is open per thread at a time
+			se.start = c->ev[c->iter & 1u][2 * k];
+			se.stop = c->ev[c->iter & 1u][2 * k + 1];
+			tyr::open_stage_events() = &se;
+		} else if (on) {
 			(void)hipEventRecord(c->ev[c->iter & 1u][2 * k], c->stream);
+		}
 	}
 	~KernelTimer() {
-		if (on) {
+		if (attached) {
+			tyr::open_stage_events() = nullptr;
+			c->evUsed[c->iter & 1u][k] = true;
+			c->evEmpty[c->iter & 1u][k] = se.launches == 0u; // (a stage that launched nothing bound no event: it counts with no time, as an empty event pair does)
+		} else if (on) {
 			(void)hipEventRecord(c->ev[c->iter & 1u][2 * k + 1], c->stream);
 			c->evUsed[c->iter & 1u][k] = true;
+			c->evEmpty[c->iter & 1u][k] = false;
 		}
 	}
 };
@@ -175,7 +193,7 @@ void collect_timings_of(tyr_ctx* c, int set) {
 		if (!c->evUsed[set][k])
 			continue;
 		float ms = 0.0f;
-		hipError_t e = hipEventElapsedTime(&ms, c->ev[set][2 * k], c->ev[set][2 * k + 1]);
+		hipError_t e = c->evEmpty[set][k] ? hipSuccess : hipEventElapsedTime(&ms, c->ev[set][2 * k], c->ev[set][2 * k + 1]);
 		if (e == hipErrorNotReady) { // (TYR_TUNE_KERNEL_SNAPSHOT: the host may be here a moment before the stage's closing event has been processed)
 			(void)hipGetLastError();
 			if (hipEventSynchronize(c->ev[set][2 * k + 1]) == hipSuccess)
@@ -233,13 +251,15 @@ int stage_begin(tyr_ctx* c) {
 	}
 	if (reset) { // kernel.cu:712-718
 		HIPCHK(hipMemsetAsync(c->blit, 0, sizeof(float4) * static_cast<size_t>(c->cfg.width) * c->cfg.height, c->stream));
-		c->hK->primary_ray_cnt = 0;
-		HIPCHK(hipMemcpyAsync(&c->dK->primary_ray_cnt, &c->hK->primary_ray_cnt, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 		// ... and with it the survivors in the work queue (the next top-up regenerates all N slots, quirk 16)
+		c->hK->primary_ray_cnt = 0;
 		std::memset(&c->hK->seg[c->cur][0][0], 0, sizeof c->hK->seg[0]);
 		std::memset(c->hK->segSurv, 0, sizeof c->hK->segSurv);
-		HIPCHK(hipMemsetAsync(&c->dK->seg[c->cur][0][0], 0, sizeof c->dK->seg[0], c->stream));
-		HIPCHK(hipMemsetAsync(c->dK->segSurv, 0, sizeof c->dK->segSurv, c->stream));
+		tyr::CounterPoke p;
+		p.what = tyr::kPokeResetQueue;
+		p.queue = static_cast<uint32_t>(c->cur);
+		launch_poke_counters(c->dK, p, c->stream);
+		HIPCHK(hipGetLastError());
 	}
 	return TYR_OK;
 }
@@ -298,6 +318,15 @@ void enqueue_shade(tyr_ctx* c, const FrameParams& P, uint32_t nLive) {
 void enqueue_connect(tyr_ctx* c, const FrameParams& P0, uint32_t maxShadow) {
 	FrameParams P = P0;
 	P.prevFolded = c->lastShadeFolded ? 1u : 0u;
+	if (c->scanCarried) {
+		// the shade launch of the iteration that ended the render (FrameParams::shadeOpensNext == 2) has padded the shadow queue and reset
+		// the tickets, and left its slot scan to this launch: no k_scan_words, no k_pad_holes in front of it
+		P.prologueDone = 1u;
+		P.scanPrevInTrace = 1u;
+		P.scanLivePrev = &c->dK->scan_live[c->scanCarriedSet];
+		P.retireGhosts = (c->tuning.foldSpheres && c->tuning.retireSky && c->unboundedRender) ? 1u : 0u; // (as the iteration's own launches had it: the scan clears the survive bytes with it)
+		c->scanCarried = false;
+	}
 	KernelTimer t(c, TYR_K_CONNECT);
 	launch_connect(P, maxShadow, (c->cfg.flags & TYR_FLAG_COUNT_VISITS) != 0, c->tuning, c->numCUs, c->launchCache, c->stream);
 }
@@ -901,11 +930,16 @@ int tyr_set_budget(tyr_ctx* c, uint64_t primary_rays) {
 	int rc = use_device(c);
 	if (rc)
 		return rc;
-	if ((rc = sync_counters(c)))
-		return rc;
+	// the host mirror is current (every entry point that enqueues work leaves it so): the one word that changes is written on both
+	// sides, the device's in stream order -- nothing to copy back and nothing to wait for
 	c->hK->budget_remaining = primary_rays;
 	c->mapped = false; // a budget of its own ends mapped mode (tyr_set_sample_map)
-	return push_counters(c);
+	tyr::CounterPoke p;
+	p.what = tyr::kPokeBudget;
+	p.budget = primary_rays;
+	launch_poke_counters(c->dK, p, c->stream);
+	HIPCHK(hipGetLastError());
+	return TYR_OK;
 }
 
 int tyr_set_frame(tyr_ctx* c, uint32_t frame) {
@@ -973,13 +1007,18 @@ int tyr_reset_accum(tyr_ctx* c) {
 	int rc = use_device(c);
 	if (rc)
 		return rc;
-	if ((rc = sync_counters(c)))
-		return rc;
+	// the clear and the counter words that go with it are stream operations in front of the next launch; the host writes its mirror
+	// itself and waits for neither
 	HIPCHK(hipMemsetAsync(c->blit, 0, sizeof(float4) * static_cast<size_t>(c->cfg.width) * c->cfg.height, c->stream));
 	c->hK->primary_ray_cnt = 0;
 	std::memset(&c->hK->seg[c->cur][0][0], 0, sizeof c->hK->seg[0]);
 	std::memset(c->hK->segSurv, 0, sizeof c->hK->segSurv);
-	return push_counters(c);
+	tyr::CounterPoke p;
+	p.what = tyr::kPokeResetQueue;
+	p.queue = static_cast<uint32_t>(c->cur);
+	launch_poke_counters(c->dK, p, c->stream);
+	HIPCHK(hipGetLastError());
+	return TYR_OK;
 }
 
 int tyr_read_accum(tyr_ctx* c, float* host_float4) {

@@ -97,7 +97,7 @@ static void print_wave_anatomy(const float2* dHit, unsigned long long feedTicks)
 #endif
 
 static int launch_iteration(tyr_ctx* c, bool pipelined) {
-	// hK is current: every entry point that enqueues work ends with sync_counters
+	// hK is current: every entry point that enqueues work ends with sync_counters, or has written the words it changed on both sides itself
 	int rc = stage_begin(c);
 	if (rc)
 		return rc;
@@ -196,7 +196,9 @@ struct IterationPlan {
 };
 // foldNext: this iteration's k_scan_words also opens the next one (no top-up can follow and the next one IS going to be queued);
 // prologueDone: the previous iteration's did that for this one -- no k_primary launch, no k_pad_holes
-static int enqueue_merged_iteration(tyr_ctx* c, const IterationPlan& p, bool begun, bool foldNext = false, bool prologueDone = false) {
+// endsRender: the host knows that no iteration follows this one (budget spent, kMaxBounces iterations since the last top-up): its shade
+// launch's last block prepares the launch that traces its shadow rays (hole padding, tickets) and leaves the slot scan to it
+static int enqueue_merged_iteration(tyr_ctx* c, const IterationPlan& p, bool begun, bool foldNext = false, bool prologueDone = false, bool endsRender = false) {
 	int rc = begun ? TYR_OK : stage_begin(c);
 	if (rc)
 		return rc;
@@ -212,7 +214,10 @@ static int enqueue_merged_iteration(tyr_ctx* c, const IterationPlan& p, bool beg
 	const bool aside = foldNext && c->tuning.scanInTrace != 0;
 	P.foldNextPrologue = (foldNext && !aside) ? 1u : 0u;
 	P.shadeOpensNext = aside ? 1u : 0u; // k_shade's last block opens the next iteration, whose traversal launch does this iteration's slot scan on its way in (TYR_TUNE_SCAN_IN_TRACE)
-	if (aside) {
+	const bool closes = endsRender && !foldNext && c->tuning.scanInTrace != 0;
+	if (closes)
+		P.shadeOpensNext = 2u;
+	if (aside || closes) {
 		P.scanSet = static_cast<uint32_t>(set);
 		P.scanLive = &c->dK->scan_live[set];
 	}
@@ -258,7 +263,7 @@ static int render_run_ahead(tyr_ctx* c, uint32_t max_iterations, uint32_t& it) {
 	if ((rc = stage_begin(c))) // may reset the accumulation and the survivor count (kernel.cu:712-718): before the plan is made
 		return rc;
 	const uint64_t N = c->cfg.queue_size;
-	// exact state in front of iteration 0 (hK is current: every entry point ends with sync_counters)
+	// exact state in front of iteration 0 (hK is current: every entry point ends with sync_counters or writes both sides itself)
 	uint64_t s = c->hK->primary_ray_cnt, budget = c->hK->budget_remaining;
 	uint32_t nNew = static_cast<uint32_t>(std::min<uint64_t>(N - s, budget));
 	uint32_t live = static_cast<uint32_t>(s) + nNew; // live(enq - 1), exact
@@ -298,7 +303,10 @@ static int render_run_ahead(tyr_ctx* c, uint32_t max_iterations, uint32_t& it) {
 			const bool opened = folded; // iteration enq - 1's k_scan_words has done this one's set_wavefront_globals and hole padding
 			foldedPrev = folded;
 			folded = mayFold && budget == 0 && queued_ahead_behind(enq, 0, lastBirth); // (budget == 0: iteration enq tops nothing up, gives birth to nothing)
-			if ((rc = enqueue_merged_iteration(c, IterationPlan{ newMax, liveMax, live, live }, false, folded, opened))) {
+			// iteration enq cannot leave a survivor (the same bound as canHaveSurvivors below, one iteration on): if it has rays at all it is
+			// the render's last, and the launch queued behind it is the one that traces its shadow rays (flushedEarly)
+			const bool endsRender = mayFold && budget == 0 && !(enq < lastBirth + static_cast<uint32_t>(kMaxBounces));
+			if ((rc = enqueue_merged_iteration(c, IterationPlan{ newMax, liveMax, live, live }, false, folded, opened, endsRender))) {
 				(void)hipStreamSynchronize(c->stream); // (the failed iteration may be partly queued; nothing of it is the render's)
 				c->scanCarried = false;
 				c->shadowSet = shadowSetBefore;
@@ -438,22 +446,26 @@ static int render_budget(tyr_ctx* c, uint32_t max_iterations, uint32_t* iteratio
 		}
 	}
 	{
-		// the last shadow rays; counters refreshed (connect's included), nothing in flight when this returns
+		// the last shadow rays; counters refreshed (connect's included), nothing in flight when this returns: the render's one wait
 		int rcj = rc ? TYR_OK : flush_pending_shadow(c);
 		c->shadowPending = false;
+		if (c->runAheadUndo) {
+			// the empty iteration's set_wavefront_globals zeroed the live and shadow counts of the last real iteration: put back in
+			// stream order, in front of the copy that brings the final counters to the host
+			c->runAheadUndo = false;
+			if (!rcj) {
+				tyr::CounterPoke p;
+				p.what = tyr::kPokeLiveShadow;
+				p.nLive = c->undoLive;
+				p.shadows = c->undoShadows;
+				launch_poke_counters(c->dK, p, c->stream);
+				rcj = static_cast<int>(hipGetLastError());
+			}
+		}
 		if (!rcj)
 			rcj = sync_counters(c);
 		if (!rcj)
 			collect_timings(c); // (an iteration queued ahead may still have had its event pairs out)
-		if (c->runAheadUndo) {
-			// the empty iteration's set_wavefront_globals zeroed the live and shadow counts of the last real iteration
-			c->runAheadUndo = false;
-			if (!rcj) {
-				c->hK->n_live = c->undoLive;
-				c->hK->shadow_ray_cnt = c->undoShadows;
-				rcj = push_counters(c);
-			}
-		}
 		if (!rc)
 			rc = rcj ? rcj : check_device_error(c);
 	}

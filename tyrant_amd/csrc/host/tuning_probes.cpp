@@ -214,6 +214,7 @@ int tyr_set_tuning(tyr_ctx* c, int key, int value) {
 		{ TYR_TUNE_LAYOUT_ON_DEVICE, 0, 1, &Tuning::layoutOnDevice },
 		{ TYR_TUNE_SCAN_IN_TRACE, 0, 1, &Tuning::scanInTrace },
 		{ TYR_TUNE_KERNEL_SNAPSHOT, 0, 1, &Tuning::kernelSnapshot },
+		{ TYR_TUNE_STAGE_TIMING, 0, 1, &Tuning::stageTiming },
 	};
 	for (const Knob& k : knobs) {
 		if (k.key != key)
