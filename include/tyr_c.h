@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -795,6 +795,78 @@ typedef struct tyr_allocate_params {
 	uint32_t min_spp, max_spp;
 } tyr_allocate_params;
 int tyr_allocate_samples(tyr_ctx* ctx, const float* error, const tyr_allocate_params* params, uint32_t* spp_map_out, uint64_t* total_out, void* stream);
+
+/* ---- Temporal anti-aliasing of the resolved frame (extension; INTEGRATION.md 4j, DESIGN.md "Temporal anti-aliasing") --------
+ * The last stage of the frame pipeline: the RESOLVED frame -- behind the tone map -- is blended into the ctx's history of its own
+ * outputs, sampled where the nearest surface of the pixel's 3 x 3 neighbourhood was one frame ago and clamped to the colour box
+ * of that neighbourhood.  The blend averages the render's per-frame jitter over 1 / alpha frames (anti-aliasing of geometry and
+ * albedo edges, which tyr_svgf's illumination filter leaves alone), and the clamp bounds what the history may contribute.
+ * Numeric contract as tyr_svgf's: one binary32 operation per operation below, in the order written, correctly rounded division
+ * and square root, no transcendental function.  max(a, b) is a > b ? a : b and min(a, b) is a < b ? a : b, exactly as written at
+ * each use (so signed zeros and NaNs have one answer); max(0, t) is t > 0 ? t : +0.
+ *   Inputs: full-frame DEVICE arrays indexed y * width + x: color float4, a resolved frame (tyr_resolve's, or tyr_denoise's /
+ *   tyr_svgf's with their RESOLVE flag): rgb in display space, a != 0 on pixels that were seen, (0, 0, 0, 0) elsewhere; depth from
+ *   tyr_render_aov (VERY_FAR: background); motion (float32 x 2) and prev_depth from tyr_render_motion.
+ *   Per pixel p = (x, y): seen = color_p.a != 0.  A pixel that is not seen outputs (0, 0, 0, 0), stores history validity 0 and is
+ *   never a tap of anything.  Everything below is for a seen p; c = color_p.rgb.
+ *   YCoCg of an rgb triple: Y = (0.25*r + 0.5*g) + 0.25*b; Co = 0.5*r - 0.5*b; Cg = (0.5*g - 0.25*r) - 0.25*b.  Back:
+ *   t = Y - Cg; r = t + Co; g = Y + Cg; b = t - Co.
+ *   Neighbourhood: taps dy = -1..1 (outer), dx = -1..1 (inner) at q = (x + dx, y + dy), skipping q outside the frame or not
+ *   seen (the centre always counts).  Per YCoCg channel k of color_q.rgb, from S1 = S2 = n = +0, mn = +inf, mx = -inf, in tap
+ *   order: S1_k += k_q; S2_k += k_q*k_q; n += 1; mn_k = k_q < mn_k ? k_q : mn_k; mx_k = k_q > mx_k ? k_q : mx_k.
+ *   Motion choice (dilation), over the same taps in the same order: the first tap is taken; a later tap replaces it when
+ *   depth_q < the taken tap's depth (the first tap wins ties).  With q the taken tap: depth_q < VERY_FAR and prev_depth_q <
+ *   VERY_FAR: m = motion_q; depth_q == VERY_FAR (the nearest surface is the background, which does not move): m = (0, 0);
+ *   otherwise, or when |m.x| < inf or |m.y| < inf fails: no history.
+ *   History position: qx = (float)x + m.x, qy = (float)y + m.y; unless -1 < qx < width and -1 < qy < height: no history.
+ *   x0 = floor(qx), fx = qx - x0 (y alike).
+ *   History sample, Catmull-Rom: without TYR_TAA_BILINEAR, when x0 >= 1, x0 + 2 < width, y0 >= 1, y0 + 2 < height and all 16
+ *   history pixels (x0 - 1 + i, y0 - 1 + j), i, j = 0..3, have validity != 0.  Per axis, with f = fx for wx and fy for wy:
+ *   w0 = f*(-0.5 + f*(1 - 0.5*f)); w1 = 1 + (f*f)*(-2.5 + 1.5*f); w2 = f*(0.5 + f*(2 - 1.5*f)); w3 = (f*f)*(-0.5 + 0.5*f).
+ *   Taps j = 0..3 (outer), i = 0..3 (inner): w = wx[i] * wy[j]; from +0: S_k += w * hist_k (rgb).  h = S: the weights are not
+ *   renormalised (in exact arithmetic they add up to 1).  At an integer position the weights are (-0, 1, 0, -0): h is the
+ *   history pixel itself.
+ *   History sample, bilinear: with TYR_TAA_BILINEAR, or where the Catmull-Rom condition fails: tyr_temporal's taps (x0, y0),
+ *   (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) in that order with weights gx*gy, fx*gy, gx*fy, fx*fy, gx = 1 - fx, gy = 1 - fy.
+ *   A tap is accepted when it is inside the frame and its history validity != 0.  Over the accepted taps in order, from +0:
+ *   S_k += w * hist_k, Wb += w.  Wb > 0: h_k = S_k / Wb; otherwise no history.
+ *   Box, per YCoCg channel k: mu = S1 / n; var = S2 / n - mu*mu; sd = sqrt(max(0, var)); e = gamma * sd; tl = mu - e;
+ *   th = mu + e; lo = min(max(tl, mn), mx), i.e. l0 = tl > mn ? tl : mn, lo = l0 < mx ? l0 : mx; hi = max(min(th, mx), mn), i.e.
+ *   h0 = th < mx ? th : mx, hi = h0 > mn ? h0 : mn.  This is lo = max(mn, mu - gamma*sd), hi = min(mx, mu + gamma*sd) with both
+ *   ends kept inside [mn, mx]: in exact arithmetic mn <= mu <= mx and the second compare of each does nothing, in binary32 mu
+ *   can leave [mn, mx] by an ulp, and then a constant frame would not be a fixed point.  The clamp of the history's YCoCg value
+ *   hk: t = hk > lo ? hk : lo; h'_k = t < hi ? t : hi.  It is a clamp, not a clip towards the centre: no division, so a flat
+ *   neighbourhood (sd = 0) is well defined.
+ *   Blend, with a history: per YCoCg channel o_k = h'_k + alpha * (c_k - h'_k), with c_k the YCoCg of c; out = (rgb of o, 1).
+ *   Without one (the first call on a ctx, TYR_TAA_RESET, any "no history" above): out = (c, 1) -- c itself, not through YCoCg.
+ *   No final clamp to [0, 1].
+ *   History: the call stores its output of every pixel (validity = out.a: 1 on seen pixels, 0 elsewhere) as the next call's
+ *   history.  The history is the call's own: it neither reads nor writes the histories or scratch of tyr_temporal, tyr_svgf or
+ *   tyr_denoise.
+ *   Parameters (NULL: the defaults): alpha in (0, 1] (0.2), gamma >= 0 and finite (1.5), flags; the defaults are discussed in
+ *   DESIGN.md "Temporal anti-aliasing".
+ *   Ordering and state: enqueued on `stream` (NULL: the ctx's stream); the call returns once it is.  It uses the ctx's device,
+ *   restores the caller's, needs no scene and touches no render state; the ctx's sharding plays no part (whole frames).  The
+ *   ctx owns the history (32 bytes per pixel: two ping-ponged float4 planes, allocated by the first call, freed by tyr_destroy,
+ *   not in tyr_scene_info's device_bytes); calls on one ctx are therefore ordered with each other whatever their streams.
+ *   device_rgba_out may be in->color itself (otherwise the two must not overlap): the kernel then writes the history plane
+ *   alone, and a device-to-device copy of that plane to device_rgba_out follows it on the same stream.
+ *   TYR_ERR_INVALID: ctx, in, color, depth, motion, prev_depth or device_rgba_out is NULL; a parameter out of range; an unknown
+ *   flag. */
+typedef struct tyr_taa_in {
+	const float* color;      /* width * height x 4: a RESOLVED frame */
+	const float* depth;      /* width * height, tyr_render_aov's */
+	const float* motion;     /* width * height x 2, tyr_render_motion's */
+	const float* prev_depth; /* width * height, tyr_render_motion's */
+} tyr_taa_in;
+#define TYR_TAA_RESET 1u    /* tyr_taa_params.flags: discard the TAA history before this frame */
+#define TYR_TAA_BILINEAR 2u /* tyr_taa_params.flags: sample the history bilinearly instead of with the 4 x 4 Catmull-Rom kernel */
+typedef struct tyr_taa_params {
+	float alpha;
+	float gamma;
+	uint32_t flags;
+} tyr_taa_params;
+int tyr_taa(tyr_ctx* ctx, const tyr_taa_in* in, const tyr_taa_params* params, void* device_rgba_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,9 @@ TYR_SVGF_RESET, TYR_SVGF_RESOLVE = 1, 2
 # tyr_svgf's defaults (host/svgf.cpp)
 SVGF_MAX_HISTORY, SVGF_DEPTH_TOLERANCE, SVGF_NORMAL_COS = 8, 0.05, 0.9
 SVGF_PASSES, SVGF_SIGMA_LUMINANCE, SVGF_SIGMA_DEPTH, SVGF_NORMAL_POWER_LOG2 = 3, 2.0, 0.02, 7
+TYR_TAA_RESET, TYR_TAA_BILINEAR = 1, 2
+# tyr_taa's defaults (host/taa.cpp; DESIGN.md "Temporal anti-aliasing", profiles/taa_bench_c3.json)
+TAA_ALPHA, TAA_GAMMA = 0.2, 1.5
 # Renderer.allocate_samples' defaults (DESIGN.md "Adaptive sampling", profiles/adaptive_bench_c3.json): every pixel keeps one
 # sample (the AOV / motion rays stay sample 0), and no pixel takes more than this many
 ADAPTIVE_MIN_SPP, ADAPTIVE_MAX_SPP = 1, 256
@@ -159,6 +162,16 @@ class SvgfParams(C.Structure):
                 ("sigma_depth", C.c_float), ("normal_power_log2", c_u32), ("flags", c_u32)]
 
 
+class TaaIn(C.Structure):
+    """tyr_taa_in: a resolved frame, render_aov's depth, render_motion's motion and prev_depth"""
+
+    _fields_ = [("color", P), ("depth", P), ("motion", P), ("prev_depth", P)]
+
+
+class TaaParams(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("gamma", C.c_float), ("flags", c_u32)]
+
+
 class AllocateParams(C.Structure):
     _fields_ = [("total", c_u64), ("min_spp", c_u32), ("max_spp", c_u32)]
 
@@ -244,6 +257,7 @@ SYMBOLS = {
     "tyr_set_sample_map": (C.c_int, [P, P, P, C.POINTER(c_u64)]),
     "tyr_render_adaptive": (C.c_int, [P, P, P, c_u32, C.POINTER(c_u32)]),
     "tyr_allocate_samples": (C.c_int, [P, P, P, P, C.POINTER(c_u64), P]),
+    "tyr_taa": (C.c_int, [P, P, P, P, P]),
 }
 
 _libs: dict = {}
@@ -795,6 +809,30 @@ class Renderer:
             if var is not None:
                 var.record_stream(stream)
         return (out, var) if want_variance else out
+
+    def taa(self, color, depth, motion, prev_depth, alpha=TAA_ALPHA, gamma=TAA_GAMMA, bilinear=False, reset=False, out=None, stream=None):
+        """tyr_taa: temporal anti-aliasing of a resolved frame against the ctx's own history of its outputs.  color (H, W, 4): a
+        resolved frame (resolve_into's, or denoise's / svgf's with resolve=True); depth (H, W) from render_aov; motion
+        (H, W, 2), prev_depth (H, W) from render_motion: contiguous float32 tensors on this ctx's device.  Returns the (H, W, 4)
+        float32 frame: `out` when given (it may be `color` itself: in place), else a new tensor.  bilinear=True samples the
+        history with four taps instead of the 4 x 4 Catmull-Rom kernel; reset=True discards the history first.  Runs on
+        `stream` (default: torch's current stream) and returns without waiting for it."""
+        import torch
+
+        n = self.H * self.W
+        f = torch.float32
+        ins = {"color": (color, f, 4 * n), "depth": (depth, f, n), "motion": (motion, f, 2 * n), "prev_depth": (prev_depth, f, n)}
+        if out is not None:
+            ins["out"] = (out, f, 4 * n)
+        dev = self._frame_tensors(ins)
+        if out is None:
+            out = torch.empty((self.H, self.W, 4), dtype=f, device=dev)
+        tin = TaaIn(color.data_ptr(), depth.data_ptr(), motion.data_ptr(), prev_depth.data_ptr())
+        prm = TaaParams(alpha, gamma, (TYR_TAA_RESET if reset else 0) | (TYR_TAA_BILINEAR if bilinear else 0))
+        self._on_stream(stream, lambda h: self.L.tyr_taa(self.h, C.byref(tin), C.byref(prm), out.data_ptr(), h), True, "tyr_taa")
+        if stream is not None:
+            out.record_stream(stream)
+        return out
 
     # ---- adaptive sampling (include/tyr_c.h "Adaptive sampling") ----
 

@@ -127,6 +127,13 @@ struct tyr_ctx {
 	uint32_t svgfCur = 0;
 	bool svgfHave = false;
 
+	// tyr_taa (host/taa.cpp): two planes of width * height (rgb, validity) pixels, allocated by the first call; plane taaCur
+	// is the last call's output (valid only when taaHave), taaDone the event behind that call
+	float4* dTaaHist = nullptr;
+	hipEvent_t taaDone = nullptr;
+	uint32_t taaCur = 0;
+	bool taaHave = false;
+
 	// tyr_set_sample_map / tyr_allocate_samples (host/adaptive.cpp): the sample map's ticket list (4 bytes per ticket, grown as needed),
 	// its length T and whether the camera rays take their pixels from it (mapped mode: until tyr_set_budget / tyr_render set a
 	// budget of their own); the list build's scratch -- the map at the local pixels, the summary + histogram the host reads back,

@@ -539,6 +539,7 @@ int tyr_destroy(tyr_ctx* c) {
 	denoise_free(c);
 	temporal_free(c);
 	svgf_free(c);
+	taa_free(c);
 	adaptive_free(c);
 	free_rayq(c->q[0]);
 	free_rayq(c->q[1]);

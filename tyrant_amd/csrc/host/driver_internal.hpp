@@ -90,6 +90,8 @@ void denoise_free(tyr_ctx* c);
 void temporal_free(tyr_ctx* c);
 // host/svgf.cpp: wait for the last tyr_svgf call; free its history, scratch and event (tyr_destroy)
 void svgf_free(tyr_ctx* c);
+// host/taa.cpp: wait for the last tyr_taa call; free its history and event (tyr_destroy)
+void taa_free(tyr_ctx* c);
 // host/adaptive.cpp: wait for the last tyr_allocate_samples call; free the ticket list and the scratch (tyr_destroy)
 void adaptive_free(tyr_ctx* c);
 // AoS import / export (host/staged_api.cpp): physical slots that hold a record, per segment counter array `seg` (device pointer)
