@@ -6,11 +6,17 @@
 // with TYR_SVGF_RESET / TYR_TAA_RESET on the first frame.  Every K-th frame's anti-aliased picture goes to
 // <prefix>_<frame>.ppm, and the mean milliseconds of each stage (hipEvent pairs on the ctx's stream) go to stdout.
 //
+// With --specular-guides[=K] (anywhere on the line; K = 8 bounces at most) the guides are taken behind mirrors and glass
+// (INTEGRATION.md 4k): tyr_render_aov_chain instead of tyr_render_aov; tyr_svgf gets the chain's albedo, normal and depth and
+// tyr_render_motion_chain's motion; tyr_taa, whose edges are the first surface's, gets depth_first and tyr_render_motion's.
+//
 //   denoised_flythrough [device] [frames = 32] [K = 8] [prefix = taa] [width = 640] [height = 360] [spp = 1] [parked = frames / 2]
+//                       [--specular-guides[=K]]
 #define TYRANT_IMPLEMENTATION
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -52,6 +58,21 @@ static T* dev_array(size_t count) {
 }
 
 int main(int argc, char** argv) {
+	int max_chain = -1; // -1: first-hit guides
+	for (int i = 1; i < argc; ++i) {
+		if (std::strncmp(argv[i], "--specular-guides", 17) != 0)
+			continue;
+		max_chain = argv[i][17] == '=' ? std::atoi(argv[i] + 18) : TYR_AOV_CHAIN_MAX;
+		for (int j = i; j + 1 < argc; ++j)
+			argv[j] = argv[j + 1];
+		--argc;
+		--i;
+	}
+	if (max_chain > TYR_AOV_CHAIN_MAX) {
+		std::fprintf(stderr, "--specular-guides: at most %d bounces\n", TYR_AOV_CHAIN_MAX);
+		return 2;
+	}
+	const bool chained = max_chain >= 0;
 	const int device = argc > 1 ? std::atoi(argv[1]) : 0;
 	const int frames = argc > 2 ? std::atoi(argv[2]) : 32;
 	const int every = argc > 3 ? std::atoi(argv[3]) : 8;
@@ -61,7 +82,7 @@ int main(int argc, char** argv) {
 	const unsigned spp = argc > 7 ? static_cast<unsigned>(std::atoi(argv[7])) : 1u;
 	const int parked = argc > 8 ? std::atoi(argv[8]) : frames / 2;
 	if (frames < 1 || W < 1 || H < 1 || spp < 1) {
-		std::fprintf(stderr, "usage: denoised_flythrough [device] [frames] [K] [prefix] [width] [height] [spp] [parked]\n");
+		std::fprintf(stderr, "usage: denoised_flythrough [device] [frames] [K] [prefix] [width] [height] [spp] [parked] [--specular-guides[=K]]\n");
 		return 2;
 	}
 	const size_t n = static_cast<size_t>(W) * H;
@@ -88,6 +109,12 @@ int main(int argc, char** argv) {
 	float* prev_depth = dev_array<float>(n);
 	float* filtered = dev_array<float>(4 * n); // tyr_svgf's resolved frame
 	float* screen = dev_array<float>(4 * n);   // tyr_taa's
+	// --specular-guides: sample 0's chain, and what tyr_taa keeps of the first surface
+	int32_t* chain = chained ? dev_array<int32_t>(n) : nullptr;
+	float* length0 = chained ? dev_array<float>(n) : nullptr;
+	float* depth_first = chained ? dev_array<float>(n) : nullptr;
+	float* motion_first = chained ? dev_array<float>(2 * n) : nullptr;
+	float* prev_depth_first = chained ? dev_array<float>(n) : nullptr;
 	std::vector<float> host(4 * n);
 
 	enum { AOV, MOTION, RENDER, SVGF, TAA, STAGES };
@@ -130,12 +157,24 @@ int main(int argc, char** argv) {
 
 		TYR_CHECK(hipEventRecord(ev[AOV], nullptr));
 		const tyr_aov_out aov{ albedo, normal, depth, prim, geom };
-		TYR_CHECK(tyr_render_aov(ctx, 1, &aov, nullptr));
+		if (chained) {
+			const tyr_aov_chain_out ext{ chain, nullptr, nullptr, length0, depth_first };
+			TYR_CHECK(tyr_render_aov_chain(ctx, 1, static_cast<uint32_t>(max_chain), &aov, &ext, nullptr));
+		} else {
+			TYR_CHECK(tyr_render_aov(ctx, 1, &aov, nullptr));
+		}
 		TYR_CHECK(tyr_sync(ctx)); // the events below are recorded on the null stream: keep it in step with the ctx's
 		TYR_CHECK(hipEventRecord(ev[MOTION], nullptr));
 		const tyr_motion_in min{ prim, geom, &prev_cam, nullptr };
 		const tyr_motion_out mout{ motion, prev_depth };
-		TYR_CHECK(tyr_render_motion(ctx, &min, &mout, nullptr));
+		if (chained) { // the virtual image's motion for the filter, the first surface's for the anti-aliasing
+			const tyr_motion_chain_in via{ chain, length0 };
+			const tyr_motion_out first{ motion_first, prev_depth_first };
+			TYR_CHECK(tyr_render_motion_chain(ctx, &min, &via, &mout, nullptr));
+			TYR_CHECK(tyr_render_motion(ctx, &min, &first, nullptr));
+		} else {
+			TYR_CHECK(tyr_render_motion(ctx, &min, &mout, nullptr));
+		}
 		TYR_CHECK(tyr_sync(ctx));
 		TYR_CHECK(hipEventRecord(ev[RENDER], nullptr));
 		TYR_CHECK(tyr_render(ctx, spp, UINT32_MAX, nullptr));
@@ -146,7 +185,7 @@ int main(int argc, char** argv) {
 		TYR_CHECK(tyr_svgf(ctx, &sin, &sp, filtered, nullptr, nullptr));
 		TYR_CHECK(tyr_sync(ctx));
 		TYR_CHECK(hipEventRecord(ev[TAA], nullptr));
-		const tyr_taa_in tin{ filtered, depth, motion, prev_depth };
+		const tyr_taa_in tin{ filtered, chained ? depth_first : depth, chained ? motion_first : motion, chained ? prev_depth_first : prev_depth };
 		const tyr_taa_params tp{ 0.2f, 1.5f, f == 0 ? TYR_TAA_RESET : 0u }; // the defaults (DESIGN.md "Temporal anti-aliasing")
 		TYR_CHECK(tyr_taa(ctx, &tin, &tp, screen, nullptr));
 		TYR_CHECK(tyr_sync(ctx));
@@ -175,12 +214,15 @@ int main(int argc, char** argv) {
 	tyr_counters k;
 	TYR_CHECK(tyr_get_counters(ctx, &k));
 	std::printf("%u pictures as %s_<frame>.ppm; device_error %u\n", pictures, prefix.c_str(), k.device_error);
+	if (chained)
+		std::printf("specular guides: max_chain %d\n", max_chain);
 	const int rc = k.device_error ? 1 : 0;
 	for (hipEvent_t& e : ev)
 		(void)hipEventDestroy(e);
 	TYR_CHECK(tyr_destroy(ctx));
 	for (void* p : { static_cast<void*>(albedo), static_cast<void*>(normal), static_cast<void*>(depth), static_cast<void*>(prim), static_cast<void*>(geom), static_cast<void*>(motion),
-	                 static_cast<void*>(prev_depth), static_cast<void*>(filtered), static_cast<void*>(screen) })
+	                 static_cast<void*>(prev_depth), static_cast<void*>(filtered), static_cast<void*>(screen), static_cast<void*>(chain), static_cast<void*>(length0),
+	                 static_cast<void*>(depth_first), static_cast<void*>(motion_first), static_cast<void*>(prev_depth_first) })
 		(void)hipFree(p);
 	return rc;
 }

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -549,6 +549,49 @@ typedef struct tyr_aov_out {
 } tyr_aov_out;
 int tyr_render_aov(tyr_ctx* ctx, uint32_t spp, const tyr_aov_out* out, void* stream);
 
+/* ---- Specular-chain guides: the AOV buffers taken behind mirrors and glass (extension) ------------------------------------
+ * tyr_render_aov's guides describe the first surface, which for a mirror or a pane of glass is not what the pixel shows.
+ * This pass follows each sample's deterministic specular chain to the first rough surface and takes the guides there (Schied
+ * et al. 2017, section 7).  Samples, tickets, rows, sharding, ordering, state and error reporting are tyr_render_aov's; the
+ * numeric contract is the render's: one binary32 operation per operation below in glm's order, correctly rounded division and
+ * square root, no transcendental function.
+ *   Per sample: T = (1, 1, 1), L = +0, k = 0 and the camera ray (o, d) of tyr_render_aov.  Repeat:
+ *   1. Trace (o, d) as extend traces a queue ray (intersect_scene: the spheres, then the tree, from VERY_FAR).  A miss ends the
+ *      sample: it adds albedo 0 and normal 0 and no depth.
+ *   2. Shade's surface: at = o + d * t; n = (at - position) / radius for a sphere, normalize(cross(e1, e2)) for a triangle;
+ *      outside = dot(n, d) < 0, n = outside ? n : n * -1; at' = at + n * EPSILON; the material (a sphere's; a triangle's DIFF,
+ *      or its record's with TYR_FLAG_TRIANGLE_MATERIALS by shade's range check); the colour (tyr_render_aov's albedo);
+ *      L = L + t.
+ *   3. The chain ends when the material is neither SPEC nor REFR, or when k == max_chain: the sample's albedo is T * colour,
+ *      its normal n, its depth L.
+ *   4. SPEC: T = T * colour; o = at'; d = reflect(d, n); k += 1.
+ *   5. REFR: the refracted ray whenever there is one, the reflected ray on total internal reflection; no random number is
+ *      drawn.  n1 = outside ? 1.2 : 1.0, n2 = outside ? 1.0 : 1.2 (kernel.cu:476-515); cosI = -dot(n, d); eta = n2 / n1;
+ *      sinT2 = (eta * eta) * (1 - cosI * cosI).  sinT2 > 1: o = at', d = reflect(d, n).  Otherwise o = at' - (n * 2) * EPSILON,
+ *      cosT = sqrt(1 - sinT2), d = eta * d + (eta * cosI - cosT) * n.  T is unchanged: shade multiplies no colour for REFR, and
+ *      the absorption inside the glass (shade's exp(-colour * t)) is deliberately left out of the guide.  k += 1.
+ *   Per pixel: out->albedo, normal and depth by tyr_render_aov's sums, divisions and VERY_FAR rule over these end-surface
+ *   values; out->prim and out->geom stay sample 0's FIRST hit, which is what tyr_render_motion and tyr_render_motion_chain
+ *   take.  ext (may be NULL), each pointer optional, full-frame DEVICE arrays: chain = the k sample 0 ended with; end_prim,
+ *   end_geom = the identity of the surface it ended on in the query convention (-1 / -1: it left the scene); length0 = sample
+ *   0's L there (VERY_FAR: it left the scene); depth_first = exactly tyr_render_aov's depth, for tyr_taa, whose edges are the
+ *   first surface's.
+ *   With max_chain == 0 every output shared with tyr_render_aov equals it bit for bit; chain is 0, the end ids are the first
+ *   ids and length0 is sample 0's t.
+ *   A ray refracted into a closed triangle box leaves it through culled back faces without a second refraction: the
+ *   reference's triangle test (loader.h:21-46), as in the render.
+ *   TYR_ERR_INVALID: max_chain > TYR_AOV_CHAIN_MAX; out is NULL; every pointer of out and ext is NULL; spp as tyr_render_aov.
+ *   TYR_ERR_NO_SCENE: nothing uploaded. */
+#define TYR_AOV_CHAIN_MAX 8
+typedef struct tyr_aov_chain_out {
+	int32_t* chain;        /* width * height, or NULL: sample 0's specular bounces followed (0: the first hit is the end surface) */
+	int32_t* end_prim;     /* width * height, or NULL */
+	int32_t* end_geom;     /* width * height, or NULL */
+	float*   length0;      /* width * height, or NULL */
+	float*   depth_first;  /* width * height, or NULL */
+} tyr_aov_chain_out;
+int tyr_render_aov_chain(tyr_ctx* ctx, uint32_t spp, uint32_t max_chain, const tyr_aov_out* out, const tyr_aov_chain_out* ext, void* stream);
+
 /* ---- Denoiser: edge-avoiding a-trous filter guided by the AOV buffers (extension) -----------------------------------------
  * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of the illumination -- the colour with the albedo divided
  * out -- steered by the tyr_render_aov guides.  Numeric contract as the render's: one binary32 operation per operation below,
@@ -631,6 +674,25 @@ typedef struct tyr_motion_out {
 	float* prev_depth;  /* width * height, or NULL */
 } tyr_motion_out;
 int tyr_render_motion(tyr_ctx* ctx, const tyr_motion_in* in, const tyr_motion_out* out, void* stream);
+
+/* tyr_render_motion for guides that tyr_render_aov_chain took: where what a pixel shows THROUGH its specular chain was in the
+ * previous frame (the "virtual motion" of reflections).  via->chain and via->length0 are tyr_render_aov_chain's outputs at
+ * this camera and frame; in->prim / geom its first-hit ids.
+ *   chain == 0: exactly tyr_render_motion's result for the pixel, bit for bit.
+ *   chain > 0 and length0 < VERY_FAR: the virtual image point X = X' = o + d * length0 with (o, d) sample 0's camera ray -- the
+ *   point on the primary ray at the summed path length -- goes through both cameras by the projection above, and
+ *   prev_depth = length(X - O_prev), which is what the previous frame's chain depth reads there.
+ *   chain > 0 and length0 == VERY_FAR (the chain left the scene): motion (0, 0), prev_depth VERY_FAR.
+ *   The "no point" rules above hold too: f <= 0 for either camera or a non-finite result give (0, 0) and VERY_FAR.
+ *   Limits: the virtual point is exact for a planar mirror over static geometry seen by a pinhole camera; for curved mirrors
+ *   and for refraction it is an approximation; in->prev_prims is ignored for what is seen through a chain (geometry that moves
+ *   behind a mirror is not followed).
+ *   TYR_ERR_INVALID: as tyr_render_motion, or via, via->chain or via->length0 NULL. */
+typedef struct tyr_motion_chain_in {
+	const int32_t* chain;   /* width * height */
+	const float* length0;   /* width * height */
+} tyr_motion_chain_in;
+int tyr_render_motion_chain(tyr_ctx* ctx, const tyr_motion_in* in, const tyr_motion_chain_in* via, const tyr_motion_out* out, void* stream);
 
 /* ---- Temporal reprojection: a running mean of frames over a reprojected history (extension) --------------------------------
  * The first stage of SVGF (Schied et al. 2017): each valid pixel blends its current illumination into the ctx's history,

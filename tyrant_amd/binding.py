@@ -29,6 +29,7 @@ TYR_ERR_NO_SCENE = -3
 TYR_ERR_DEVICE = -6
 TYR_ERR_UNSUPPORTED = -7
 TYR_QUERY_SPHERES = 1
+AOV_CHAIN_MAX = 8  # TYR_AOV_CHAIN_MAX
 TYR_REFIT_DEVICE = 1
 TYR_DENOISE_RESOLVE = 1
 # tyr_denoise's defaults (host/denoise.cpp)
@@ -121,6 +122,12 @@ class AovOut(C.Structure):
     _fields_ = [("albedo", P), ("normal", P), ("depth", P), ("prim", P), ("geom", P)]
 
 
+class AovChainOut(C.Structure):
+    """tyr_aov_chain_out: device pointers of what tyr_render_aov_chain adds, NULL to skip one"""
+
+    _fields_ = [("chain", P), ("end_prim", P), ("end_geom", P), ("length0", P), ("depth_first", P)]
+
+
 class DenoiseIn(C.Structure):
     """tyr_denoise_in: device pointers of the frame (NULL: the ctx's blit buffer) and its guides"""
 
@@ -139,6 +146,12 @@ class MotionIn(C.Structure):
 
 class MotionOut(C.Structure):
     _fields_ = [("motion", P), ("prev_depth", P)]
+
+
+class MotionChainIn(C.Structure):
+    """tyr_motion_chain_in: render_aov(max_chain=...)'s chain and length0 (device)"""
+
+    _fields_ = [("chain", P), ("length0", P)]
 
 
 class TemporalIn(C.Structure):
@@ -250,8 +263,10 @@ SYMBOLS = {
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
+    "tyr_render_aov_chain": (C.c_int, [P, c_u32, c_u32, P, P, P]),
     "tyr_denoise": (C.c_int, [P, P, P, P, P]),
     "tyr_render_motion": (C.c_int, [P, P, P, P]),
+    "tyr_render_motion_chain": (C.c_int, [P, P, P, P, P]),
     "tyr_temporal": (C.c_int, [P, P, P, P, P, P]),
     "tyr_svgf": (C.c_int, [P, P, P, P, P, P]),
     "tyr_set_sample_map": (C.c_int, [P, P, P, C.POINTER(c_u64)]),
@@ -664,12 +679,16 @@ class Renderer:
         self._query_finish()
         return occ
 
-    def render_aov(self, spp, albedo=True, normal=True, depth=True, ids=True, stream=None) -> dict:
+    def render_aov(self, spp, albedo=True, normal=True, depth=True, ids=True, stream=None, max_chain=None) -> dict:
         """tyr_render_aov: first-hit guide buffers of the current camera at the current frame counter, spp camera rays per pixel
         (the rays of a render's first wavefront from an empty queue).  Returns a dict of torch tensors on this ctx's device:
         "albedo", "normal" (H, W, 3) float32, "depth" (H, W) float32 (VERY_FAR where no sample hit), "prim", "geom" (H, W) int32
         (sample 0's identity: geom 0 sphere, 1 triangle, -1 miss) -- those asked for.  Runs on `stream` (default: torch's current
-        stream) and returns once it is done.  A sharded ctx fills its own rows; the others are zero."""
+        stream) and returns once it is done.  A sharded ctx fills its own rows; the others are zero.
+        max_chain (0 .. AOV_CHAIN_MAX; None: the call above) takes tyr_render_aov_chain instead: albedo, normal and depth are
+        those of the surface each sample's specular chain ends on, after at most max_chain mirror / glass bounces; prim, geom
+        stay the first hit; and the dict gains "chain", "end_prim", "end_geom" (H, W) int32, "length0" and "depth_first" (H, W)
+        float32 (include/tyr_c.h "Specular-chain guides")."""
         import torch
 
         dev = torch.device("cuda", self.device)
@@ -684,7 +703,15 @@ class Renderer:
             res["prim"] = torch.zeros((self.H, self.W), dtype=torch.int32, device=dev)
             res["geom"] = torch.zeros((self.H, self.W), dtype=torch.int32, device=dev)
         out = AovOut(*(res[k].data_ptr() if k in res else None for k in ("albedo", "normal", "depth", "prim", "geom")))
-        self._on_stream(stream, lambda h: self.L.tyr_render_aov(self.h, spp, C.byref(out), h), True)
+        if max_chain is None:
+            self._on_stream(stream, lambda h: self.L.tyr_render_aov(self.h, spp, C.byref(out), h), True)
+        else:
+            for k in ("chain", "end_prim", "end_geom"):
+                res[k] = torch.zeros((self.H, self.W), dtype=torch.int32, device=dev)
+            for k in ("length0", "depth_first"):
+                res[k] = torch.zeros((self.H, self.W), dtype=torch.float32, device=dev)
+            ext = AovChainOut(*(res[k].data_ptr() for k in ("chain", "end_prim", "end_geom", "length0", "depth_first")))
+            self._on_stream(stream, lambda h: self.L.tyr_render_aov_chain(self.h, spp, max_chain, C.byref(out), C.byref(ext), h), True)
         self._query_finish()
         return res
 
@@ -722,18 +749,23 @@ class Renderer:
                 raise ValueError(f"{what}: a contiguous {dtype} tensor of {size} values on {dev}")
         return dev
 
-    def render_motion(self, prim, geom, prev_camera, prev_prims=None, stream=None) -> dict:
+    def render_motion(self, prim, geom, prev_camera, prev_prims=None, stream=None, chain=None, length0=None) -> dict:
         """tyr_render_motion: per pixel the motion to the previous frame and the depth expected there, from render_aov's sample-0
         ids (prim, geom: (H, W) int32 tensors on this ctx's device) at the current camera and frame.  prev_camera: the previous
         frame's camera (fields as set_camera takes them).  prev_prims: None (the geometry did not move), or the records held
         before the last refit in the uploaded order -- a contiguous tensor of 40-byte records on this device, or a TRIANGLE_DTYPE
         numpy array (copied over on the current stream).  Returns a dict of torch tensors: "motion" (H, W, 2), "prev_depth"
         (H, W).  Runs on `stream` (default: torch's current stream) and returns once it is enqueued.  A sharded ctx fills its own
-        rows; the others are zero."""
+        rows; the others are zero.  chain, length0 (both or neither; (H, W) int32 / float32 from render_aov(max_chain=...)):
+        tyr_render_motion_chain -- where a pixel's chain has bounces, the motion of the virtual image point seen through them."""
         import torch
 
         n = self.H * self.W
         dev = self._frame_tensors({"prim": (prim, torch.int32, n), "geom": (geom, torch.int32, n)})
+        if (chain is None) != (length0 is None):
+            raise ValueError("chain and length0 go together")
+        if chain is not None:
+            self._frame_tensors({"chain": (chain, torch.int32, n), "length0": (length0, torch.float32, n)})
         f3 = lambda x: (c_f * 3)(*[float(v) for v in x])  # noqa: E731
         cam = CameraC(f3(prev_camera.position), f3(prev_camera.direction), f3(prev_camera.up), prev_camera.focalDistance, prev_camera.lensRadius)
         pp = None
@@ -747,12 +779,18 @@ class Renderer:
         res = {"motion": torch.zeros((self.H, self.W, 2), dtype=torch.float32, device=dev), "prev_depth": torch.zeros((self.H, self.W), dtype=torch.float32, device=dev)}
         mi = MotionIn(prim.data_ptr(), geom.data_ptr(), C.cast(C.pointer(cam), P), pp)
         mo = MotionOut(res["motion"].data_ptr(), res["prev_depth"].data_ptr())
-        self._on_stream(stream, lambda h: self.L.tyr_render_motion(self.h, C.byref(mi), C.byref(mo), h), True)
+        if chain is None:
+            self._on_stream(stream, lambda h: self.L.tyr_render_motion(self.h, C.byref(mi), C.byref(mo), h), True)
+        else:
+            via = MotionChainIn(chain.data_ptr(), length0.data_ptr())
+            self._on_stream(stream, lambda h: self.L.tyr_render_motion_chain(self.h, C.byref(mi), C.byref(via), C.byref(mo), h), True)
         if stream is not None:
             for t in res.values():
                 t.record_stream(stream)
             if pp is not None:
                 prev_prims.record_stream(stream)
+            if chain is not None:
+                chain.record_stream(stream), length0.record_stream(stream)
         return res
 
     def temporal(self, albedo, normal, depth, motion, prev_depth, accum=None, max_history=TEMPORAL_MAX_HISTORY, depth_tolerance=TEMPORAL_DEPTH_TOLERANCE,

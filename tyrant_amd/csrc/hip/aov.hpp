@@ -29,6 +29,19 @@ struct AovParams {
 	uint32_t spp;          // spp * nPixels < 2^32
 };
 
+// by-value kernel argument of the specular-chain pass (tyr_render_aov_chain): the first-hit pass's, and what the chain adds
+struct AovChainParams {
+	AovParams a;           // albedo, normal, depth: of the surface the chain ends on; prim, geom: sample 0's first hit
+	int32_t* chain;        // full-frame outputs of sample 0, each optional: specular bounces followed
+	int32_t* endPrim;      // identity of the surface it ended on (-1 / -1: it left the scene)
+	int32_t* endGeom;
+	float* length0;        // its summed path length (VERY_FAR: it left the scene)
+	float* depthFirst;     // the first-hit pass's depth
+	uint32_t maxChain;     // 0 .. TYR_AOV_CHAIN_MAX
+	uint32_t triMaterials; // TYR_FLAG_TRIANGLE_MATERIALS: a triangle's material is its record's, else DIFF
+};
+
 void launch_aov(const AovParams& P, int numCUs, LaunchCache& lc, hipStream_t stream);
+void launch_aov_chain(const AovChainParams& P, int numCUs, LaunchCache& lc, hipStream_t stream);
 
 } // namespace tyr

@@ -4,7 +4,8 @@
 // k_render_motion regenerates each local pixel's sample-0 camera ray (camera_seed / camera_focus / camera_lens, as
 // k_primary and the AOV pass make it), finds its hit point from tyr_render_aov's ids alone -- one triangle_test_uv or
 // one sphere_intersect, no traversal -- moves it to the previous frame's triangle record by its barycentrics, and projects
-// both points through their camera's pinhole.
+// both points through their camera's pinhole.  k_motion_chain (tyr_render_motion_chain) does the same, except where
+// tyr_render_aov_chain followed a specular chain: there it projects the virtual image point.
 //
 // k_temporal blends a frame's illumination into a bilinearly reprojected history that the ctx keeps ping-ponged: it reads
 // history[j] and writes history[j ^ 1].  Every lane owns one pixel and sums its four taps in registers in the specified
@@ -34,7 +35,10 @@ __device__ __forceinline__ bool project(f3 X, f3 O, f3 F, f3 R, f3 U, float FF, 
 
 } // namespace
 
-__global__ void __launch_bounds__(kBlock) k_render_motion(const MotionParams P) {
+// one pixel of the motion pass.  CHAIN (tyr_render_motion_chain): where the pixel's specular chain has bounces, the point is the
+// virtual image point on the camera ray at the chain's summed length, the same in both frames
+template <bool CHAIN>
+__device__ __forceinline__ void motion_pixel(const MotionParams& P, const int32_t* __restrict__ chain, const float* __restrict__ length0) {
 	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
 	const uint32_t x = blockIdx.x * kTile + (wave & 1u) * 8u + (lane & 7u);
 	const uint32_t yl = blockIdx.y * kTile + (wave >> 1) * 8u + (lane >> 3);
@@ -46,13 +50,23 @@ __global__ void __launch_bounds__(kBlock) k_render_motion(const MotionParams P) 
 	float mx = 0.f, my = 0.f, pd = kVeryFar;
 	const bool tri = geom == 1 && prim >= 0 && static_cast<uint32_t>(prim) < P.nPrims;
 	const bool sph = geom == 0 && prim >= 0 && prim < TYR_NUM_SPHERES;
-	if (tri || sph) {
+	bool through = false;
+	float reach = 0.f;
+	if (CHAIN) {
+		through = chain[i] > 0;
+		reach = length0[i];
+	}
+	if (through ? reach < kVeryFar : (tri || sph)) {
 		// sample 0's camera ray: ticket 0 * nPixels + p (hip/aov.hip)
 		uint32_t seed = camera_seed(P, yl * P.W + x);
 		const CameraRay cr = camera_lens(P, seed, camera_focus(P, seed, static_cast<int>(x), static_cast<int>(y)), ld3(P.camPos), ld3(P.camRight), ld3(P.camUp));
 		f3 X = mk3(0.f, 0.f, 0.f), Xp = X;
 		bool hit = false;
-		if (tri) {
+		if (through) {
+			hit = true;
+			X = cr.origin + cr.direction * reach;
+			Xp = X;
+		} else if (tri) {
 			const TriData td = triangle_load(P.tris, static_cast<uint32_t>(prim));
 			float u = 0.f, v = 0.f;
 			hit = triangle_test_uv(td, make_ray(cr.origin, cr.direction), u, v) != 0.f;
@@ -87,6 +101,10 @@ __global__ void __launch_bounds__(kBlock) k_render_motion(const MotionParams P) 
 	if (P.prevDepth)
 		P.prevDepth[i] = pd;
 }
+
+__global__ void __launch_bounds__(kBlock) k_render_motion(const MotionParams P) { motion_pixel<false>(P, nullptr, nullptr); }
+
+__global__ void __launch_bounds__(kBlock) k_motion_chain(const MotionParams P, const int32_t* __restrict__ chain, const float* __restrict__ length0) { motion_pixel<true>(P, chain, length0); }
 
 __global__ void __launch_bounds__(kBlock) k_temporal(const TemporalParams P) {
 	const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
@@ -173,6 +191,10 @@ __global__ void __launch_bounds__(kBlock) k_temporal(const TemporalParams P) {
 
 void launch_motion(const MotionParams& P, hipStream_t stream) {
 	hipLaunchKernelGGL(k_render_motion, dim3((P.W + kTile - 1) / kTile, (P.localRows + kTile - 1) / kTile), dim3(kBlock), 0, stream, P);
+}
+
+void launch_motion_chain(const MotionParams& P, const int32_t* chain, const float* length0, hipStream_t stream) {
+	hipLaunchKernelGGL(k_motion_chain, dim3((P.W + kTile - 1) / kTile, (P.localRows + kTile - 1) / kTile), dim3(kBlock), 0, stream, P, chain, length0);
 }
 
 void launch_temporal(const TemporalParams& P, hipStream_t stream) {

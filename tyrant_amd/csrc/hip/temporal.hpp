@@ -48,6 +48,7 @@ struct TemporalParams {
 };
 
 void launch_motion(const MotionParams& P, hipStream_t stream);
+void launch_motion_chain(const MotionParams& P, const int32_t* chain, const float* length0, hipStream_t stream); // full-frame, as prim / geom
 void launch_temporal(const TemporalParams& P, hipStream_t stream);
 
 } // namespace tyr

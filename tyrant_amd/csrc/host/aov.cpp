@@ -1,5 +1,6 @@
-// aov.cpp -- tyr_render_aov: first-hit guide buffers (albedo, normal, depth, ids) of the ctx's current camera and frame
-// (include/tyr_c.h "AOV buffers"; the kernel is hip/aov.hip).  The pass behaves like a query (host/query.cpp): it runs on the
+// aov.cpp -- tyr_render_aov: first-hit guide buffers (albedo, normal, depth, ids) of the ctx's current camera and frame, and
+// tyr_render_aov_chain: the same guides taken behind mirrors and glass (include/tyr_c.h "AOV buffers" and "Specular-chain
+// guides"; the kernels are hip/aov.hip).  Each pass behaves like a query (host/query.cpp): it runs on the
 // caller's stream with a ticket word of that stream, its stack overflow bit goes to tyr_query_error, and a later refit or
 // scene change waits for it.  No render state is read back or written: the camera basis is computed here, not stored.
 #include <algorithm>
@@ -13,24 +14,23 @@
 using namespace tyr;
 using namespace tyr::drv;
 
-int tyr_render_aov(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, void* stream) {
-	if (!c || !out || spp == 0 || (!out->albedo && !out->normal && !out->depth && !out->prim && !out->geom))
+namespace {
+
+// the checks, the stream's ticket and the kernel argument both passes share; `any`: the caller asked for some output
+int aov_setup(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, bool any, void* stream, DeviceScope& scope, hipStream_t& s, tyr_ctx::QueryStream*& qs, AovParams& P) {
+	if (!c || !out || spp == 0 || !any)
 		return TYR_ERR_INVALID;
 	if (static_cast<uint64_t>(spp) * c->localPixels >= (1ull << 32)) // the tickets s * P + p are 32-bit, as k_primary's
 		return TYR_ERR_INVALID;
 	if (!c->haveScene)
 		return TYR_ERR_NO_SCENE;
-	DeviceScope scope;
 	HIPCHK(hipGetDevice(&scope.prev));
 	if (int rc = use_device(c))
 		return rc;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
 	uint32_t* ticket = nullptr;
 	if (int rc = query_ticket(c, stream, s, qs, ticket))
 		return rc;
 
-	AovParams P{};
 	P.scene = c->scene;
 	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0))); // as the render's launches stage them
 	std::memcpy(P.spheres, c->spheres, sizeof(P.spheres));
@@ -55,7 +55,45 @@ int tyr_render_aov(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, void* strea
 	P.error = c->dQuery;
 	P.nPixels = c->localPixels;
 	P.spp = spp;
+	return TYR_OK;
+}
+
+} // namespace
+
+int tyr_render_aov(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, void* stream) {
+	DeviceScope scope;
+	hipStream_t s = nullptr;
+	tyr_ctx::QueryStream* qs = nullptr;
+	AovParams P{};
+	const bool any = out && (out->albedo || out->normal || out->depth || out->prim || out->geom);
+	if (int rc = aov_setup(c, spp, out, any, stream, scope, s, qs, P))
+		return rc;
 	launch_aov(P, c->numCUs, c->launchCache, s);
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(qs->done, s));
+	return TYR_OK;
+}
+
+int tyr_render_aov_chain(tyr_ctx* c, uint32_t spp, uint32_t max_chain, const tyr_aov_out* out, const tyr_aov_chain_out* ext, void* stream) {
+	if (max_chain > TYR_AOV_CHAIN_MAX)
+		return TYR_ERR_INVALID;
+	DeviceScope scope;
+	hipStream_t s = nullptr;
+	tyr_ctx::QueryStream* qs = nullptr;
+	AovChainParams P{};
+	const bool any = out && (out->albedo || out->normal || out->depth || out->prim || out->geom || (ext && (ext->chain || ext->end_prim || ext->end_geom || ext->length0 || ext->depth_first)));
+	if (int rc = aov_setup(c, spp, out, any, stream, scope, s, qs, P.a))
+		return rc;
+	if (ext) {
+		P.chain = ext->chain;
+		P.endPrim = ext->end_prim;
+		P.endGeom = ext->end_geom;
+		P.length0 = ext->length0;
+		P.depthFirst = ext->depth_first;
+	}
+	P.maxChain = max_chain;
+	P.triMaterials = (c->cfg.flags & TYR_FLAG_TRIANGLE_MATERIALS) ? 1u : 0u;
+	launch_aov_chain(P, c->numCUs, c->launchCache, s);
 	HIPCHK(hipGetLastError());
 	HIPCHK(hipEventRecord(qs->done, s));
 	return TYR_OK;

@@ -1,4 +1,4 @@
-// temporal.cpp -- tyr_render_motion: motion vectors and the expected previous depth of the ctx's current AOV frame; and
+// temporal.cpp -- tyr_render_motion / tyr_render_motion_chain: motion vectors and the expected previous depth of the ctx's current AOV frame; and
 // tyr_temporal: the reprojected accumulation of frames with a history the ctx owns (include/tyr_c.h "Motion vectors" and
 // "Temporal reprojection"; the kernels are hip/temporal.hip).
 // The motion pass behaves like a query (host/aov.cpp): it reads the uploaded triangles on the caller's stream, and a later
@@ -52,7 +52,10 @@ void temporal_free(tyr_ctx* c) {
 } // namespace drv
 } // namespace tyr
 
-int tyr_render_motion(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_out* out, void* stream) {
+namespace {
+
+// both motion passes; via: tyr_render_motion_chain's chain inputs, or null
+int render_motion(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_chain_in* via, const tyr_motion_out* out, void* stream) {
 	if (!c || !in || !out || !in->prim || !in->geom || !in->prev_camera || (!out->motion && !out->prev_depth))
 		return TYR_ERR_INVALID;
 	if (!c->haveScene)
@@ -87,11 +90,24 @@ int tyr_render_motion(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_out*
 	P.motion = out->motion;
 	P.prevDepth = out->prev_depth;
 	if (c->localPixels != 0) {
-		launch_motion(P, s);
+		if (via)
+			launch_motion_chain(P, via->chain, via->length0, s);
+		else
+			launch_motion(P, s);
 		HIPCHK(hipGetLastError());
 	}
 	HIPCHK(hipEventRecord(qs->done, s));
 	return TYR_OK;
+}
+
+} // namespace
+
+int tyr_render_motion(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_out* out, void* stream) { return render_motion(c, in, nullptr, out, stream); }
+
+int tyr_render_motion_chain(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_chain_in* via, const tyr_motion_out* out, void* stream) {
+	if (!via || !via->chain || !via->length0)
+		return TYR_ERR_INVALID;
+	return render_motion(c, in, via, out, stream);
 }
 
 int tyr_temporal(tyr_ctx* c, const tyr_temporal_in* in, const tyr_temporal_params* params, void* device_rgba_out, float* history_len_out, void* stream) {
