@@ -8,14 +8,13 @@ export; C3's tree at full size against tyr_query_closest on the oracle's camera 
 argument checks, partial outputs and streams; the example's PFM guides."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT, bits, built_scene
+from kernel_resources import kernel_resources
 
 CSRC = os.path.join(ROOT, "tyrant_amd", "csrc")
 LDS_PER_CU, LDS_GRANULE = 163840, 1280
@@ -27,20 +26,7 @@ SENTINEL = -7.25
 def test_aov_kernel_keeps_registers_and_lds_in_budget():
     """no vector spills; scratch no larger than the LdsStack's private spill arrays; LDS and registers that admit the five
     blocks per CU its __launch_bounds__ plans for (as k_query_closest)"""
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.fail("no hipcc: the kernels cannot be built")
-    subprocess.run(["make", "-s", "-C", CSRC, "asm"], check=True, capture_output=True, timeout=900)
-    res, cur = {}, None
-    for line in open(os.path.join(CSRC, "build", "aov.resources.txt")):
-        m = re.search(r"remark:\s+(.*?)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        text = m.group(1)
-        if text.startswith("Function Name:"):
-            cur = res.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.rsplit(":", 1)
-            cur[k.strip()] = int(v) if v.strip().lstrip("-").isdigit() else v.strip()
+    res = kernel_resources("aov")
     names = [n for n in res if "k_render_aov" in n]
     assert len(names) == 1, list(res)
     k = res[names[0]]

@@ -7,8 +7,6 @@ GPU: bit-exact against the restatement on seeded and rendered inputs; the resolv
 converged render; isolation from the render state; arguments, streams, sharding and the example's denoised image."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
@@ -16,6 +14,7 @@ import pytest
 
 import denoise_ref as ref
 from conftest import ROOT, bits, built_scene
+from kernel_resources import kernel_resources
 
 CSRC = os.path.join(ROOT, "tyrant_amd", "csrc")
 VERY_FAR = ref.VERY_FAR
@@ -25,24 +24,6 @@ QUALITY_BOUND = 0.06
 
 
 # ---- CPU: resources of the denoise kernels -----------------------------------------------------------------------------
-def kernel_resources(unit):
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.fail("no hipcc: the kernels cannot be built")
-    subprocess.run(["make", "-s", "-C", CSRC, "asm"], check=True, capture_output=True, timeout=900)
-    res, cur = {}, None
-    for line in open(os.path.join(CSRC, "build", f"{unit}.resources.txt")):
-        m = re.search(r"remark:\s+(.*?)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        text = m.group(1)
-        if text.startswith("Function Name:"):
-            cur = res.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.rsplit(":", 1)
-            cur[k.strip()] = int(v) if v.strip().lstrip("-").isdigit() else v.strip()
-    return res
-
-
 def test_denoise_kernels_keep_registers_in_budget():
     """the prepare kernel and the three pass kernels (inner, last linear, last resolve): no spills, no scratch, no LDS, and
     the eight waves per SIMD that __launch_bounds__(256) without a block minimum leaves room for"""

@@ -6,50 +6,30 @@ because a by-value kernel argument is loaded in the kernel's first block and kep
 (device_common.hpp kernarg_view) brought that to no spill at all and five blocks per CU, worth 15 % of the kernel.  A change
 that quietly brings the spills back, or one LDS granule too many (the CU then places four blocks where the occupancy query
 still answers five), costs that again without failing any parity test: this file is the guard."""
-import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tyrant_amd", "csrc")
+from kernel_resources import have_hipcc, make_asm, parse_resources
+
 LDS_PER_CU = 163840  # MI355X: 160 KB per CU ...
 LDS_GRANULE = 1280   # ... handed out in 1280-byte granules (hip/traverse_flat.hip k_trace_flat: 31,748 B x 5 fit, 32,004 B x 5 do not)
 
 
-def _resources(unit):
-    out = {}
-    cur = None
-    for line in open(os.path.join(CSRC, "build", unit + ".resources.txt")):
-        m = re.search(r"remark:\s+(.*?)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        text = m.group(1)
-        if text.startswith("Function Name:"):
-            cur = out.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
-    return out
-
-
 @pytest.fixture(scope="module")
 def resources():
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
+    if not have_hipcc():
         pytest.skip("no hipcc")
-    subprocess.run(["make", "-s", "-C", CSRC, "asm"], check=True, capture_output=True, timeout=900)
+    make_asm()
     r = {}
     for unit in ("frame", "shade", "traverse_flat"):
-        r.update(_resources(unit))
+        r.update(parse_resources(unit))
     return r
 
 
 def _kernel(resources, key):
     names = [n for n in resources if key in n]
     assert len(names) == 1, (key, names)
-    return {k: (int(v) if v.lstrip("-").isdigit() else v) for k, v in resources[names[0]].items()}
+    return resources[names[0]]
 
 
 def _blocks_that_fit(lds_bytes):

@@ -7,42 +7,21 @@ against the reference harness (or the oracle the CPU tests pin to it), the spher
 hostile rays and batch sizes, barycentrics, isolation from the render state, streams and argument checks."""
 import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT, bits, built_scene
+from kernel_resources import kernel_resources
 
-CSRC = os.path.join(ROOT, "tyrant_amd", "csrc")
 LDS_PER_CU, LDS_GRANULE = 163840, 1280
 
 
 # ---- CPU: resources of the query kernels ------------------------------------------------------------------------------
-def _query_resources():
-    out, cur = {}, None
-    for line in open(os.path.join(CSRC, "build", "query.resources.txt")):
-        m = re.search(r"remark:\s+(.*?)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        text = m.group(1)
-        if text.startswith("Function Name:"):
-            cur = out.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.rsplit(":", 1)
-            cur[k.strip()] = int(v) if v.strip().lstrip("-").isdigit() else v.strip()
-    return out
-
-
 def test_query_kernels_keep_registers_and_lds_in_budget():
     """no vector spills; scratch no larger than the LdsStack's private spill arrays (52 entries of 8 / 4 bytes, plus the
     frame's alignment); LDS that admits the five (closest) / seven (any) blocks per CU that the occupancy query plans for"""
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.fail("no hipcc: the kernels cannot be built")
-    subprocess.run(["make", "-s", "-C", CSRC, "asm"], check=True, capture_output=True, timeout=900)
-    res = _query_resources()
+    res = kernel_resources("query")
     spill_entries = 64 - 12
     for kind, with_t, blocks in (("k_query_closest", True, 5), ("k_query_any", False, 7)):
         for sph in (0, 1):

@@ -23,6 +23,7 @@ import specular_ref as sr
 import test_aov
 import test_temporal
 from conftest import ROOT, bits, built_scene
+from kernel_resources import kernel_resources
 
 CSRC = os.path.join(ROOT, "tyrant_amd", "csrc")
 BENCH = os.path.join(ROOT, "profiles", "specular_guides_bench.json")
@@ -193,10 +194,10 @@ def test_the_test_scenes_cover_every_branch(orc):
 
 
 def test_chain_kernel_keeps_registers_and_lds_in_budget():
-    """k_render_chain as the build reports it: 103 VGPRs, which is four waves per SIMD (k_render_aov: 76 and five); no vector
+    """k_render_chain as the build reports it: 103 VGPRs, which is four waves per SIMD (k_render_aov: 75 and five); no vector
     spill; scratch no larger than the LdsStack's private spill arrays (k_render_aov's 432 bytes); LDS that admits five blocks per
-    CU.  k_render_aov itself is unchanged: test_aov's own test still holds its five."""
-    res = test_temporal.kernel_resources("aov")
+    CU.  k_render_aov is the same body without the chain (aov_body<false>): test_aov's own test holds its five."""
+    res = kernel_resources("aov")
     names = [n for n in res if "k_render_chain" in n]
     assert len(names) == 1, list(res)
     k = res[names[0]]
@@ -205,7 +206,7 @@ def test_chain_kernel_keeps_registers_and_lds_in_budget():
     assert k["VGPRs"] <= 104 and k["Occupancy [waves/SIMD]"] >= 4, k
     per_block = -(-k["LDS Size [bytes/block]"] // test_aov.LDS_GRANULE) * test_aov.LDS_GRANULE
     assert test_aov.LDS_PER_CU // per_block >= 5, k
-    m = test_temporal.kernel_resources("temporal")
+    m = kernel_resources("temporal")
     names = [n for n in m if "k_motion_chain" in n]
     assert len(names) == 1, list(m)
     k = m[names[0]]

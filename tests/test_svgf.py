@@ -12,9 +12,6 @@ import ctypes as C
 import dataclasses
 import json
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,8 +20,8 @@ import denoise_ref
 import svgf_ref as ref
 import test_temporal
 from conftest import ROOT, bits, built_scene
+from kernel_resources import kernel_resources
 
-CSRC = os.path.join(ROOT, "tyrant_amd", "csrc")
 VERY_FAR = ref.VERY_FAR
 F = np.float32
 # test_svgf_quality_on_a_panning_cornell_sequence: SVGF's MSE over temporal -> denoise's, both with their defaults, against a
@@ -149,24 +146,6 @@ def test_restatement_feeds_back_the_first_pass():
 
 
 # ---- CPU: resources of the kernels -------------------------------------------------------------------------------------
-def kernel_resources(unit):
-    if shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"):
-        pytest.fail("no hipcc: the kernels cannot be built")
-    subprocess.run(["make", "-s", "-C", CSRC, "asm"], check=True, capture_output=True, timeout=900)
-    res, cur = {}, None
-    for line in open(os.path.join(CSRC, "build", f"{unit}.resources.txt")):
-        m = re.search(r"remark:\s+(.*?)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        text = m.group(1)
-        if text.startswith("Function Name:"):
-            cur = res.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.rsplit(":", 1)
-            cur[k.strip()] = int(v) if v.strip().lstrip("-").isdigit() else v.strip()
-    return res
-
-
 def test_svgf_kernels_keep_registers_in_budget():
     """k_svgf_reproject, k_svgf_variance and the three pass kernels: no spills, no scratch, no LDS, eight waves per SIMD"""
     res = kernel_resources("svgf")

@@ -7,11 +7,13 @@
 //                (kernel.cu:163-174): the tree, then the spheres with (d + epsilon) < tmax.  A boolean: the order of the two
 //                halves does not change it, so the spheres are tested first and a blocked ray never enters the tree.
 //
-// The production traversal's pieces (hip/traverse.hpp), not its loop: quad nodes through test_quad, the first nStaged quad
-// nodes in LDS, the LdsStack with its private spill arrays, triangle_test on the leaves.  A wave is a flat per-lane state
-// machine (interior ref | leaf ref | kRefPop | kRefDone) as in k_trace_flat: one pop attempt and one quad test per lane per
-// trip, refilled from a private range of ray indices that it draws from one device-wide ticket word, `chunk` rays at a time.
-// Rays are contiguous inside a chunk, so a caller's coherent rays (a camera's) stay together in a wave.
+// The loop is hip/query_common.hpp's, shared with the guide passes (hip/aov.hip): the production traversal's pieces
+// (hip/traverse.hpp), not its loop -- quad nodes through test_quad, the first nStaged quad nodes in LDS, the LdsStack with its
+// private spill arrays, triangle_test on the leaves.  A wave is a flat per-lane state machine (interior ref | leaf ref |
+// kRefPop | kRefDone) as in k_trace_flat: one pop attempt and one quad test per lane per trip, refilled from a private range of
+// ray indices that it draws from one device-wide ticket word, `chunk` rays at a time.  Rays are contiguous inside a chunk, so
+// a caller's coherent rays (a camera's) stay together in a wave.  This file is what a query adds: the load of a caller's ray
+// and its validity test, the any-hit sphere test, and the answer's way into the caller's arrays.
 #include "device_common.hpp"
 #include "query.hpp"
 #include "query_common.hpp"
@@ -46,172 +48,85 @@ __device__ __forceinline__ void query_body(const QueryParams& P0) {
 	TYR_DECLARE_FLAT_STACK(st, !ANY)
 	__shared__ float4 stagedNodes[7 * kStagedNodes];
 	const DevScene& sc = P0.scene;
-	const uint32_t nStaged = sc.nStaged;
-	for (uint32_t i = threadIdx.x; i < 7 * nStaged; i += kBlock) {
-		const uint32_t v = i / nStaged, k = i - v * nStaged;
-		stagedNodes[v * kStagedNodes + k] = sc.quads[8 * k + v];
-	}
-	__syncthreads();
+	q_stage_nodes(stagedNodes, sc);
 	const uint32_t lane = lane_id();
-	const unsigned long long below = (1ull << lane) - 1ull;
-	const uint32_t n = P0.n;
 
-	float rox = 0.f, roy = 0.f, roz = 0.f, rdx = 0.f, rdy = 0.f, rdz = 0.f, rix = 0.f, riy = 0.f, riz = 0.f;
-	bool regular = true;
-	float dist = 0.f, tmax = 0.f;
-	uint32_t ref = kRefDone, ray = 0;
-	int prim = -1, sphere = -1;
-	bool hitTri = false, occluded = false, live = false, overflow = false;
+	QueryRay q = {};
+	q.ref = kRefDone;
+	float tmax = 0.f;
+	uint32_t ray = 0;
+	bool live = false, overflow = false;
 
 	// a finished ray's answer, into the caller's arrays at its index (64-bit offsets: 3 n floats pass 2^32 bytes)
 	auto finish = [&]() {
 		const QueryParams& P = kernarg_view<QueryParams>(); // (read where it lies: not held in scalar registers through the descent)
 		const size_t i = ray;
 		if (ANY) {
-			P.occluded[i] = occluded ? 1 : 0;
+			P.occluded[i] = q.occluded ? 1 : 0;
 		} else {
-			const bool hit = hitTri || sphere >= 0;
-			P.t[i] = dist;
-			P.prim[i] = hitTri ? prim : (hit ? sphere : -1);
+			const bool hit = q.hitTri || q.sphere >= 0;
+			P.t[i] = q.dist;
+			P.prim[i] = q.hitTri ? q.prim : (hit ? q.sphere : -1);
 			if (P.geom)
-				P.geom[i] = hitTri ? 1 : (hit ? 0 : -1); // GeometryType: 0 sphere, 1 triangle
+				P.geom[i] = q.hitTri ? 1 : (hit ? 0 : -1); // GeometryType: 0 sphere, 1 triangle
 			if (P.uv) {
-				const float2 uv = hitTri ? triangle_uv(sc.tris, (uint32_t)prim, mk3(rox, roy, roz), mk3(rdx, rdy, rdz)) : make_float2(0.f, 0.f);
+				const float2 uv = q.hitTri ? triangle_uv(sc.tris, (uint32_t)q.prim, mk3(q.ox, q.oy, q.oz), mk3(q.dx, q.dy, q.dz)) : make_float2(0.f, 0.f);
 				reinterpret_cast<float2*>(P.uv)[i] = uv;
 			}
 		}
 		overflow = overflow || st.overflow;
 		live = false;
-		ref = kRefDone;
+		q.ref = kRefDone;
 	};
 
 	QueryFeed feed;
-	feed.init(n);
-	bool exhausted = (n == 0);
+	feed.init(P0.n);
 	for (;;) {
 		// ---- refill free lanes ----
-		const unsigned long long idleMask = __ballot(!live);
-		const uint32_t nIdle = (uint32_t)__popcll(idleMask);
-		if (!exhausted && nIdle >= kQueryRefillMinIdle) {
-			const uint32_t rank = (uint32_t)__popcll(idleMask & below);
-			uint32_t got = 0;
-			bool fed = false;
-			while (got < nIdle) {
-				if (feed.next == feed.end && !feed.draw(kernarg_view<QueryParams>().ticket, n, lane)) {
-					exhausted = true;
-					break;
-				}
-				const uint32_t avail = feed.end - feed.next, room = nIdle - got;
-				const uint32_t take = avail < room ? avail : room;
-				if (!live && rank >= got && rank < got + take) {
-					ray = feed.next + (rank - got);
-					fed = true;
-				}
-				feed.next += take;
-				got += take;
-			}
-			if (fed) {
-				const QueryParams& P = kernarg_view<QueryParams>();
-				const size_t i3 = 3 * (size_t)ray;
-				const float ox = P.origins[i3 + 0], oy = P.origins[i3 + 1], oz = P.origins[i3 + 2];
-				const float dx = P.directions[i3 + 0], dy = P.directions[i3 + 1], dz = P.directions[i3 + 2];
-				tmax = P.tmax ? P.tmax[ray] : kVeryFar;
-				const RayConst nr = make_ray(mk3(ox, oy, oz), mk3(dx, dy, dz));
-				rox = nr.o.x, roy = nr.o.y, roz = nr.o.z, rdx = nr.d.x, rdy = nr.d.y, rdz = nr.d.z, rix = nr.inv.x, riy = nr.inv.y, riz = nr.inv.z;
-				regular = ray_is_regular(nr);
-				dist = tmax;
-				prim = -1;
-				sphere = -1;
-				hitTri = false;
-				occluded = false;
-				st.reset();
-				live = true;
-				// a ray with a NaN or infinite component is a miss (and never enters a box)
-				const bool valid = finite3(ox, oy, oz) && finite3(dx, dy, dz);
-				if (SPHERES && valid) {
+		const uint32_t fresh = feed.refill(live, lane, [] { return kernarg_view<QueryParams>().ticket; });
+		if (fresh != kNoItem) {
+			ray = fresh;
+			const QueryParams& P = kernarg_view<QueryParams>();
+			const size_t i3 = 3 * (size_t)ray;
+			const float ox = P.origins[i3 + 0], oy = P.origins[i3 + 1], oz = P.origins[i3 + 2];
+			const float dx = P.directions[i3 + 0], dy = P.directions[i3 + 1], dz = P.directions[i3 + 2];
+			tmax = P.tmax ? P.tmax[ray] : kVeryFar;
+			const RayConst nr = make_ray(mk3(ox, oy, oz), mk3(dx, dy, dz));
+			q.start(nr, tmax);
+			st.reset();
+			live = true;
+			// a ray with a NaN or infinite component is a miss (and never enters a box)
+			const bool valid = finite3(ox, oy, oz) && finite3(dx, dy, dz);
+			if (SPHERES && valid) {
+				if (ANY) {
 #pragma unroll
-					for (int s = TYR_NUM_SPHERES; s--;) {
+					for (int s = TYR_NUM_SPHERES; s--;) { // kernel.cu:168-172
 						const float d = sphere_intersect(P.spheres[s], nr.o, nr.d);
-						if (ANY) {
-							occluded = occluded || (d && (d + kEpsilon) < tmax); // kernel.cu:168-172
-						} else if (d && d < dist) { // kernel.cu:130-135
-							dist = d;
-							sphere = s;
-						}
+						q.occluded = q.occluded || (d && (d + kEpsilon) < tmax);
 					}
+				} else {
+					q_spheres_closest(P.spheres, nr, q);
 				}
-				ref = (valid && !occluded) ? root_ref(sc, nr, dist) : kRefDone;
-				if (ref != kRefDone)
-					ref = sc.quadRootRef;
-				if (ref == kRefDone)
-					finish(); // missed the root box, blocked by a sphere, or not a ray
 			}
-			// mostly rays that ended at once: top the wave up again first
-			if (!exhausted && (uint32_t)__popcll(__ballot(live)) < kQueryMinTraversing && (uint32_t)__popcll(__ballot(!live)) >= kQueryRefillMinIdle)
-				continue;
+			q.ref = (valid && !q.occluded) ? root_ref(sc, nr, q.dist) : kRefDone;
+			if (q.ref != kRefDone)
+				q.ref = sc.quadRootRef;
+			if (q.ref == kRefDone)
+				finish(); // missed the root box, blocked by a sphere, or not a ray
 		}
+		if (feed.top_up(live)) // mostly rays that ended at once
+			continue;
 		if (__ballot(live) == 0ull) {
-			if (exhausted)
+			if (feed.exhausted)
 				break;
 			continue;
 		}
-		const bool allRegular = (__ballot(live && !regular) == 0ull);
-		const RayConst r = { mk3(rox, roy, roz), mk3(rdx, rdy, rdz), mk3(rix, riy, riz), rix < 0, riy < 0, riz < 0 }; // bvh.h:120-121
-		// ---- descent: one pop attempt + one quad test per lane per trip ----
-		for (;;) {
-			const uint32_t nTrav = (uint32_t)__popcll(q_traversing(ref));
-			if (nTrav == 0)
-				break;
-			if (nTrav < kQueryMinTraversing) {
-				const bool anyLeaf = q_at_leaf(ref) != 0ull;
-				const bool canRefill = !exhausted && (uint32_t)__popcll(__ballot(!live || ref == kRefDone)) >= kQueryRefillMinIdle;
-				if (anyLeaf || canRefill)
-					break;
-			}
-			if (ref == kRefPop) {
-				uint32_t pr;
-				float pt;
-				if (st.pop(pr, pt)) {
-					if (pt < dist) // the pop-time half of Bbox.h:61 (any hit keeps no entry distance: -inf, always taken)
-						ref = pr;
-				} else {
-					ref = kRefDone;
-				}
-			}
-			if ((int)ref >= 0) {
-				const QuadHits q = allRegular ? test_quad<true, !ANY, true>(sc.quads, ref, r, dist, stagedNodes, nStaged) : test_quad<false, !ANY, true>(sc.quads, ref, r, dist, stagedNodes, nStaged);
-				const lanemask any01 = q.hit[0] | q.hit[1], any012 = any01 | q.hit[2];
-				st.push3(q.hit[3] & any012, q.ref[3], q.t[3], q.hit[2] & any01, q.ref[2], q.t[2], q.hit[1] & q.hit[0], q.ref[1], q.t[1]);
-				ref = lane_in(q.hit[0]) ? q.ref[0] : lane_in(q.hit[1]) ? q.ref[1] : lane_in(q.hit[2]) ? q.ref[2] : lane_in(q.hit[3]) ? q.ref[3] : kRefPop;
-			}
-		}
-		// ---- leaves: bvh.h:129-140 (closest hit) / bvh.h:229-238 (any hit), primitives in array order ----
-		if (q_is_leaf(ref)) {
-			const uint32_t off = ref & (kMaxPrimOffset - 1);
-			const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-			bool found = false;
-			TriData tri = triangle_load(sc.tris, off);
-			for (uint32_t i = 0; i < cnt && !found; ++i) {
-				const TriData cur = tri; // the next primitive of the leaf is on its way while this one is tested
-				if (i + 1 < cnt)
-					tri = triangle_load(sc.tris, off + i + 1);
-				const float t = triangle_test(cur, r);
-				if (ANY) {
-					found = (t > kEpsilon && ((dist - t) > kEpsilon)); // bvh.h:232-236
-				} else if (t > kEpsilon && t < dist && ((dist - t) > kEpsilon)) { // bvh.h:133-137
-					prim = (int)(off + i);
-					dist = t;
-					hitTri = true;
-				}
-			}
-			occluded = occluded || found;
-			ref = found ? kRefDone : kRefPop;
-		}
-		if (live && ref == kRefDone)
+		// lanes that could start work: free ones and finished rays, while rays remain
+		q_traverse<ANY>(sc, st, stagedNodes, q, live, [&](uint32_t ref) { return !feed.exhausted && (uint32_t)__popcll(__ballot(!live || ref == kRefDone)) >= kQueryRefillMinIdle; });
+		if (live && q.ref == kRefDone)
 			finish();
 	}
-	if (__ballot(overflow) != 0ull && lane == 0)
-		atomicOr(kernarg_view<QueryParams>().error, kQueryErrStackOverflow);
+	q_report_overflow(overflow, lane, kernarg_view<QueryParams>().error);
 }
 
 template <bool SPHERES>

@@ -566,6 +566,14 @@ __device__ __forceinline__ lanemask lanes_where(bool p) { return __builtin_amdgc
 __device__ __forceinline__ bool lane_in(lanemask m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 __device__ __forceinline__ lanemask mask_select(lanemask sel, lanemask a, lanemask b) { return (sel & a) | (~sel & b); }
 
+// the flat state machines' lane states (k_trace_flat and the counting kernels in hip/traverse_flat.hip, the query loop in
+// hip/query_common.hpp): interior ref | leaf ref | kRefPop | kRefDone
+__device__ __forceinline__ bool ref_is_leaf(uint32_t ref) { return (ref & kRefLeaf) && ref < kRefPop; }
+// the same as wave-wide masks, one ballot per comparison (the ballot of a compound condition goes through a 0/1
+// VGPR and a second comparison, see slab_fast_mask)
+__device__ __forceinline__ lanemask lanes_traversing(uint32_t ref) { return __builtin_amdgcn_ballot_w64((int)ref >= 0) | __builtin_amdgcn_ballot_w64(ref == kRefPop); }
+__device__ __forceinline__ lanemask lanes_at_leaf(uint32_t ref) { return __builtin_amdgcn_ballot_w64((ref & kRefLeaf) != 0u) & __builtin_amdgcn_ballot_w64(ref < kRefPop); }
+
 struct QuadHits { // in visit order (ORDERED) or in node order (not ORDERED; quad_ranks gives each slot's place in the visit order)
 	uint32_t ref[4];
 	float t[4];

@@ -33,12 +33,7 @@ constexpr uint32_t kTraceBlockWide = 768;
 // `minTraversing` lanes are still descending and there is other work for the wave (leaves to
 // intersect, or enough free lanes for a refill).
 // ======================================================================================
-__device__ __forceinline__ bool ref_is_leaf(uint32_t ref) { return (ref & kRefLeaf) && ref < kRefPop; }
-__device__ __forceinline__ bool ref_is_traversing(uint32_t ref) { return ((int)ref >= 0) || ref == kRefPop; }
-// the same as wave-wide masks, one ballot per comparison (the ballot of a compound condition goes through a 0/1
-// VGPR and a second comparison, see slab_fast_mask)
-__device__ __forceinline__ unsigned long long lanes_traversing(uint32_t ref) { return __builtin_amdgcn_ballot_w64((int)ref >= 0) | __builtin_amdgcn_ballot_w64(ref == kRefPop); }
-__device__ __forceinline__ unsigned long long lanes_at_leaf(uint32_t ref) { return __builtin_amdgcn_ballot_w64((ref & kRefLeaf) != 0u) & __builtin_amdgcn_ballot_w64(ref < kRefPop); }
+// (the lane-state predicates ref_is_leaf / lanes_traversing / lanes_at_leaf: hip/traverse.hpp, shared with the query loop)
 
 #ifdef TYR_QUAD_STATS
 constexpr bool kLoopStats = true; // diagnostic build: the production (quad) kernel fills tyr_counters.debug too, tools/loop_occupancy.py
