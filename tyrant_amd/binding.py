@@ -122,6 +122,12 @@ class AovOut(C.Structure):
     _fields_ = [("albedo", P), ("normal", P), ("depth", P), ("prim", P), ("geom", P)]
 
 
+class NearestOut(C.Structure):
+    """tyr_nearest_out: device pointers of tyr_query_nearest's outputs; uv, region, point may be NULL"""
+
+    _fields_ = [("dist2", P), ("prim", P), ("uv", P), ("region", P), ("point", P)]
+
+
 class AovChainOut(C.Structure):
     """tyr_aov_chain_out: device pointers of what tyr_render_aov_chain adds, NULL to skip one"""
 
@@ -261,6 +267,7 @@ SYMBOLS = {
     "tyr_query_closest": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P, P, P, P]),
     "tyr_query_any": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
+    "tyr_query_nearest": (C.c_int, [P, c_u32, P, P, c_u32, P, P]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
     "tyr_render_aov_chain": (C.c_int, [P, c_u32, c_u32, P, P, P]),
@@ -558,20 +565,25 @@ class Renderer:
         _check(self.L.tyr_queue_import(self.h, _ptr(r), n_survivors), "tyr_queue_import")
 
     # ---- ray queries on the uploaded scene (tyr_query_closest / tyr_query_any) ----
+    def _query_take(self, a, what, shape):
+        """a caller's float32 CUDA tensor as it is (a numpy array is copied to the ctx's device first)"""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        if isinstance(a, np.ndarray):
+            a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        if not isinstance(a, torch.Tensor):
+            raise TypeError(f"{what}: a torch tensor or a numpy array")
+        if a.dtype != torch.float32 or a.device != dev or not a.is_contiguous() or tuple(a.shape) != shape:
+            raise ValueError(f"{what}: a contiguous float32 tensor of shape {shape} on {dev}, not {tuple(a.shape)} {a.dtype} on {a.device}")
+        return a
+
     def _query_rays(self, origins, directions, tmax):
         """the caller's (N, 3) float32 CUDA tensors as they are (numpy arrays are copied to the ctx's device first)"""
         import torch
 
         dev = torch.device("cuda", self.device)
-
-        def take(a, what, shape):
-            if isinstance(a, np.ndarray):
-                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-            if not isinstance(a, torch.Tensor):
-                raise TypeError(f"{what}: a torch tensor or a numpy array")
-            if a.dtype != torch.float32 or a.device != dev or not a.is_contiguous() or tuple(a.shape) != shape:
-                raise ValueError(f"{what}: a contiguous float32 tensor of shape {shape} on {dev}, not {tuple(a.shape)} {a.dtype} on {a.device}")
-            return a
+        take = self._query_take
 
         staged = not all(isinstance(a, torch.Tensor) for a in (origins, directions, tmax) if a is not None)
         o = origins if isinstance(origins, torch.Tensor) else np.asarray(origins)
@@ -678,6 +690,31 @@ class Renderer:
         self._on_stream(stream, lambda h: self.L.tyr_query_any(self.h, n, o.data_ptr(), d.data_ptr(), tp, flags, occ.data_ptr(), h), staged)
         self._query_finish()
         return occ
+
+    def query_nearest(self, points, max_dist=None, stream=None):
+        """tyr_query_nearest: for every point the nearest triangle of the uploaded scene (include/tyr_c.h "Closest-point queries").
+        points: (N, 3) float32, max_dist: (N,) or None -- torch tensors on this ctx's device, taken as they are, or numpy arrays.
+        Returns torch tensors (dist2, prim, uv, region, point): without a triangle nearer than max_dist, dist2 = max_dist^2 (+inf for
+        an invalid point or max_dist), prim = -1, uv = (0, 0), region = 0 and point = the query point."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        take = self._query_take
+        staged = not all(isinstance(a, torch.Tensor) for a in (points, max_dist) if a is not None)
+        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
+        n = p.shape[0] if p.ndim == 2 else -1
+        p = take(p, "points", (n, 3))
+        md = take(max_dist, "max_dist", (n,)) if max_dist is not None else None
+        dist2 = torch.empty(n, dtype=torch.float32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
+        region = torch.empty(n, dtype=torch.uint8, device=dev)
+        point = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        out = NearestOut(dist2.data_ptr(), prim.data_ptr(), uv.data_ptr(), region.data_ptr(), point.data_ptr())
+        mp = md.data_ptr() if md is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_nearest(self.h, n, p.data_ptr(), mp, 0, C.byref(out), h), staged)
+        self._query_finish()
+        return dist2, prim, uv, region, point
 
     def render_aov(self, spp, albedo=True, normal=True, depth=True, ids=True, stream=None, max_chain=None) -> dict:
         """tyr_render_aov: first-hit guide buffers of the current camera at the current frame counter, spp camera rays per pixel
