@@ -228,6 +228,52 @@ void orc_stage_extend_debug(orc_ctx* c); /* kernel.cu:300-328 (ORC_FLAG_DEBUG_BV
 void orc_stage_shade(orc_ctx* c);   /* kernel.cu:347-627 */
 void orc_stage_connect(orc_ctx* c); /* kernel.cu:630-646 */
 void orc_stage_end(orc_ctx* c);     /* frame++ and the caller's std::swap (kernel.cu:736-739, main.cpp:169) */
+/* ---- per-ray branch trace of orc_stage_shade (TEST INFRASTRUCTURE only: the product has no such output) ------------
+ * With an array of 2 * queue_size words set, shade writes for record `index` the 64-bit mask of the ways it went
+ * (words 2 * index: low half, 2 * index + 1: high half); NULL (the default) switches it off.  The trace reads what shade
+ * computes and changes none of it.  tests/shade_cases.py names the bits from this list. */
+#define ORC_TR_HIT (1ull << 0)
+#define ORC_TR_MISS (1ull << 1)
+#define ORC_TR_SPHERE (1ull << 2)
+#define ORC_TR_TRIANGLE (1ull << 3)
+#define ORC_TR_MAT_DIFF (1ull << 4) /* << material: DIFF, SPEC, REFR, PHONG, LIGHT = bits 4 .. 8 (after the fall-back of an out-of-range materialType) */
+#define ORC_TR_OUTSIDE (1ull << 9)
+#define ORC_TR_INSIDE (1ull << 10)
+#define ORC_TR_LIGHT_SEEN (1ull << 11)   /* LIGHT with lastSpecular: it emits */
+#define ORC_TR_LIGHT_UNSEEN (1ull << 12) /* LIGHT without: throughput zeroed */
+#define ORC_TR_NEE_SUN_DIFF (1ull << 13)
+#define ORC_TR_NEE_EMITTER_DIFF (1ull << 14)
+#define ORC_TR_NEE_SUN_PHONG (1ull << 15)
+#define ORC_TR_NEE_EMITTER_PHONG (1ull << 16)
+#define ORC_TR_REJ_SUN_COS (1ull << 17)       /* sunLight <= 0 */
+#define ORC_TR_REJ_COS_SURFACE (1ull << 18)   /* cosSurfaceToLight <= 0 */
+#define ORC_TR_REJ_COS_LIGHT (1ull << 19)     /* cosLightToSurface <= 0 on spheres[6] */
+#define ORC_TR_REJ_TRIANGLE_BACK (1ull << 20) /* cosLightToSurface <= 0 on an emissive triangle: its back side */
+#define ORC_TR_REJ_LOBE_SUN (1ull << 21)      /* Phong: phongCos <= epsilon toward the sun (with sunLight > 0) */
+#define ORC_TR_REJ_LOBE_EMITTER (1ull << 22)  /* Phong: phongCos <= epsilon toward a valid emitter sample */
+#define ORC_TR_PICK_SPHERE (1ull << 23)
+#define ORC_TR_PICK_TRIANGLE (1ull << 24)
+#define ORC_TR_BOUNCES_BELOW_MAX (1ull << 25)
+#define ORC_TR_BOUNCES_AT_MAX (1ull << 26)
+#define ORC_TR_TIR (1ull << 27)
+#define ORC_TR_FRESNEL_REFLECT (1ull << 28) /* reflected by the draw, not by total internal reflection */
+#define ORC_TR_REFRACT (1ull << 29)
+#define ORC_TR_PHONG_ONE_ROUND (1ull << 30)
+#define ORC_TR_PHONG_MORE_ROUNDS (1ull << 31)
+#define ORC_TR_SURVIVED (1ull << 32)
+#define ORC_TR_DIED_P_EPSILON (1ull << 33)
+#define ORC_TR_DIED_DRAW (1ull << 34)
+#define ORC_TR_DIED_BOUNCE_CAP (1ull << 35)
+#define ORC_TR_MISS_SKY (1ull << 36)
+#define ORC_TR_MISS_SUNSKY (1ull << 37)
+#define ORC_TR_ABSORB (1ull << 38)         /* left glass: exp(-colour * distance) applied */
+#define ORC_TR_ABSORB_TO_ZERO (1ull << 39) /* ... and a non-zero throughput came out (0, 0, 0) */
+#define ORC_TR_MATERIAL_FALLBACK (1ull << 40) /* materialType above the highest allowed: DIFF */
+#define ORC_TR_PALETTE (1ull << 41)
+#define ORC_TR_SHADOW_RAY (1ull << 42)     /* a shadow ray was appended */
+#define ORC_TR_P_CLAMPED (1ull << 43)      /* the largest throughput channel is above 1: p = 1 */
+void orc_set_shade_trace(orc_ctx* c, uint32_t* masks_or_null);
+
 /* overwrite the work queue (for kernel-level parity tests) */
 void orc_import_work_queue(orc_ctx* c, const orc_ray* rays, uint32_t n_survivors);
 

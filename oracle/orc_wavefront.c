@@ -53,6 +53,7 @@ struct orc_ctx {
 	orc_shadow* shadow_queue;
 	float* blit_buffer; /* float4[W*H] */
 	orc_counters k;
+	uint32_t* shade_trace; /* orc_set_shade_trace: two words per record, or NULL (test infrastructure, orc.h) */
 };
 
 void orc_default_spheres(orc_sphere s[ORC_NUM_SPHERES]) {
@@ -188,6 +189,7 @@ void orc_set_frame(orc_ctx* c, uint32_t frame) {
 	c->frame = frame;
 	c->k.frame = frame;
 }
+void orc_set_shade_trace(orc_ctx* c, uint32_t* masks) { c->shade_trace = masks; }
 void orc_get_counters(const orc_ctx* c, orc_counters* out) { *out = c->k; }
 const float* orc_blit_buffer(const orc_ctx* c) { return c->blit_buffer; }
 const orc_ray* orc_ray_queue(const orc_ctx* c, int which) { return which == 0 ? c->ray_buffer : c->ray_buffer_next; }
@@ -424,8 +426,9 @@ static int sample_sphere_light(const orc_ctx* c, uint32_t* seed, v3 origin, v3 n
  *   over the triangle), emitting from its front side (normal e1 x e2, loader.h:28).
  * Returns 1 if a shadow ray is due; *weight = emission * area-measure factors that replace "emission, 4 pi r^2" of the
  * sphere formulas (kernel.cu:436-442), including the 1/(pick probability) = nLights + 1. */
-static int sample_light(const orc_ctx* c, uint32_t* seed, v3 origin, v3 normal, v3* lightDir, float* cosSurfaceToLight, float* cosLightToSurface, v3* lightVector, v3* emission, float* area) {
+static int sample_light_untraced(const orc_ctx* c, uint32_t* seed, v3 origin, v3 normal, v3* lightDir, float* cosSurfaceToLight, float* cosLightToSurface, v3* lightVector, v3* emission, float* area, int* picked_triangle) {
 	const orc_sphere* ls = &c->spheres[6];
+	*picked_triangle = 0;
 	if (!(c->flags & ORC_FLAG_LIGHT_LIST) || c->nLights == 0) {
 		*emission = v3load(ls->emmission);
 		*area = 4 * ORC_PI * ls->radius * ls->radius;
@@ -438,6 +441,7 @@ static int sample_light(const orc_ctx* c, uint32_t* seed, v3 origin, v3 normal, 
 		*area = 4 * ORC_PI * ls->radius * ls->radius;
 		return sample_sphere_light(c, seed, origin, normal, lightDir, cosSurfaceToLight, cosLightToSurface, lightVector);
 	}
+	*picked_triangle = 1;
 	const orc_triangle* t = &c->prims[c->lights[k]];
 	const float u1 = rng_float(seed);
 	const float u2 = rng_float(seed);
@@ -457,6 +461,18 @@ static int sample_light(const orc_ctx* c, uint32_t* seed, v3 origin, v3 normal, 
 	return *cosSurfaceToLight > 0 && *cosLightToSurface > 0;
 }
 
+/* sample_light with the shade trace (orc.h ORC_TR_*): which kind of emitter was picked, and each condition that rejects the sample */
+static int sample_light(const orc_ctx* c, uint32_t* seed, v3 origin, v3 normal, v3* lightDir, float* cosSurfaceToLight, float* cosLightToSurface, v3* lightVector, v3* emission, float* area, uint64_t* tr) {
+	int tri;
+	const int ok = sample_light_untraced(c, seed, origin, normal, lightDir, cosSurfaceToLight, cosLightToSurface, lightVector, emission, area, &tri);
+	*tr |= tri ? ORC_TR_PICK_TRIANGLE : ORC_TR_PICK_SPHERE;
+	if (!(*cosSurfaceToLight > 0))
+		*tr |= ORC_TR_REJ_COS_SURFACE;
+	if (!(*cosLightToSurface > 0))
+		*tr |= tri ? ORC_TR_REJ_TRIANGLE_BACK : ORC_TR_REJ_COS_LIGHT;
+	return ok;
+}
+
 static void push_shadow(orc_ctx* c, v3 origin, v3 dir, v3 color, int index, float closest) {
 	orc_shadow* s = &c->shadow_queue[c->k.shadow_ray_cnt++];
 	v3store(s->origin, origin);
@@ -472,6 +488,8 @@ void orc_stage_shade(orc_ctx* c) {
 	const float phongexponent = 40.0f;
 	for (uint32_t index = 0; index < c->k.n_live; ++index) {
 		int new_frame = 0;
+		uint64_t tr = 0; /* the shade trace of this record (orc.h ORC_TR_*): written at the end when an array is set, read by nothing here */
+		const uint32_t shadows_before = c->k.shadow_ray_cnt;
 		orc_ray ray = c->ray_buffer[index]; /* local copy; the reference mutates in place, nothing reads it back */
 		v3 color = v3make(0.f, 0.f, 0.f);
 		v3 object_color = v3make(0.f, 0.f, 0.f);
@@ -484,6 +502,7 @@ void orc_stage_shade(orc_ctx* c) {
 			origin = v3add(origin, v3scale(direction, ray.distance));
 
 			v3 normal;
+			tr |= ORC_TR_HIT | (ray.geometry_type == 0 ? ORC_TR_SPHERE : ORC_TR_TRIANGLE);
 			if (ray.geometry_type == 0) {
 				const orc_sphere* object = &c->spheres[ray.identifier];
 				normal = v3divs(v3sub(origin, v3load(object->position)), object->radius);
@@ -501,21 +520,28 @@ void orc_stage_shade(orc_ctx* c) {
 					/* extension: LIGHT on a triangle needs ORC_FLAG_LIGHT_LIST */
 					const int highest = (c->flags & ORC_FLAG_LIGHT_LIST) ? ORC_LIGHT : ORC_PHONG;
 					reflection_type = triangle->materialType <= highest ? triangle->materialType : ORC_DIFF;
+					if (triangle->materialType > highest)
+						tr |= ORC_TR_MATERIAL_FALLBACK;
 				}
 				if (c->flags & ORC_FLAG_TRIANGLE_COLORS) {
 					/* the reference's commented-out `tempTriangle.color = mesh.color` (Scene.cpp:44), treated like a sphere's
 					 * colour (kernel.cu:375-377) */
 					object_color = v3load(c->palette_color[triangle->pad_[0]]);
+					tr |= ORC_TR_PALETTE;
 					if (reflection_type != ORC_REFR && reflection_type != ORC_LIGHT)
 						direct = v3mul(direct, object_color);
 				}
 			}
 
 			int outside = v3dot(normal, direction) < 0;
+			tr |= outside ? ORC_TR_OUTSIDE : ORC_TR_INSIDE;
+			tr |= ORC_TR_MAT_DIFF << reflection_type;
+			tr |= ray.bounces < ORC_MAX_BOUNCES ? ORC_TR_BOUNCES_BELOW_MAX : ORC_TR_BOUNCES_AT_MAX;
 			normal = outside ? normal : v3scale(normal, -1.f);
 			origin = v3add(origin, v3scale(normal, ORC_EPSILON));
 
 			if (reflection_type == ORC_LIGHT) {
+				tr |= ray.lastSpecular ? ORC_TR_LIGHT_SEEN : ORC_TR_LIGHT_UNSEEN;
 				if (ray.lastSpecular) {
 					color = v3mul(direct, ray.geometry_type == 0 ? v3load(c->spheres[ray.identifier].emmission) : triangle_emission(c, &c->prims[ray.identifier]));
 				} else {
@@ -533,16 +559,20 @@ void orc_stage_shade(orc_ctx* c) {
 				v3 sunSampleDir = v3load(sd);
 				float sunLight = v3dot(normal, sunSampleDir);
 				if (rng_float(&seed) < 0.5f) {
+					tr |= ORC_TR_NEE_SUN_DIFF;
 					if (sunLight > 0.f) {
 						float sv[3];
 						orc_sun(&c->sun, sd, sv);
 						v3 col = v3mul(v3rscale(2.0f, direct), v3scale(v3scale(v3load(sv), sunLight), 1E-5f));
 						push_shadow(c, origin, sunSampleDir, col, ray.index, 1e20f);
+					} else {
+						tr |= ORC_TR_REJ_SUN_COS;
 					}
 				} else {
 					v3 lightDir, lightVector, emission;
 					float cosS, cosL, area;
-					if (sample_light(c, &seed, origin, normal, &lightDir, &cosS, &cosL, &lightVector, &emission, &area)) {
+					tr |= ORC_TR_NEE_EMITTER_DIFF;
+					if (sample_light(c, &seed, origin, normal, &lightDir, &cosS, &cosL, &lightVector, &emission, &area, &tr)) {
 						float closestAllowed = v3length(lightVector);
 						float solidAngle = (cosL * area) / v3dot(lightVector, lightVector);
 						v3 shadowColor = v3scale(v3scale(v3scale(v3mul(v3scale(emission, 2.0f), direct), solidAngle), ORC_INV_PI), cosS);
@@ -578,6 +608,7 @@ void orc_stage_shade(orc_ctx* c) {
 				const float sinT2 = n * n * (1.0f - cosI * cosI);
 				if (sinT2 > 1.0f) {
 					fresnel = 1.0f;
+					tr |= ORC_TR_TIR;
 				} else {
 					const float x = 1.0f - cosI;
 					fresnel = r0 + (1.0f - r0) * x * x * x * x * x;
@@ -585,20 +616,29 @@ void orc_stage_shade(orc_ctx* c) {
 				if (rng_float(&seed) < fresnel) {
 					ray.lastSpecular = 1;
 					direction = v3reflect(direction, normal);
+					if (!(sinT2 > 1.0f))
+						tr |= ORC_TR_FRESNEL_REFLECT;
 				} else {
+					tr |= ORC_TR_REFRACT;
 					origin = v3sub(origin, v3scale(v3scale(normal, 2.f), ORC_EPSILON));
 					const float cosT = sqrtf(1.0f - sinT2);
 					direction = v3add(v3rscale(n, direction), v3rscale(n * cosI - cosT, normal));
 				}
 				if (!outside) {
 					v3 a = v3scale(v3neg(object_color), ray.distance);
+					const int lit = direct.x != 0 || direct.y != 0 || direct.z != 0;
 					direct = v3mul(direct, v3make(dm_expf(a.x), dm_expf(a.y), dm_expf(a.z)));
+					tr |= ORC_TR_ABSORB;
+					if (lit && direct.x == 0 && direct.y == 0 && direct.z == 0)
+						tr |= ORC_TR_ABSORB_TO_ZERO;
 				}
 				break;
 			}
 			case ORC_PHONG: {
 				v3 w, u, v, d;
+				int rounds = 0;
 				do {
+					++rounds;
 					float phi = 2 * ORC_PI * rng_float(&seed);
 					float r2 = rng_float(&seed);
 					float cosTheta = dm_powf(1.0f - r2, 1.0f / (phongexponent + 1.0f));
@@ -613,12 +653,18 @@ void orc_stage_shade(orc_ctx* c) {
 					d = v3add(v3add(v3scale(v3scale(u, dm_cosf(phi)), sinTheta), v3scale(v3scale(v, dm_sinf(phi)), sinTheta)), v3scale(w, cosTheta));
 					d = v3normalize(d);
 				} while (v3dot(d, normal) <= ORC_EPSILON);
+				tr |= rounds == 1 ? ORC_TR_PHONG_ONE_ROUND : ORC_TR_PHONG_MORE_ROUNDS;
 
 				float sd[3];
 				orc_cone_sample(&c->sun, &seed, sd);
 				v3 sunSampleDir = v3load(sd);
 				float sunLight = v3dot(normal, sunSampleDir);
 				if (rng_float(&seed) < 0.5f) {
+					tr |= ORC_TR_NEE_SUN_PHONG;
+					if (!(sunLight > 0.f))
+						tr |= ORC_TR_REJ_SUN_COS;
+					else if (!(v3dot(sunSampleDir, w) > ORC_EPSILON))
+						tr |= ORC_TR_REJ_LOBE_SUN;
 					if (sunLight > 0.f) {
 						float phongCos = v3dot(sunSampleDir, w);
 						if (phongCos > ORC_EPSILON) {
@@ -632,8 +678,11 @@ void orc_stage_shade(orc_ctx* c) {
 				} else {
 					v3 lightDir, lightVector, emission;
 					float cosS, cosL, area;
-					if (sample_light(c, &seed, origin, normal, &lightDir, &cosS, &cosL, &lightVector, &emission, &area)) {
+					tr |= ORC_TR_NEE_EMITTER_PHONG;
+					if (sample_light(c, &seed, origin, normal, &lightDir, &cosS, &cosL, &lightVector, &emission, &area, &tr)) {
 						float phongCos = v3dot(lightDir, w);
+						if (!(phongCos > ORC_EPSILON))
+							tr |= ORC_TR_REJ_LOBE_EMITTER;
 						if (phongCos > ORC_EPSILON) {
 							phongCos = dm_powf(phongCos, phongexponent);
 							float closestAllowed = v3length(lightVector);
@@ -657,7 +706,16 @@ void orc_stage_shade(orc_ctx* c) {
 
 			/* Russian roulette, kernel.cu:599-611 */
 			float p = glm_minf(1.0f, glm_maxf(direct.z, glm_maxf(direct.x, direct.y)));
+			if (glm_maxf(direct.z, glm_maxf(direct.x, direct.y)) > 1.0f)
+				tr |= ORC_TR_P_CLAMPED;
+			if (c->k.shadow_ray_cnt != shadows_before)
+				tr |= ORC_TR_SHADOW_RAY;
+			if (!(ray.bounces < ORC_MAX_BOUNCES))
+				tr |= ORC_TR_DIED_BOUNCE_CAP;
+			else if (!(p > (0 + ORC_EPSILON)))
+				tr |= ORC_TR_DIED_P_EPSILON;
 			if (ray.bounces < ORC_MAX_BOUNCES && p > (0 + ORC_EPSILON) && rng_float(&seed) <= p) {
+				tr |= ORC_TR_SURVIVED;
 				ray.bounces++;
 				direct = v3scale(direct, 1.0f / p);
 				v3store(ray.origin, origin);
@@ -671,6 +729,7 @@ void orc_stage_shade(orc_ctx* c) {
 		} else {
 			float dv[3], sv[3];
 			v3store(dv, direction);
+			tr |= ORC_TR_MISS | (ray.lastSpecular ? ORC_TR_MISS_SUNSKY : ORC_TR_MISS_SKY);
 			if (!ray.lastSpecular)
 				orc_sky(&c->sun, dv, sv);
 			else
@@ -684,6 +743,12 @@ void orc_stage_shade(orc_ctx* c) {
 		px[1] += color.y;
 		px[2] += color.z;
 		px[3] += (float)new_frame;
+		if (c->shade_trace) {
+			if ((tr & ORC_TR_HIT) && !(tr & (ORC_TR_SURVIVED | ORC_TR_DIED_BOUNCE_CAP | ORC_TR_DIED_P_EPSILON)))
+				tr |= ORC_TR_DIED_DRAW;
+			c->shade_trace[2 * (size_t)index] = (uint32_t)tr;
+			c->shade_trace[2 * (size_t)index + 1] = (uint32_t)(tr >> 32);
+		}
 	}
 	c->k.total_shadow_rays += c->k.shadow_ray_cnt;
 }

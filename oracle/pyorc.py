@@ -164,6 +164,7 @@ def lib() -> C.CDLL:
         for name in ("orc_stage_begin", "orc_stage_primary", "orc_stage_extend", "orc_stage_extend_debug", "orc_stage_shade", "orc_stage_connect", "orc_stage_end"):
             getattr(L, name).argtypes = [P]
         L.orc_import_work_queue.argtypes = [P, P, c_u32]
+        L.orc_set_shade_trace.argtypes = [P, P]
         L.orc_bbox_host_ops.argtypes = [P, c_i, P, P]
         L.orc_glm.restype = c_i
         L.orc_glm.argtypes = [c_i, P, P, P, c_i, P]
@@ -382,6 +383,17 @@ class Oracle:
     def import_work_queue(self, rays: np.ndarray, n_survivors: int):
         r = np.ascontiguousarray(rays)
         self.L.orc_import_work_queue(self.h, _ptr(r), n_survivors)
+
+    def set_shade_trace(self, on: bool = True):
+        """switch the per-record branch trace of the shade stage on or off (orc_set_shade_trace; the array lives here)"""
+        self._trace = np.zeros(2 * self.N, dtype=np.uint32) if on else None
+        self.L.orc_set_shade_trace(self.h, None if self._trace is None else _ptr(self._trace))
+
+    def shade_trace(self, count=None) -> np.ndarray:
+        """uint64 masks (orc.h ORC_TR_*) of the records the last shade stage processed"""
+        n = self.N if count is None else count
+        w = self._trace[: 2 * n].astype(np.uint64)
+        return w[0::2] | (w[1::2] << np.uint64(32))
 
     def sun_params(self) -> SunParams:
         return self.L.orc_sun_params(self.h).contents
