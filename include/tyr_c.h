@@ -303,7 +303,11 @@ int tyr_scene_hash(tyr_ctx* ctx, tyr_layout_stats* out);
  * max, clamp, mix, smoothstep and the vec3 operators in glm's evaluation order -- Dependencies/glm-0.9.9.3/glm/detail/
  * func_geometric.inl:14-116, func_common.inl:16-29, 103-111, 257-265, 566 -- plus the deterministic pow / exp), run ON
  * THE DEVICE over n float3 triples of host arrays a, b, c into host array out (float3 each): the hook that pins the
- * device arithmetic to the vendored glm's own answers (tests/golden/ref_glm.npz).  op codes: oracle/ref_harness.cpp. */
+ * device arithmetic to the vendored glm's own answers (tests/golden/ref_glm.npz).  op codes 0-19: oracle/ref_harness.cpp.
+ * Ops 32-49 are the project's own and have no glm counterpart: the numeric contract's sin / cos / exp / pow (hip/detmath.hpp)
+ * with the binary64 values they round, and the samplers of hip/device_common.hpp, listed at contract_probe in
+ * hip/frame.hip.  They write three 32-bit WORDS per element into out (binary64 values as two words, low first; seeds and
+ * integers as they are) and read seeds as the bit patterns of a's first component.  Ops 20-31 are TYR_ERR_INVALID. */
 int tyr_vecmath_probe(int32_t device, int32_t op, const float* a, const float* b, const float* c, uint32_t n, float* out);
 
 /* The atmosphere as the shade kernel evaluates it (hip/sunsky.hpp, hip/device_common.hpp cone_sample), run ON THE DEVICE

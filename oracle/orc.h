@@ -129,6 +129,11 @@ float orc_dm_sinf(float x);
 float orc_dm_cosf(float x);
 float orc_dm_expf(float x);
 float orc_dm_powf(float x, float y);
+/* the same over arrays, with the binary64 values each function rounds (orc_dm.c lists the ops and the layout:
+ * out32 holds 2 words, out64 4 doubles per element; y is read by pow only) */
+int orc_dm_map(int op, const float* x, const float* y, int n, uint32_t* out32, double* out64);
+/* the RNG and the sampling helpers above over arrays of three 32-bit words per element (ops: orc_wavefront.c) */
+int orc_sampler_map(int op, const uint32_t* in, int n, uint32_t* out);
 
 /* ---- f4, headless: Camera::handle_input / Camera::update (camera.cpp:3-52) as pure functions ---------------------- */
 typedef struct {

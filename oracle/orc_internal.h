@@ -72,10 +72,14 @@ static inline float glm_clampf(float x, float lo, float hi) { return glm_minf(gl
 /* ---------------- deterministic transcendental layer ---------------------- */
 
 static inline double dm_round(double t) {
-	/* round-to-nearest-even for |t| < 2^51 via the 1.5*2^52 trick */
+	/* IEEE roundToIntegralTiesToEven for |t| < 2^51: the 1.5*2^52 trick gives the magnitude, and the result keeps t's
+	 * sign as rint's does (the trick alone turns -0.0 and every t in [-0.5, -0] into +0.0; the device's rint, one
+	 * v_rndne_f64, gives -0.0 there).  The sign of a zero kd never reaches a binary32 result -- kd * c is then a zero
+	 * and x - (+-0) is x unless x is itself a zero, and each polynomial maps both zeros to one value -- but it is in
+	 * the binary64 values the device is compared with (tests/test_numeric_contract.py). */
 	const double M = 6755399441055744.0;
 	double u = t + M;
-	return u - M;
+	return copysign(u - M, t);
 }
 static inline double dm_pow2i(int k) {
 	/* exact 2^k for -1022 <= k <= 1023 */

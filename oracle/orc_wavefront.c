@@ -257,6 +257,47 @@ void orc_orthonormal_basis_naive(const float w_[3], float u_[3], float v_[3]) {
 	v3store(v_, v3cross(w, u));
 }
 
+/* The RNG and the sampling helpers over arrays of three 32-bit words per element: what the device's probe ops 44-49
+ * (hip/frame.hip contract_probe) are compared with.  Seeds are in[3*i]; floats travel as their bit patterns.
+ *   0  rng_float, seed after, rng_int_0_max(16) from the same seed     1  rng_float2, seed after, seed after rng_int_0_max(16)
+ *   2  stratified sample: sx, sy, seed after    3  disk(in[0], in[1]): dx, dy, 0    4 / 5  basis(in[0..2]): u / v */
+int orc_sampler_map(int op, const uint32_t* in, int n, uint32_t* out) {
+	if (op < 0 || op > 5)
+		return -1;
+	for (int i = 0; i < n; ++i) {
+		const uint32_t* a = in + 3 * (size_t)i;
+		uint32_t* o = out + 3 * (size_t)i;
+		float f[3], r[3] = { 0.0f, 0.0f, 0.0f }, v[3];
+		uint32_t s = a[0], s2 = a[0];
+		memcpy(f, a, 12);
+		switch (op) {
+		case 0:
+			r[0] = rng_float(&s);
+			memcpy(o, r, 4);
+			o[1] = s;
+			o[2] = (uint32_t)rng_int_0_max(&s2, 16);
+			continue;
+		case 1:
+			r[0] = rng_float2(&s);
+			(void)rng_int_0_max(&s2, 16);
+			memcpy(o, r, 4);
+			o[1] = s;
+			o[2] = s2;
+			continue;
+		case 2:
+			orc_random_2d_stratified_sample(&s, r);
+			memcpy(o, r, 8);
+			o[2] = s;
+			continue;
+		case 3: orc_concentric_sample_disk(f, r); break;
+		case 4: orc_orthonormal_basis_naive(f, r, v); break;
+		default: orc_orthonormal_basis_naive(f, v, r); break;
+		}
+		memcpy(o, r, 12);
+	}
+	return 0;
+}
+
 /* ---- host prologue of launch_kernels (kernel.cu:671-718) ------------------ */
 void orc_stage_begin(orc_ctx* c) {
 	if (c->first_time) {

@@ -113,6 +113,9 @@ def lib() -> C.CDLL:
             getattr(L, name).argtypes = [c_f]
         L.orc_dm_powf.restype = c_f
         L.orc_dm_powf.argtypes = [c_f, c_f]
+        _declare_dm_map(L)
+        L.orc_sampler_map.restype = c_i
+        L.orc_sampler_map.argtypes = [c_i, P, c_i, P]
         L.orc_sun_setup.argtypes = [fp, C.POINTER(SunParams)]
         for name in ("orc_sun", "orc_sky", "orc_sunsky"):
             getattr(L, name).argtypes = [C.POINTER(SunParams), fp, fp]
@@ -248,6 +251,53 @@ def brute_closest(prims: np.ndarray, origin, direction, tmax, last_on_ties: bool
     ident = np.zeros(n, dtype=np.int32)
     lib().orc_brute_closest_batch(_ptr(prims), prims.shape[0], _ptr(o), _ptr(d), _ptr(tm), n, int(last_on_ties), _ptr(t), _ptr(ident))
     return t, ident
+
+
+def _declare_dm_map(L):
+    L.orc_dm_map.restype = c_i
+    L.orc_dm_map.argtypes = [c_i, P, P, c_i, P, P]
+
+
+def load_dm(path: str) -> C.CDLL:
+    """another build of oracle/orc_dm.c alone (a test compiles one with other floating-point flags), for dm_map(L=...)"""
+    L = C.CDLL(path)
+    _declare_dm_map(L)
+    return L
+
+
+# orc_dm_map's ops and what they return: name -> (array, column), array 32 = out32 (uint32), 64 = out64 (binary64 as uint64 bits)
+DM_OPS = {"sin": 0, "cos": 1, "sincos": 2, "exp": 3, "pow": 4}
+DM_FIELDS = {
+    "sin": {"f32": (32, 0), "q": (32, 1), "r": (64, 0), "rounded": (64, 1)},
+    "cos": {"f32": (32, 0), "q": (32, 1), "r": (64, 0), "rounded": (64, 1)},
+    "sincos": {"sin": (32, 0), "cos": (32, 1)},
+    "exp": {"f32": (32, 0), "kd": (64, 0), "r": (64, 1), "rounded": (64, 2)},
+    "pow": {"f32": (32, 0), "log2": (64, 0), "t": (64, 1), "w": (64, 2), "rounded": (64, 3)},
+}
+
+
+def dm_map(fn: str, x, y=None, L=None) -> dict:
+    """orc_dm_map over arrays: {field: bit patterns} (uint32 for binary32 results and q, uint64 for binary64 values)"""
+    x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+    y = None if y is None else np.ascontiguousarray(y, dtype=np.float32).ravel()
+    assert y is None or y.shape == x.shape
+    n = x.shape[0]
+    o32 = np.zeros((n, 2), dtype=np.uint32)
+    o64 = np.zeros((n, 4), dtype=np.float64)
+    rc = (L or lib()).orc_dm_map(DM_OPS[fn], _ptr(x), None if y is None else _ptr(y), n, _ptr(o32), _ptr(o64))
+    if rc:
+        raise ValueError(f"orc_dm_map({fn}) failed: {rc}")
+    u64 = o64.view(np.uint64)
+    return {k: (o32 if a == 32 else u64)[:, col].copy() for k, (a, col) in DM_FIELDS[fn].items()}
+
+
+def sampler_map(op: int, words) -> np.ndarray:
+    """orc_sampler_map over (n, 3) uint32 words (floats as their bit patterns) -> (n, 3) uint32 words"""
+    w = np.ascontiguousarray(words, dtype=np.uint32).reshape(-1, 3)
+    out = np.zeros_like(w)
+    if lib().orc_sampler_map(op, _ptr(w), w.shape[0], _ptr(out)):
+        raise ValueError(f"orc_sampler_map({op}) failed")
+    return out
 
 
 def sun_setup(sun_position=(0.05, 0.3)) -> SunParams:

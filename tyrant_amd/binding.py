@@ -965,6 +965,16 @@ def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: 
     return out
 
 
+def contract_probe(op: int, a: np.ndarray, b: np.ndarray | None = None, device: int = 0) -> np.ndarray:
+    """tyr_vecmath_probe's own ops (32-49: hip/detmath.hpp and the samplers, listed at contract_probe in hip/frame.hip) over
+    (n, 3) arrays of 32-bit words -- float32, or uint32 where the op reads seeds -- into (n, 3) uint32 words"""
+    a, b = (np.ascontiguousarray(x).reshape(-1, 3) for x in (a, a if b is None else b))
+    assert all(x.dtype in (np.float32, np.uint32) for x in (a, b)) and a.shape == b.shape and 32 <= op <= 49
+    out = np.zeros(a.shape, dtype=np.uint32)
+    _check(lib().tyr_vecmath_probe(device, op, _ptr(a), _ptr(b), _ptr(a), a.shape[0], _ptr(out)), "tyr_vecmath_probe")
+    return out
+
+
 # ---- multi-GPU combine (RCCL behind the C ABI) --------------------------------------------------
 
 

@@ -58,7 +58,7 @@ constexpr double kPio2Lo = 0x1.0b4611a626331p-34;
 constexpr double kSqrt2 = 0x1.6a09e667f3bcdp+0;
 
 // round to nearest even; rint lowers to v_rndne_f64 and equals the 1.5*2^52 add/subtract
-// trick for every |t| < 2^51
+// trick for every |t| < 2^51 in magnitude; it keeps t's sign where the result is a zero (the oracle's dm_round copies it)
 __device__ __forceinline__ double rne(double t) { return __builtin_rint(t); }
 __device__ __forceinline__ double pow2i(int k) { return __longlong_as_double((long long)(k + 1023) << 52); }
 

@@ -373,13 +373,143 @@ __global__ void __launch_bounds__(kBlock) k_resolve(const float4* __restrict__ b
 // ======================================================================================
 // tyr_vecmath_probe: hip/vecmath.hpp (and the deterministic pow / exp) evaluated ON THE DEVICE over arrays, so that the
 // functions every kernel is built from can be pinned to the vendored glm's answers (tests/golden/ref_glm.npz).
-// Same op codes as oracle/ref_harness.cpp ref_glm.
+// Ops 0-19: the op codes of oracle/ref_harness.cpp ref_glm.
 // ======================================================================================
+// Ops >= 32 are the project's own (no glm counterpart): the numeric contract's functions (hip/detmath.hpp) with the binary64
+// values they round, and the samplers of device_common.hpp, against the oracle's orc_dm_map / orc_sampler_map (DESIGN.md
+// section 2).  Three 32-bit WORDS per element, so that binary64 values (low word first) and seeds pass as bit patterns.  Each
+// op restates the function's own lines with the function's own building blocks; a value the function does not reach for this
+// argument (an early return) is 0.
+__device__ __forceinline__ void put64(uint32_t* w, double v) {
+	const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+	w[1] = (uint32_t)u;
+	w[2] = (uint32_t)(u >> 32);
+}
+__device__ void contract_probe(int op, f3 A, f3 B, uint32_t seedWord, uint32_t* __restrict__ w) {
+	const float x = A.x;
+	w[0] = w[1] = w[2] = 0u;
+	switch (op) {
+	case 32:   // sinf_det: [result, r]
+	case 33:   //           [q, the binary64 value that is rounded]
+	case 34:   // cosf_det: [result, r]
+	case 35: { //           [q, the binary64 value that is rounded]
+		const bool isSin = op < 34;
+		if (!(op & 1))
+			w[0] = __float_as_uint(isSin ? dm::sinf_det(x) : dm::cosf_det(x));
+		if (!(fabsf(x) < 1048576.0f))
+			break;
+		int q;
+		const double r = dm::reduce_pio2((double)x, q);
+		if (!(op & 1)) {
+			put64(w, r);
+			break;
+		}
+		w[0] = (uint32_t)q;
+		if (isSin) {
+			const double s = (q & 1) ? dm::cos_poly(r) : dm::sin_poly(r);
+			put64(w, (q & 2) ? -s : s);
+		} else {
+			const double c = (q & 1) ? dm::sin_poly(r) : dm::cos_poly(r);
+			put64(w, ((q + 1) & 2) ? -c : c);
+		}
+		break;
+	}
+	case 36: { // sincosf_det: [sin, cos, 0]
+		float s, c;
+		dm::sincosf_det(x, s, c);
+		w[0] = __float_as_uint(s);
+		w[1] = __float_as_uint(c);
+		break;
+	}
+	case 37:   // expf_det: [result, kd]
+	case 38:   //           [0, r]
+	case 39: { //           [0, exp_poly(r) * pow2i(kd)]
+		if (op == 37)
+			w[0] = __float_as_uint(dm::expf_det(x));
+		const double xd = (double)x;
+		if (x != x || xd > 89.0 || xd < -104.0)
+			break;
+		const double kd = dm::rne(xd * dm::kLog2e);
+		const double r = (xd - kd * dm::kLn2Hi) - kd * dm::kLn2Lo;
+		put64(w, op == 37 ? kd : op == 38 ? r : dm::exp_poly(r) * dm::pow2i((int)kd));
+		break;
+	}
+	case 40:   // powf_det(A.x, B.x): [result, log2_det(x)]
+	case 41:   //                     [0, t]
+	case 42:   //                     [0, w]
+	case 43: { //                     [0, exp_poly(w) * pow2i(kd)]
+		const float y = B.x;
+		if (op == 40)
+			w[0] = __float_as_uint(dm::powf_det(x, y));
+		if (y != y || !(x > 0.0f) || x == __builtin_inff())
+			break;
+		const double l2 = dm::log2_det((double)x);
+		const double t = (double)y * l2;
+		if (op <= 41) {
+			put64(w, op == 40 ? l2 : t);
+			break;
+		}
+		if (t > 129.0 || t < -152.0)
+			break;
+		const double kd = dm::rne(t);
+		const double ww = (t - kd) * dm::kLn2;
+		put64(w, op == 42 ? ww : dm::exp_poly(ww) * dm::pow2i((int)kd));
+		break;
+	}
+	case 44: { // seed = the word at A.x: [rng_float, seed after, rng_int_0_max(16) from the same seed]
+		uint32_t s = seedWord, s2 = s;
+		w[0] = __float_as_uint(rng_float(s));
+		w[1] = s;
+		w[2] = (uint32_t)rng_int_0_max(s2, 16);
+		break;
+	}
+	case 45: { // [rng_float2, seed after, seed after rng_int_0_max(16)]
+		uint32_t s = seedWord, s2 = s;
+		w[0] = __float_as_uint(rng_float2(s));
+		w[1] = s;
+		(void)rng_int_0_max(s2, 16);
+		w[2] = s2;
+		break;
+	}
+	case 46: { // stratified_sample: [sx, sy, seed after]
+		uint32_t s = seedWord;
+		float sx, sy;
+		stratified_sample(s, sx, sy);
+		w[0] = __float_as_uint(sx);
+		w[1] = __float_as_uint(sy);
+		w[2] = s;
+		break;
+	}
+	case 47: { // concentric_sample_disk(A.x, A.y): [dx, dy, 0]
+		float dx, dy;
+		concentric_sample_disk(A.x, A.y, dx, dy);
+		w[0] = __float_as_uint(dx);
+		w[1] = __float_as_uint(dy);
+		break;
+	}
+	case 48:   // orthonormal_basis_naive(A): u
+	case 49: { //                             v
+		f3 u, v;
+		orthonormal_basis_naive(A, u, v);
+		const f3 r = op == 48 ? u : v;
+		w[0] = __float_as_uint(r.x);
+		w[1] = __float_as_uint(r.y);
+		w[2] = __float_as_uint(r.z);
+		break;
+	}
+	default: break;
+	}
+}
+
 __global__ void __launch_bounds__(kBlock) k_vecmath_probe(int op, const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ c, uint32_t n, float* __restrict__ out) {
 	const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
 	if (i >= n)
 		return;
 	const f3 A = ld3(a + 3 * i), B = ld3(b + 3 * i), Cc = ld3(c + 3 * i);
+	if (op >= 32) {
+		contract_probe(op, A, B, reinterpret_cast<const uint32_t*>(a)[3 * i], reinterpret_cast<uint32_t*>(out) + 3 * i);
+		return;
+	}
 	f3 r = mk3(0.f, 0.f, 0.f);
 	switch (op) {
 	case 0: r.x = dot(A, B); break;

@@ -21,7 +21,7 @@ using namespace tyr::drv;
 extern "C" {
 
 int tyr_vecmath_probe(int32_t device, int32_t op, const float* a, const float* b, const float* c, uint32_t n, float* out) {
-	if (!a || !b || !c || !out || n == 0 || op < 0 || op > 19)
+	if (!a || !b || !c || !out || n == 0 || op < 0 || (op > 19 && op < 32) || op > 49)
 		return TYR_ERR_INVALID;
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
