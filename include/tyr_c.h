@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -557,6 +557,66 @@ typedef struct tyr_nearest_out {
 } tyr_nearest_out;
 int tyr_query_nearest(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 */, const float* max_dist /* n or NULL */, uint32_t flags /* must be 0 */,
                       const tyr_nearest_out* out, void* stream);
+
+/* ---- multi-hit queries (extension) ----------------------------------------------------------------------------------------
+ * "What does this ray go through?" for a caller's batch of rays, against the scene the ctx holds: how many surfaces lie on the
+ * segment, and the nearest max_hits of them in order -- every layer for transparency, X-ray thickness or sensor simulation, the
+ * number of surfaces between two points, and (count odd with TYR_QUERY_TWO_SIDED) whether a point is inside a closed mesh.  The
+ * contract is a set over the triangles the reference's any-hit traversal would test, with no visit order in it.
+ *
+ * All arithmetic is binary32, one operation per operation written, nothing contracted, divisions correctly rounded, glm's
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z,   cross(a, b) = (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y).
+ *
+ * Reached triangles R(ray): with the reference's node array, invDir = 1 / direction and dirIsNeg as bvh.h:216-217 make them, a
+ * node passes when BBox::intersect(origin, invDir, dirIsNeg, tmax) (Bbox.h:38-62) is true -- the bound is the ray's tmax at every
+ * node.  R is the set of the primitives of those leaves all of whose ancestors, and the leaf itself, pass: what
+ * CachedBVH::intersectSimple(ray, tmax) (bvh.h:213-256) would test if it never returned early.
+ *
+ * Value of a (ray, triangle) pair, with vert, e1, e2 from the uploaded record, o the origin and d the direction:
+ *   pvec = cross(d, e2),  det = dot(e1, pvec)
+ *   without TYR_QUERY_TWO_SIDED: no hit when det < 0.0000001f (loader.h:28), side = 0
+ *   with it:                     no hit when fabsf(det) < 0.0000001f, side = det < 0 (1: the ray meets the back face)
+ *   invDet = 1 / det (of the actual det),  tvec = o - vert,  u = dot(tvec, pvec) * invDet,  no hit when u < 0 || u > 1
+ *   qvec = cross(tvec, e1),  v = dot(d, qvec) * invDet,  no hit when v < 0 || u + v > 1,  t = dot(e2, qvec) * invDet
+ * (loader.h:32-45 as written).  For det >= 1e-7 this is tyr_query_closest's triangle test and its uv, bit for bit: the one-sided
+ * hits of a ray are a subset of its two-sided hits, with equal t and uv.  A NaN falls through the comparisons as in the reference
+ * and dies at the accept rule.
+ *
+ * Hit set: H = { i in R : t_i > 1e-3 and (tmax - t_i) > 1e-3 } (bvh.h:229).
+ *
+ * Answer, per ray: count = |H| -- every hit in range, NOT capped by max_hits -- and back_count = its members with side 1.  The
+ * min(max_hits, |H|) smallest pairs (t_i, i) in lexicographic order go into the ray's row, nearest first: of bit-equal t the
+ * lower build-order index comes first.  Unused entries of the row: t = tmax as given, prim = -1, uv = (0, 0), side = 0.  A ray
+ * with a NaN or infinite origin or direction component has count = back_count = 0 and a row of unused entries; a scene without
+ * triangles answers every ray that way.  There is no distance pruning: the definition has none and count needs the whole
+ * segment -- a caller bounds the work with tmax.  Surfaces closer together than 1e-3 are all listed (peeling with repeated
+ * closest-hit calls loses them to the accept rule, and pays one traversal per layer).
+ *
+ * Scope of the guarantee: trees whose boxes are exact nested unions (a parent's box is the union of its children's, a leaf's
+ * of its triangles' boxes) -- those of tyr_bvh_build, tyr_bvh_build_device, tyr_scene_build_upload and tyr_scene_refit.
+ *
+ * Arrays, streams and state follow tyr_query_nearest: every array pointer is a DEVICE pointer, contiguous, float32 / int32 /
+ * uint32 / uint8, indexed with 64-bit offsets -- origins, directions n x 3; tmax n, or NULL for VERY_FAR (kernel.cu:15).  While
+ * the call runs, a ray's rows of out->t and out->prim are its working buffer.  n up to 2^31 - 1, independent of queue_size;
+ * n == 0: TYR_OK and nothing launched.  The work is enqueued on `stream` (NULL: the ctx's stream); the call uses the ctx's
+ * device, restores the caller's and touches no render state.  A later tyr_scene_refit waits for it, a query issued after a
+ * refit sees the refitted scene, and a traversal stack overflow sets bit 1 of tyr_query_error.
+ * TYR_ERR_INVALID: ctx, origins, directions, out, out->count, out->t or out->prim NULL, n >= 2^31, max_hits 0 or above
+ * TYR_QUERY_HITS_MAX, or a flag other than TYR_QUERY_TWO_SIDED (TYR_QUERY_SPHERES included: the sphere table is not part of it);
+ * TYR_ERR_NO_SCENE: nothing uploaded.
+ * Not part of it: spheres, distance pruning, more than TYR_QUERY_HITS_MAX entries per ray, signed distance as a call. */
+#define TYR_QUERY_TWO_SIDED 2u   /* tyr_query_hits only */
+#define TYR_QUERY_HITS_MAX 32
+typedef struct tyr_hits_out {
+	uint32_t* count;       /* n, required: |H|, every hit in range, not capped by max_hits */
+	float*    t;           /* n x max_hits, required */
+	int32_t*  prim;        /* n x max_hits, required: build-order index, -1 = unused entry */
+	float*    uv;          /* n x max_hits x 2, or NULL */
+	uint8_t*  side;        /* n x max_hits, or NULL: 0 front, 1 back */
+	uint32_t* back_count;  /* n, or NULL: members of H with side 1 */
+} tyr_hits_out;
+int tyr_query_hits(tyr_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* tmax /* n or NULL = VERY_FAR */, uint32_t max_hits, uint32_t flags,
+                   const tyr_hits_out* out, void* stream);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

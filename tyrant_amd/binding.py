@@ -29,6 +29,8 @@ TYR_ERR_NO_SCENE = -3
 TYR_ERR_DEVICE = -6
 TYR_ERR_UNSUPPORTED = -7
 TYR_QUERY_SPHERES = 1
+TYR_QUERY_TWO_SIDED = 2  # tyr_query_hits only
+TYR_QUERY_HITS_MAX = 32
 AOV_CHAIN_MAX = 8  # TYR_AOV_CHAIN_MAX
 TYR_REFIT_DEVICE = 1
 TYR_DENOISE_RESOLVE = 1
@@ -126,6 +128,12 @@ class NearestOut(C.Structure):
     """tyr_nearest_out: device pointers of tyr_query_nearest's outputs; uv, region, point may be NULL"""
 
     _fields_ = [("dist2", P), ("prim", P), ("uv", P), ("region", P), ("point", P)]
+
+
+class HitsOut(C.Structure):
+    """tyr_hits_out: device pointers of tyr_query_hits's outputs; uv, side, back_count may be NULL"""
+
+    _fields_ = [("count", P), ("t", P), ("prim", P), ("uv", P), ("side", P), ("back_count", P)]
 
 
 class AovChainOut(C.Structure):
@@ -268,6 +276,7 @@ SYMBOLS = {
     "tyr_query_any": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
     "tyr_query_nearest": (C.c_int, [P, c_u32, P, P, c_u32, P, P]),
+    "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
     "tyr_render_aov_chain": (C.c_int, [P, c_u32, c_u32, P, P, P]),
@@ -715,6 +724,33 @@ class Renderer:
         self._on_stream(stream, lambda h: self.L.tyr_query_nearest(self.h, n, p.data_ptr(), mp, 0, C.byref(out), h), staged)
         self._query_finish()
         return dist2, prim, uv, region, point
+
+    def query_hits(self, origins, directions, tmax=None, max_hits=4, two_sided=False, stream=None):
+        """tyr_query_hits: every surface a ray goes through within (1e-3, tmax - 1e-3) (include/tyr_c.h "Multi-hit queries").
+        origins, directions: (N, 3) float32, tmax: (N,) or None (VERY_FAR) -- torch tensors on this ctx's device, taken as they are,
+        or numpy arrays.  Returns torch tensors (count, t, prim, uv, side, back_count): count (N,) int32 (the
+        library's uint32), the number of hits in range (not capped by max_hits); t, prim, side (N, max_hits) and uv (N, max_hits, 2) the nearest
+        max_hits of them, nearest first, of equal t the lower build-order index first -- unused entries hold t = tmax, prim = -1,
+        uv = (0, 0), side = 0; back_count (N,) the hits met from behind (two_sided=True; side 1).  Inside a closed mesh: count odd
+        with two_sided=True."""
+        import torch
+
+        if not 1 <= int(max_hits) <= TYR_QUERY_HITS_MAX:
+            raise ValueError(f"max_hits: 1 .. {TYR_QUERY_HITS_MAX}")
+        k = int(max_hits)
+        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        t = torch.empty((n, k), dtype=torch.float32, device=dev)
+        prim = torch.empty((n, k), dtype=torch.int32, device=dev)
+        uv = torch.empty((n, k, 2), dtype=torch.float32, device=dev)
+        side = torch.empty((n, k), dtype=torch.uint8, device=dev)
+        back = torch.empty(n, dtype=torch.int32, device=dev)
+        out = HitsOut(count.data_ptr(), t.data_ptr(), prim.data_ptr(), uv.data_ptr(), side.data_ptr(), back.data_ptr())
+        flags = TYR_QUERY_TWO_SIDED if two_sided else 0
+        tp = tm.data_ptr() if tm is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_hits(self.h, n, o.data_ptr(), d.data_ptr(), tp, k, flags, C.byref(out), h), staged)
+        self._query_finish()
+        return count, t, prim, uv, side, back
 
     def render_aov(self, spp, albedo=True, normal=True, depth=True, ids=True, stream=None, max_chain=None) -> dict:
         """tyr_render_aov: first-hit guide buffers of the current camera at the current frame counter, spp camera rays per pixel
