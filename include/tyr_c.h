@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -547,7 +547,7 @@ int tyr_query_error(tyr_ctx* ctx, uint32_t* bits_out, int reset);
  * refitted scene, and a traversal stack overflow sets bit 1 of tyr_query_error.
  * TYR_ERR_INVALID: ctx, points, out, out->dist2 or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
  * Not part of it: the sphere table (flags must be 0), signed distance (region is what a caller needs to pick a face, edge or
- * vertex pseudo-normal itself), k nearest. */
+ * vertex pseudo-normal itself).  The k nearest and all triangles within a radius: tyr_query_nearest_k below. */
 typedef struct tyr_nearest_out {
 	float*   dist2;  /* n, required */
 	int32_t* prim;   /* n, required: build-order index as tyr_query_closest's prim, -1 = none */
@@ -557,6 +557,47 @@ typedef struct tyr_nearest_out {
 } tyr_nearest_out;
 int tyr_query_nearest(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 */, const float* max_dist /* n or NULL */, uint32_t flags /* must be 0 */,
                       const tyr_nearest_out* out, void* stream);
+
+/* ---- k-nearest queries (extension) -----------------------------------------------------------------------------------------
+ * "Which triangles are within r of this point, and which k of them are nearest?" for a caller's batch of points, against the
+ * scene the ctx holds: contact candidates for collision (with tyr_scene_refit), every triangle around a closest edge or vertex
+ * (tyr_query_nearest names only the lowest index of a tie), and the number of surfaces near a point.  The contract is a set
+ * over all triangles of the uploaded array with no traversal order in it.
+ *
+ * Per (point, triangle) pair everything is the "Closest-point queries" block's above, operation by operation: the value F_i,
+ * its (u2, v2), region and closest point c; per point bound2 = max_dist * max_dist, +inf when max_dist is NULL, and the rules
+ * for an invalid point or max_dist.
+ *
+ * Member set, per point: W = { i : F_i < bound2 } -- strict; a pair whose F is NaN is not a member.
+ * Answer, per point: count = |W| (written when out->count is not NULL) -- every member, NOT capped by k; with max_dist NULL the
+ * number of triangles with a finite F, so a caller bounds the work with max_dist.  The min(k, |W|) smallest pairs (F_i, i) in
+ * lexicographic order go into the point's row, nearest first: of bit-equal values the lower build-order index comes first.
+ *   a kept entry:                  dist2 = F_i, prim = i, uv = (u2, v2), region, point = c of that pair
+ *   an unused entry:               dist2 = bound2, prim = -1, uv = (0, 0), region = 0, point = p
+ *   invalid point or max_dist:     count = 0, every entry unused with dist2 = +inf
+ * A scene without triangles answers every point with unused entries and count = 0.
+ * It follows that with k == 1 dist2, prim, uv, region and point are tyr_query_nearest's, bit for bit; that the row for k is the
+ * first k entries of the row for any larger k; and that asking for count or not makes no difference to the row.
+ *
+ * Scope of the guarantee, arrays (DEVICE pointers, contiguous, indexed with 64-bit offsets), n up to 2^31 - 1 and n == 0,
+ * streams, the device, "touches no render state", tyr_scene_refit and bit 1 of tyr_query_error are tyr_query_nearest's: points
+ * n x 3; max_dist n or NULL; out->dist2, out->prim n x k (required); out->count n, out->uv n x k x 2, out->region n x k,
+ * out->point n x k x 3 (each may be NULL).  While the call runs, a point's rows of out->dist2 and out->prim are its working
+ * buffer.  Without a count the search is pruned by the k-th value found so far; with it, by bound2 alone.
+ * TYR_ERR_INVALID: ctx, points, out, out->dist2 or out->prim NULL, n >= 2^31, k 0 or above TYR_QUERY_NEAREST_K_MAX, or
+ * flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
+ * Not part of it: the sphere table, signed distance, more than TYR_QUERY_NEAREST_K_MAX entries per point, approximate search. */
+#define TYR_QUERY_NEAREST_K_MAX 32
+typedef struct tyr_nearest_k_out {
+	float*    dist2;   /* n x k, required */
+	int32_t*  prim;    /* n x k, required: build-order index, -1 = unused entry */
+	uint32_t* count;   /* n, or NULL: |W|, every triangle inside the bound, not capped by k */
+	float*    uv;      /* n x k x 2, or NULL */
+	uint8_t*  region;  /* n x k, or NULL */
+	float*    point;   /* n x k x 3, or NULL */
+} tyr_nearest_k_out;
+int tyr_query_nearest_k(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 */, const float* max_dist /* n or NULL */,
+                        uint32_t k, uint32_t flags /* must be 0 */, const tyr_nearest_k_out* out, void* stream);
 
 /* ---- multi-hit queries (extension) ----------------------------------------------------------------------------------------
  * "What does this ray go through?" for a caller's batch of rays, against the scene the ctx holds: how many surfaces lie on the

@@ -31,6 +31,7 @@ TYR_ERR_UNSUPPORTED = -7
 TYR_QUERY_SPHERES = 1
 TYR_QUERY_TWO_SIDED = 2  # tyr_query_hits only
 TYR_QUERY_HITS_MAX = 32
+TYR_QUERY_NEAREST_K_MAX = 32
 AOV_CHAIN_MAX = 8  # TYR_AOV_CHAIN_MAX
 TYR_REFIT_DEVICE = 1
 TYR_DENOISE_RESOLVE = 1
@@ -128,6 +129,12 @@ class NearestOut(C.Structure):
     """tyr_nearest_out: device pointers of tyr_query_nearest's outputs; uv, region, point may be NULL"""
 
     _fields_ = [("dist2", P), ("prim", P), ("uv", P), ("region", P), ("point", P)]
+
+
+class NearestKOut(C.Structure):
+    """tyr_nearest_k_out: device pointers of tyr_query_nearest_k's outputs; count, uv, region, point may be NULL"""
+
+    _fields_ = [("dist2", P), ("prim", P), ("count", P), ("uv", P), ("region", P), ("point", P)]
 
 
 class HitsOut(C.Structure):
@@ -276,6 +283,7 @@ SYMBOLS = {
     "tyr_query_any": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
     "tyr_query_nearest": (C.c_int, [P, c_u32, P, P, c_u32, P, P]),
+    "tyr_query_nearest_k": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
@@ -724,6 +732,38 @@ class Renderer:
         self._on_stream(stream, lambda h: self.L.tyr_query_nearest(self.h, n, p.data_ptr(), mp, 0, C.byref(out), h), staged)
         self._query_finish()
         return dist2, prim, uv, region, point
+
+    def query_nearest_k(self, points, k, max_dist=None, count=False, stream=None):
+        """tyr_query_nearest_k: for every point the k nearest triangles of the uploaded scene inside max_dist (include/tyr_c.h
+        "k-nearest queries").  points: (N, 3) float32, max_dist: (N,) or None -- torch tensors on this ctx's device, taken as they
+        are, or numpy arrays.  Returns torch tensors (dist2, prim, uv, region, point) of shapes (N, k), (N, k), (N, k, 2), (N, k),
+        (N, k, 3): nearest first, of equal dist2 the lower build-order index first -- unused entries hold dist2 = max_dist^2 (+inf
+        for an invalid point or max_dist), prim = -1, uv = (0, 0), region = 0 and point = the query point.  With count=True a
+        sixth tensor (N,) int32 (the library's uint32): every triangle inside max_dist, not capped by k -- the search is then
+        pruned by max_dist alone, so give one."""
+        import torch
+
+        if not 1 <= int(k) <= TYR_QUERY_NEAREST_K_MAX:
+            raise ValueError(f"k: 1 .. {TYR_QUERY_NEAREST_K_MAX}")
+        k = int(k)
+        dev = torch.device("cuda", self.device)
+        take = self._query_take
+        staged = not all(isinstance(a, torch.Tensor) for a in (points, max_dist) if a is not None)
+        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
+        n = p.shape[0] if p.ndim == 2 else -1
+        p = take(p, "points", (n, 3))
+        md = take(max_dist, "max_dist", (n,)) if max_dist is not None else None
+        dist2 = torch.empty((n, k), dtype=torch.float32, device=dev)
+        prim = torch.empty((n, k), dtype=torch.int32, device=dev)
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if count else None
+        uv = torch.empty((n, k, 2), dtype=torch.float32, device=dev)
+        region = torch.empty((n, k), dtype=torch.uint8, device=dev)
+        point = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
+        out = NearestKOut(dist2.data_ptr(), prim.data_ptr(), cnt.data_ptr() if count else None, uv.data_ptr(), region.data_ptr(), point.data_ptr())
+        mp = md.data_ptr() if md is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_nearest_k(self.h, n, p.data_ptr(), mp, k, 0, C.byref(out), h), staged)
+        self._query_finish()
+        return (dist2, prim, uv, region, point, cnt) if count else (dist2, prim, uv, region, point)
 
     def query_hits(self, origins, directions, tmax=None, max_hits=4, two_sided=False, stream=None):
         """tyr_query_hits: every surface a ray goes through within (1e-3, tmax - 1e-3) (include/tyr_c.h "Multi-hit queries").
