@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -359,9 +359,31 @@ enum {
 	TYR_TUNE_SCAN_IN_TRACE = 25,     /* tyr_render one iteration ahead of the counts (TYR_TUNE_RUN_AHEAD), with TYR_TUNE_FOLD_PROLOGUE: 1 (default) = once the primary budget is spent, an iteration's slot scan -- whose tables only the NEXT shade launch reads -- is not a launch of its own: the shade launch's last block opens the next iteration (set_wavefront_globals, kernel.cu:227-244, and the padding of the queue segments' ends) and that iteration's traversal launch does the scan on its way in, a wave per 16384 slots; 0 = a k_scan_words launch in front of the traversal launch, opening the iteration itself */
 	TYR_TUNE_KERNEL_SNAPSHOT = 26,   /* tyr_render one iteration ahead of the counts (TYR_TUNE_RUN_AHEAD): 1 (default) = the counts the host's loop waits for (survivors, shadow rays, the error word) are written to pinned host memory by the shade launch's last block and the host polls their stamp -- no copy and no event in the stream between an iteration's shade launch and the next traversal launch; 0 = a copy of the counters behind the shade launch + an event */
 	TYR_TUNE_STAGE_TIMING = 27,      /* with TYR_FLAG_PROFILE: 0 (default) = a hipEventRecord in front of and behind every timed stage; 1 = the stage's start / stop events are attached to its own launches (hipExtLaunchKernelGGL): no marker packet between two kernels and a stage time without the packets' share -- but a dispatch that reports time stamps idles the GPU about as long as the pair did, so it is not the default */
+	TYR_TUNE_PRIMARY_OVERLAP = 28,   /* merged path of tyr_render: 1 (default) = a top-up of camera rays is made in two parts: the rays whose pixel lies in the camera window (tyr_primary_window: the only ones that can enter the tree) in front of the iteration's traversal launch, all the others beside it on a second, lowest-priority stream of the ctx; 0 = one k_primary in front of the traversal launch */
+	TYR_TUNE_OVERLAP_TRACE_BLOCKS = 29, /* ... the traversal launch of such an iteration runs this many 256-thread blocks per CU (3..5, default 3) instead of what the occupancy query admits, so that the second part has registers, wave slots and LDS to be resident beside it: for that one launch this key stands in for TYR_TUNE_WAVES_PER_SIMD, and TYR_TUNE_WIDE_BLOCK_MIN_ITEMS does not apply (no 768-thread blocks); every other launch keeps the caller's values */
+	TYR_TUNE_OVERLAP_MIN_NEW = 30,   /* ... only top-ups of at least this many rays, and at least four times the survivors they join (the host's upper bounds), are made in two parts: beside a traversal launch fat with survivors the second part only slows it; default 1 Mi, 0 = every top-up */
+	TYR_TUNE_WINDOW_INSET = 31,      /* test only: the camera window shrunk by this many pixels on every side (default 0), so that rays which do enter the tree lie outside it and the second part has to trace them itself (tyr_primary_window_info.strays) */
 	TYR_TUNE_FOLD_SPHERES = 19       /* merged path of tyr_render: 1 (default) = shade does the sphere pre-passes' work (kernel.cu:127-136, 168-172) for the rays it emits, while they are in registers; 0 = the pre-pass kernels re-read them */
 };
 int tyr_set_tuning(tyr_ctx* ctx, int key, int value);
+
+/* The camera window: the pixel rectangle [x0, x1) x [y0, y1) outside which no camera ray of the ctx's camera is expected to pass
+ * the root box of the scene's tree -- the box's eight corners through the pinhole projection, widened by the jitter's pixel and one
+ * more (TYR_TUNE_PRIMARY_OVERLAP schedules a top-up by it).  whole_frame: the window is the whole frame -- a thin lens, a camera
+ * inside the box, a corner on or behind the camera plane, a box out of the picture, no tree.  local_y0 / local_y1: the window's rows
+ * among the rank's own (y = local * nranks + rank).  strays: camera rays made outside the window that passed the root box all the
+ * same and were traced where they were made, since tyr_create (as of the last completed render); results never depend on it.
+ * splits: top-ups that tyr_render launched in two parts since tyr_create (an iteration queued ahead for nothing included). */
+typedef struct tyr_primary_window_info {
+	uint32_t x0, x1, y0, y1;
+	uint32_t local_y0, local_y1;
+	uint32_t whole_frame;
+	uint32_t strays;
+	uint32_t splits;
+} tyr_primary_window_info;
+int tyr_primary_window(tyr_ctx* ctx, tyr_primary_window_info* out);
+/* ... the same for any camera, frame, sharding and root box, without a ctx or a device (strays, splits: 0) */
+int tyr_primary_window_probe(const tyr_camera* cam, uint32_t width, uint32_t height, uint32_t rank, uint32_t nranks, const float root_min[3], const float root_max[3], int inset, tyr_primary_window_info* out);
 
 /* ---- multi-GPU: the frame's rows are dealt y % nranks == rank (tyr_config.rank / nranks) --------------------
  * The reference is single-GPU (main.cpp:94 computes `multi_gpu` and never uses it); BASELINE.json's north_star makes

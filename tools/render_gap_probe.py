@@ -2,7 +2,9 @@
 outside the kernels, without a profiler: `steps` times set_frame + reset_accum + render (1080p, 8 spp, the C3 mesh), the host
 clock around each of the three calls, and -- profile=1, every stage bracketed for it -- the stages' summed time from timings()
 in a second pass, so that `ms per step - kernel ms per step` is the time per step in which no stage of ours ran.
-mask: the stages the first pass times (bench.py's timed region keeps TYR_K_EXTEND | TYR_K_CONNECT = 10)."""
+mask: the stages the first pass times (bench.py's timed region keeps TYR_K_EXTEND | TYR_K_CONNECT = 10).
+The second pass runs with primary_overlap=0: with a top-up in two parts TYR_K_PRIMARY (window part's start to rest part's end) runs
+beside TYR_K_EXTEND and the stages' sum would count that time twice."""
 import os
 import statistics
 import sys
@@ -58,10 +60,10 @@ if profile:
     timed = {k: (v["ms"] / steps, v["launches"] / steps) for k, v in tm.items() if v["launches"]}
     print("  stages timed in this pass (ms per step, launches per step):", {k: (round(a, 4), b) for k, (a, b) in timed.items()})
     # second pass: every stage bracketed, for the kernels' own time per step (the brackets themselves stretch the step, not the stages)
-    g.set_tuning(profile_mask=31)
+    g.set_tuning(profile_mask=31, primary_overlap=0)  # (stages that follow one another: their sum is the kernels' time)
     g.timings(reset=True)
     ms_all, _ = run(steps)
     tm = g.timings(reset=True)
     busy = sum(v["ms"] for v in tm.values()) / steps
-    print(f"  all stages bracketed: {ms_all * 1e3:.4f} ms per step, stages' sum {busy:.4f} ms per step:", {k: round(v["ms"] / steps, 4) for k, v in tm.items() if v["launches"]})
+    print(f"  all stages bracketed, primary_overlap=0: {ms_all * 1e3:.4f} ms per step, stages' sum {busy:.4f} ms per step:", {k: round(v["ms"] / steps, 4) for k, v in tm.items() if v["launches"]})
     print(f"  first pass's step - stages' sum = {ms_step * 1e3 - busy:.4f} ms per step with no stage running (boundaries inside the render + between renders + the 33 MB clear)")

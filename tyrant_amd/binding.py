@@ -210,6 +210,10 @@ class AllocateParams(C.Structure):
     _fields_ = [("total", c_u64), ("min_spp", c_u32), ("max_spp", c_u32)]
 
 
+class PrimaryWindowInfo(C.Structure):
+    _fields_ = [("x0", c_u32), ("x1", c_u32), ("y0", c_u32), ("y1", c_u32), ("local_y0", c_u32), ("local_y1", c_u32), ("whole_frame", c_u32), ("strays", c_u32), ("splits", c_u32)]
+
+
 class Timings(C.Structure):
     _fields_ = [("ms", C.c_double * 5), ("launches", c_u64 * 5)]
 
@@ -256,6 +260,8 @@ SYMBOLS = {
     "tyr_sun_setup": (C.c_int, [C.c_float, C.c_float, P]),
     "tyr_camera_handle_input": (C.c_int, [P, P, C.c_double]),
     "tyr_get_timings": (C.c_int, [P, C.POINTER(Timings), C.c_int]),
+    "tyr_primary_window": (C.c_int, [P, C.POINTER(PrimaryWindowInfo)]),
+    "tyr_primary_window_probe": (C.c_int, [C.POINTER(CameraC), c_u32, c_u32, c_u32, c_u32, C.POINTER(c_f), C.POINTER(c_f), C.c_int, C.POINTER(PrimaryWindowInfo)]),
     "tyr_set_tuning": (C.c_int, [P, C.c_int, C.c_int]),
     "tyr_bvh_build": (C.c_int, [P, c_i32, P, P, c_i32]),
     "tyr_bvh_build_device": (C.c_int, [c_i32, P, c_i32, P, P, P]),
@@ -509,12 +515,19 @@ class Renderer:
         _check(self.L.tyr_get_counters(self.h, C.byref(k)), "tyr_get_counters")
         return k.asdict()
 
+    def primary_window(self) -> dict:
+        """The camera window of the current camera and scene (tyr_primary_window): x0, x1, y0, y1, local_y0, local_y1, whole_frame, strays, splits."""
+        w = PrimaryWindowInfo()
+        _check(self.L.tyr_primary_window(self.h, C.byref(w)), "tyr_primary_window")
+        return {k: int(getattr(w, k)) for k, _ in w._fields_}
+
     def timings(self, reset=False) -> dict:
         t = Timings()
         _check(self.L.tyr_get_timings(self.h, C.byref(t), int(reset)), "tyr_get_timings")
         return {n: {"ms": t.ms[i], "launches": int(t.launches[i])} for i, n in enumerate(KERNEL_NAMES)}
 
-    TUNING_KEYS = {"refill_min_idle": 1, "waves_per_simd": 2, "min_traversing": 4, "ticket_chunk": 5, "static_share": 8, "staged_nodes": 9, "profile_mask": 11, "merge_trace": 12, "static_interleave": 13, "run_ahead": 14, "wide_drain": 15, "fold_spheres": 19, "retire_sky": 20, "resolve_shadows": 21, "wide_block_min_items": 22, "fold_prologue": 23, "layout_on_device": 24, "scan_in_trace": 25, "kernel_snapshot": 26, "stage_timing": 27}
+    TUNING_KEYS = {"refill_min_idle": 1, "waves_per_simd": 2, "min_traversing": 4, "ticket_chunk": 5, "static_share": 8, "staged_nodes": 9, "profile_mask": 11, "merge_trace": 12, "static_interleave": 13, "run_ahead": 14, "wide_drain": 15, "fold_spheres": 19, "retire_sky": 20, "resolve_shadows": 21, "wide_block_min_items": 22, "fold_prologue": 23, "layout_on_device": 24, "scan_in_trace": 25, "kernel_snapshot": 26, "stage_timing": 27,
+                   "primary_overlap": 28, "overlap_trace_blocks": 29, "overlap_min_new": 30, "window_inset": 31}
 
     def set_tuning(self, **knobs):
         for name, v in knobs.items():
@@ -1097,6 +1110,15 @@ def cone_probe(sun_position, seed: int, n: int, device: int = 0):
     out = np.zeros(3 * n + 1, dtype=np.float32)
     _check(lib().tyr_sunsky_probe(device, float(sun_position[0]), float(sun_position[1]), 3, _ptr(inp), n, _ptr(out)), "tyr_sunsky_probe")
     return out[: 3 * n].reshape(n, 3).copy(), int(out[3 * n : 3 * n + 1].view(np.uint32)[0])
+
+
+def primary_window_probe(cam, width: int, height: int, root_min, root_max, rank: int = 0, nranks: int = 1, inset: int = 0) -> dict:
+    """The camera window (tyr_primary_window_probe) of any camera, frame, sharding and root box; no ctx, no device."""
+    f3 = lambda x: (c_f * 3)(*[float(v) for v in x])  # noqa: E731
+    c = CameraC(f3(cam.position), f3(cam.direction), f3(cam.up), cam.focalDistance, cam.lensRadius)
+    w = PrimaryWindowInfo()
+    _check(lib().tyr_primary_window_probe(C.byref(c), width, height, rank, nranks, f3(root_min), f3(root_max), inset, C.byref(w)), "tyr_primary_window_probe")
+    return {k: int(getattr(w, k)) for k, _ in w._fields_}
 
 
 def dist_unique_id() -> bytes:

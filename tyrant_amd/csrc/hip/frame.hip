@@ -9,51 +9,160 @@ namespace tyr {
 // ======================================================================================
 // primary_rays, kernel.cu:247-297.  One thread per new queue slot.
 // ======================================================================================
-__global__ void __launch_bounds__(kBlock) k_primary(const FrameParams P) {
-	__shared__ uint32_t baseSh[kClasses], cntSh[8], lastSh;
-	const uint32_t index = blockIdx.x * kBlock + threadIdx.x;
-	const uint32_t cnt = P.k->primary_ray_cnt; // survivors already in the buffer (kernel.cu:253)
-	const unsigned long long room = (unsigned long long)(P.N - cnt);
-	const unsigned long long budget = P.k->budget_remaining;
-	const uint32_t nNew = (uint32_t)(room < budget ? room : budget);
-	const bool mine = index < nNew; // (a launch with nothing to generate is one block that only runs the globals below)
-	const uint32_t vslot = index + cnt; // the slot the serial order gives this ray (kernel.cu:254): what seeds its shading
-	uint32_t seed = camera_seed(P, index);
+// Three kernels share the body.  k_primary makes a whole top-up.  k_primary_window and k_primary_rest make it in two parts
+// (DESIGN.md 4.8 (6)): the rays whose pixel lies in the camera window -- the only ones that can pass the root box, so the
+// only ones the iteration's traversal launch reads -- and, beside that launch on a second stream, all the others.  A ray is
+// the same ray whichever kernel makes it: its ticket `index` gives it its seed, its pixel and its virtual slot.
+enum : int { kPrimaryWhole = 0, kPrimaryWindow = 1, kPrimaryRest = 2 };
 
-	const uint32_t start = P.k->start_position;
-	const int x = (int)((start + index) % P.W);
-	const int yl = (int)(((start + index) / P.W) % P.localRows);
-	const int y = yl * (int)P.nranks + (int)P.rank; // nranks == 1: kernel.cu:264
-
-	const CameraRay cr = camera_lens(P, seed, camera_focus(P, seed, x, y), ld3(P.camPos), ld3(P.camRight), ld3(P.camUp));
-	const f3 lensPoint = cr.origin, direction = cr.direction;
-
-	// extend's sphere half for this ray, while it is in registers (k_extend_spheres then only has the survivors of the
-	// last iteration to do), and the traversal's own first test (root_ref at the refill of k_trace_flat: same function,
-	// same bound, same answer): a ray that fails it goes to class 1 and is finished with this record
-	const float2 hitRecord = sphere_hit_record(P, lensPoint, direction);
-	const bool tree = mine && P.scene.rootRef != kRefDone && root_ref(P.scene, make_ray(lensPoint, direction), hitRecord.x) != kRefDone;
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	// A camera ray that hits no sphere and fails the root box is finished before it is queued (P.retireSky, tyr_render's
-	// merged path): what shade would do with it is fixed -- kernel.cu:613-617 with the fresh ray's lastSpecular = true and
-	// direct = (1,1,1) (kernel.cu:295, variables.h:33): color = sunsky(direction), one finished path, no survivor, no shadow
-	// ray, and NO random number drawn -- so it is done here, while the direction is in registers: the pixel gets its
-	// radiance (the same operations: 0 + 1 * x is x), the ray's survive byte is 0, and the record is never written or read
-	// (42 % of the first wavefront's rays on C3: 112 bytes of queue traffic and a shade lane each).  Every count stays: the
-	// ray was generated and traced (n_live and the totals are sums, not queue lengths).
-	const bool sky = P.retireSky != 0u && mine && !tree && !(hitRecord.x < kVeryFar);
-	if (__ballot(sky) != 0ull) {
-		f3 radiance = mk3(0.f, 0.f, 0.f);
-		if (sky) {
-			if (P.sun.sunAngularDiameterCos == 1.0f) {
-				radiance = mk3(1.0f, 0.0f, 0.0f); // sunsky.cu:118-119
-			} else {
-				const Atmosphere a = atmosphere(P.sun, direction);
-				radiance = sunsky_radiance(P.sun, a);
+// A ray of k_primary_rest that does pass the root box (the window is a bound the host computed, not something the result may
+// rest on): the traversal launch is already running and does not know of it, so it is traced here -- the quad tree in the
+// reference's visit order with the closest-hit accept rule, as hip/query_common.hpp q_traverse does it -- and queued with its
+// answer.  One ray at a time per wave, on the wave's own 64-entry LDS stack (bvh.h:124): this is a path for a handful of rays.
+// Why a walk of its own and neither of the two there are: bvh_closest (hip/traverse.hpp) walks the PAIR nodes, which a ctx of
+// the merged path does not have on the device (tyr_scene_upload lays them out only for the counting and BVH_DEBUG flags: 64 MB on
+// C3); q_traverse is a wave-wide state machine over LdsStack<12>, 24 KB of LDS per block plus 52 private entries per lane --
+// scratch, and LDS that k_primary_rest's blocks need to fit beside the traversal launch's.  What has to stay in step with those
+// two is the push order (farthest hit first), the pop test and the leaf's accept rule; tests/test_primary_overlap.py holds them to
+// the oracle with the window shrunk, tests/fuzz_primary_overlap.py on random scenes.
+struct WaveStack {
+	uint2* entry;
+	int n;
+	bool overflow;
+	__device__ __forceinline__ void push(bool on, uint32_t r, float t) {
+		if (!on)
+			return;
+		if (n < kStackSize)
+			entry[n++] = make_uint2(r, __float_as_uint(t));
+		else
+			overflow = true;
+	}
+};
+__device__ __forceinline__ float2 trace_stray(const DevScene& sc, uint2* stack, f3 origin, f3 direction, float2 hitRecord, bool& overflow) {
+	const RayConst r = make_ray(origin, direction);
+	WaveStack st{ stack, 0, false };
+	float dist = hitRecord.x;
+	uint32_t ref = sc.quadRootRef;
+	while (ref != kRefDone) {
+		if (ref == kRefPop) {
+			ref = kRefDone;
+			while (st.n > 0) {
+				const uint2 e = st.entry[--st.n];
+				if (__uint_as_float(e.y) < dist) { // the pop-time half of Bbox.h:61
+					ref = e.x;
+					break;
+				}
 			}
-			P.survFlag[vslot] = 0; // what k_shade writes for a ray that does not survive (k_scan_words reads every slot below n_live)
+		} else if ((int)ref >= 0) {
+			const QuadHits h = test_quad<false, true>(sc.quads, ref, r, dist);
+			const bool h0 = lane_in(h.hit[0]), h1 = lane_in(h.hit[1]), h2 = lane_in(h.hit[2]), h3 = lane_in(h.hit[3]);
+			st.push(h3 && (h0 || h1 || h2), h.ref[3], h.t[3]);
+			st.push(h2 && (h0 || h1), h.ref[2], h.t[2]);
+			st.push(h1 && h0, h.ref[1], h.t[1]);
+			ref = h0 ? h.ref[0] : h1 ? h.ref[1] : h2 ? h.ref[2] : h3 ? h.ref[3] : kRefPop;
+		} else { // a leaf: bvh.h:129-140
+			const uint32_t off = ref & (kMaxPrimOffset - 1);
+			const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
+			for (uint32_t i = 0; i < cnt; ++i) {
+				const float t = triangle_test(triangle_load(sc.tris, off + i), r);
+				if (t > kEpsilon && t < dist && ((dist - t) > kEpsilon)) {
+					hitRecord = make_float2(t, __uint_as_float(off + i));
+					dist = t;
+				}
+			}
+			ref = kRefPop;
 		}
-		accumulate_pixels_wave(P.blit, y * (int)P.W + x, radiance, sky ? 1 : 0);
+	}
+	overflow = overflow || st.overflow;
+	return hitRecord;
+}
+
+template <int PART>
+__device__ __forceinline__ void primary_rays(const FrameParams& P, const PrimaryWindow& win) {
+	__shared__ uint32_t baseSh[kClasses], cntSh[8], lastSh;
+	__shared__ uint2 strayStack[PART == kPrimaryRest ? (kBlock / 64) * kStackSize : 1];
+	uint32_t index = blockIdx.x * kBlock + threadIdx.x;
+	uint32_t cnt, nNew, start;
+	if (PART == kPrimaryRest) {
+		cnt = P.k->plan_cnt, nNew = P.k->plan_new, start = P.k->plan_start;
+	} else {
+		cnt = P.k->primary_ray_cnt; // survivors already in the buffer (kernel.cu:253)
+		const unsigned long long room = (unsigned long long)(P.N - cnt);
+		const unsigned long long budget = P.k->budget_remaining;
+		nNew = (uint32_t)(room < budget ? room : budget);
+		start = P.k->start_position;
+	}
+	bool mine; // (a launch with nothing to generate is one block that only runs the globals below)
+	int x, yl;
+	if (PART == kPrimaryWindow) {
+		// thread -> (sweep over the rank's rows, row of the window, column of the window) -> the ticket that has this pixel
+		const uint32_t ww = win.x1 - win.x0, per = ww * (win.yl1 - win.yl0);
+		const uint32_t sweep = index / per, rem = index - sweep * per, row = rem / ww;
+		x = (int)(win.x0 + (rem - row * ww));
+		yl = (int)(win.yl0 + row);
+		const unsigned long long at = (unsigned long long)sweep * P.localPixels + (uint32_t)yl * P.W + (uint32_t)x; // = start + ticket
+		mine = at >= start && at - start < nNew;
+		index = (uint32_t)(at - start);
+	} else {
+		x = (int)((start + index) % P.W);
+		yl = (int)(((start + index) / P.W) % P.localRows);
+		mine = index < nNew;
+		if (PART == kPrimaryRest)
+			mine = mine && !((uint32_t)x >= win.x0 && (uint32_t)x < win.x1 && (uint32_t)yl >= win.yl0 && (uint32_t)yl < win.yl1);
+	}
+	const uint32_t vslot = index + cnt; // the slot the serial order gives this ray (kernel.cu:254): what seeds its shading
+	const int y = yl * (int)P.nranks + (int)P.rank; // nranks == 1: kernel.cu:264
+	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	f3 lensPoint = mk3(0.f, 0.f, 0.f), direction = mk3(0.f, 0.f, 0.f);
+	float2 hitRecord = make_float2(kVeryFar, 0.f);
+	bool tree = false, sky = false;
+	// (the two parts: a wave none of whose lanes has a ray -- the other part's pixels -- has nothing to compute)
+	if (PART == kPrimaryWhole || __ballot(mine) != 0ull) {
+		uint32_t seed = camera_seed(P, index);
+		const CameraRay cr = camera_lens(P, seed, camera_focus(P, seed, x, y), ld3(P.camPos), ld3(P.camRight), ld3(P.camUp));
+		lensPoint = cr.origin, direction = cr.direction;
+
+		// extend's sphere half for this ray, while it is in registers (k_extend_spheres then only has the survivors of the
+		// last iteration to do), and the traversal's own first test (root_ref at the refill of k_trace_flat: same function,
+		// same bound, same answer): a ray that fails it goes to class 1 and is finished with this record
+		hitRecord = sphere_hit_record(P, lensPoint, direction);
+		tree = mine && P.scene.rootRef != kRefDone && root_ref(P.scene, make_ray(lensPoint, direction), hitRecord.x) != kRefDone;
+		// A camera ray that hits no sphere and fails the root box is finished before it is queued (P.retireSky, tyr_render's
+		// merged path): what shade would do with it is fixed -- kernel.cu:613-617 with the fresh ray's lastSpecular = true and
+		// direct = (1,1,1) (kernel.cu:295, variables.h:33): color = sunsky(direction), one finished path, no survivor, no shadow
+		// ray, and NO random number drawn -- so it is done here, while the direction is in registers: the pixel gets its
+		// radiance (the same operations: 0 + 1 * x is x), the ray's survive byte is 0, and the record is never written or read
+		// (42 % of the first wavefront's rays on C3: 112 bytes of queue traffic and a shade lane each).  Every count stays: the
+		// ray was generated and traced (n_live and the totals are sums, not queue lengths).
+		sky = P.retireSky != 0u && mine && !tree && !(hitRecord.x < kVeryFar);
+		if (__ballot(sky) != 0ull) {
+			f3 radiance = mk3(0.f, 0.f, 0.f);
+			if (sky) {
+				if (P.sun.sunAngularDiameterCos == 1.0f) {
+					radiance = mk3(1.0f, 0.0f, 0.0f); // sunsky.cu:118-119
+				} else {
+					const Atmosphere a = atmosphere(P.sun, direction);
+					radiance = sunsky_radiance(P.sun, a);
+				}
+				P.survFlag[vslot] = 0; // what k_shade writes for a ray that does not survive (k_scan_words reads every slot below n_live)
+			}
+			accumulate_pixels_wave(P.blit, y * (int)P.W + x, radiance, sky ? 1 : 0);
+		}
+		if (PART == kPrimaryRest) {
+			if (__ballot(tree) != 0ull) {
+				if (lane == 0)
+					atomicAdd(&P.k->primary_strays, (uint32_t)__popcll(__ballot(tree)));
+				bool overflow = false;
+				for (unsigned long long m; (m = __ballot(tree)) != 0ull;) {
+					if (lane == (uint32_t)__ffsll((long long)m) - 1u) {
+						hitRecord = trace_stray(kernarg_view<FrameParams>().scene, strayStack + wave * kStackSize, lensPoint, direction, hitRecord, overflow);
+						tree = false; // its record carries the answer: it joins the rays that are finished with theirs
+					}
+				}
+				if (__ballot(overflow) != 0ull && lane == 0)
+					atomicOr(&P.k->device_error, kErrStackOverflow);
+			}
+		}
 	}
 	// the block's rays of either class go to segment blockIdx % 8 of that class, behind what it holds: one atomic each
 	const unsigned long long bt = __ballot(tree), bsky = __ballot(mine && !tree && !sky), below = (1ull << lane) - 1ull;
@@ -98,6 +207,8 @@ __global__ void __launch_bounds__(kBlock) k_primary(const FrameParams P) {
 		P.work.hit[slot] = hitRecord;
 		P.work.key[slot] = vslot;
 	}
+	if (PART == kPrimaryRest)
+		return; // (k_primary_window has opened the iteration)
 	// set_wavefront_globals (kernel.cu:227-244, launched behind primary_rays at kernel.cu:720): by the block that finishes last
 	__syncthreads();
 	if (threadIdx.x == 0) {
@@ -113,12 +224,22 @@ __global__ void __launch_bounds__(kBlock) k_primary(const FrameParams P) {
 			const uint32_t words = gridDim.x < kTicketWords ? gridDim.x : kTicketWords;
 			last = atomicAdd(&P.k->primary_blocks_done, 1u) + 1u == words ? 1u : 0u;
 		}
+		if (PART == kPrimaryWindow && last) {
+			// the top-up, for k_primary_rest: what every block of this launch computed from the counts the globals now overwrite
+			P.k->plan_cnt = cnt;
+			P.k->plan_new = nNew;
+			P.k->plan_start = start;
+		}
 		lastSh = last;
 	}
 	__syncthreads();
 	if (lastSh)
 		wavefront_globals(P);
 }
+
+__global__ void __launch_bounds__(kBlock) k_primary(const FrameParams P) { primary_rays<kPrimaryWhole>(P, PrimaryWindow{}); }
+__global__ void __launch_bounds__(kBlock) k_primary_window(const FrameParams P, const PrimaryWindow win) { primary_rays<kPrimaryWindow>(P, win); }
+__global__ void __launch_bounds__(kBlock) k_primary_rest(const FrameParams P, const PrimaryWindow win) { primary_rays<kPrimaryRest>(P, win); }
 
 // extend pre-pass: kernel.cu:125-136 (spheres first; their distance bounds the BVH search)
 // (grid-stride over the device's count: the host may have sized the grid from an upper bound, and a capped grid makes a
@@ -636,6 +757,19 @@ void launch_pad_holes(const FrameParams& P, bool workQueue, bool shadowQueue, hi
 void launch_primary(const FrameParams& P, uint32_t maxNew, hipStream_t stream) {
 	// always launched: its last block is set_wavefront_globals
 	launch_in_stage(k_primary, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), stream, P);
+}
+void launch_primary_window(const FrameParams& P, const PrimaryWindow& win, uint32_t maxNew, hipStream_t stream) {
+	// the sweeps over the rank's rows that maxNew tickets can touch from any start position, each with the window's pixels
+	const unsigned long long per = (unsigned long long)(win.x1 - win.x0) * (win.yl1 - win.yl0);
+	const unsigned long long sweeps = maxNew ? ((unsigned long long)P.localPixels + maxNew - 2ull) / P.localPixels + 1ull : 0ull;
+	const unsigned long long threads = per * sweeps;
+	launch_in_stage(k_primary_window, dim3(threads ? (uint32_t)((threads + kBlock - 1) / kBlock) : 1u), dim3(kBlock), stream, P, win);
+}
+void launch_primary_rest(const FrameParams& P, const PrimaryWindow& win, uint32_t maxNew, hipStream_t stream, hipEvent_t stop) {
+	if (stop)
+		hipExtLaunchKernelGGL(k_primary_rest, dim3(blocks_for(maxNew)), dim3(kBlock), 0, stream, nullptr, stop, 0, P, win);
+	else
+		hipLaunchKernelGGL(k_primary_rest, dim3(blocks_for(maxNew)), dim3(kBlock), 0, stream, P, win);
 }
 void launch_scan(const FrameParams& P, uint32_t maxLive, hipStream_t stream) {
 	if (maxLive == 0)

@@ -40,6 +40,23 @@ struct tyr_ctx {
 	uint32_t shadowSet = 0; // which of the two sets holds the counts of the shadow queue's current content (tyr_shadow_export)
 
 	hipEvent_t evSnapshot = nullptr;
+	// A top-up in two parts (host/primary_window.cpp): the lowest-priority stream k_primary_rest runs on beside the
+	// traversal launch, the event it waits for (k_primary_window has left it the plan) and the event behind it (the ctx's stream waits
+	// for it right behind the traversal launch: whatever follows there follows the whole top-up)
+	hipStream_t sideStream = nullptr;
+	hipEvent_t evWindowDone = nullptr, evRestDone = nullptr;
+	// the camera window and what it was computed from (recomputed when that changes, not per render)
+	struct WindowKey {
+		tyr_camera cam;
+		float rootMin[3], rootMax[3];
+		uint32_t rootRef;
+		int inset;
+	} windowKey{};
+	bool windowValid = false;
+	bool windowWhole = true;       // the window is the whole frame (or empty): a top-up is one k_primary
+	uint32_t windowRect[4] = { 0, 0, 0, 0 }; // x0, x1, y0, y1 in the frame's pixels
+	tyr::PrimaryWindow window{};   // ... and in the rank's own rows
+	uint32_t primarySplits = 0;    // top-ups launched in two parts since tyr_create (tyr_primary_window_info.splits)
 	// TYR_TUNE_SCAN_IN_TRACE
 	bool scanCarried = false;      // the last shade launch left its slot scan to the next traversal launch (hip/scan_wave.hpp)
 	uint32_t scanCarriedSet = 0;

@@ -163,11 +163,12 @@ struct KernelTimer {
 	int k;
 	bool on, attached;
 	tyr::StageEvents se;
-	KernelTimer(tyr_ctx* c_, int k_) : c(c_), k(k_), on((c_->cfg.flags & TYR_FLAG_PROFILE) != 0 && ((c_->tuning.profileMask >> k_) & 1) != 0), attached(on && c_->tuning.stageTiming != 0) {
+	bool startOnly; // the stage ends on another stream: its stop event is the caller's to record or attach there (enqueue_primary's top-up in two parts)
+	KernelTimer(tyr_ctx* c_, int k_, bool startOnly_ = false) : c(c_), k(k_), on((c_->cfg.flags & TYR_FLAG_PROFILE) != 0 && ((c_->tuning.profileMask >> k_) & 1) != 0), attached(on && c_->tuning.stageTiming != 0), startOnly(startOnly_) {
 		if (attached) {
 			assert(tyr::open_stage_events() == nullptr); // stages do not nest: one is open per thread at a time
 			se.start = c->ev[c->iter & 1u][2 * k];
-			se.stop = c->ev[c->iter & 1u][2 * k + 1];
+			se.stop = startOnly ? nullptr : c->ev[c->iter & 1u][2 * k + 1];
 			tyr::open_stage_events() = &se;
 		} else if (on) {
 			(void)hipEventRecord(c->ev[c->iter & 1u][2 * k], c->stream);
@@ -179,7 +180,8 @@ struct KernelTimer {
 			c->evUsed[c->iter & 1u][k] = true;
 			c->evEmpty[c->iter & 1u][k] = se.launches == 0u; // (a stage that launched nothing bound no event: it counts with no time, as an empty event pair does)
 		} else if (on) {
-			(void)hipEventRecord(c->ev[c->iter & 1u][2 * k + 1], c->stream);
+			if (!startOnly)
+				(void)hipEventRecord(c->ev[c->iter & 1u][2 * k + 1], c->stream);
 			c->evUsed[c->iter & 1u][k] = true;
 			c->evEmpty[c->iter & 1u][k] = false;
 		}
@@ -220,10 +222,12 @@ uint32_t planned_new(const tyr_ctx* c) {
 
 void camera_basis(const tyr_ctx* c, float right[3], float up[3]) { camera_basis(c, c->cam, right, up); }
 
-void camera_basis(const tyr_ctx* c, const tyr_camera& cam, float right[3], float up[3]) {
+void camera_basis(const tyr_ctx* c, const tyr_camera& cam, float right[3], float up[3]) { camera_basis(c->cfg.width, c->cfg.height, cam, right, up); }
+
+void camera_basis(uint32_t width, uint32_t height, const tyr_camera& cam, float right[3], float up[3]) {
 	const f3 dir = ld3(cam.direction), camUp = ld3(cam.up);
 	// kernel.cu:699-700
-	const f3 r = normalize(cross(dir, camUp)) * 1.5f * (static_cast<float>(c->cfg.width) / static_cast<float>(c->cfg.height));
+	const f3 r = normalize(cross(dir, camUp)) * 1.5f * (static_cast<float>(width) / static_cast<float>(height));
 	const f3 u = normalize(cross(r, dir)) * 1.5f;
 	right[0] = r.x;
 	right[1] = r.y;
@@ -266,14 +270,35 @@ int stage_begin(tyr_ctx* c) {
 
 // enqueue one stage; the host mirror hK must be current for the sizes used here (upper bounds will do: every kernel takes
 // its counts from the device)
-void enqueue_primary(tyr_ctx* c, const FrameParams& P, uint32_t nNew) {
-	{
+void enqueue_primary(tyr_ctx* c, const FrameParams& P, uint32_t nNew, const PrimaryWindow* split) {
+	if (!split) {
 		KernelTimer t(c, TYR_K_PRIMARY);
 		if (c->mapped) // tyr_set_sample_map: the pixels come from the map's ticket list
 			launch_primary_mapped(P, MappedPrimary{ c->dTickets, c->ticketTotal }, nNew, c->stream);
 		else
 			launch_primary(P, nNew, c->stream);
+		return;
 	}
+	// The top-up in two parts.  The window's rays are all the iteration's traversal launch reads of the top-up; the
+	// others -- class 1 records, sky pixels, survive bytes: nothing the pre-passes or the traversal kernel touch -- follow on the
+	// low-priority stream as soon as the window's part has left them the plan, and run beside those launches (enqueue_trace has this
+	// stream wait for them behind its traversal kernel).  (Started WITH the window's part, from counts the host holds, they end no
+	// sooner and the traversal launch later: profiles/primary_overlap_ab.txt.)
+	// TYR_K_PRIMARY of such an iteration: from the start of the window's part to the end of the other one.
+	const bool timed = (c->cfg.flags & TYR_FLAG_PROFILE) != 0 && ((c->tuning.profileMask >> TYR_K_PRIMARY) & 1) != 0;
+	hipEvent_t const stop = timed ? c->ev[c->iter & 1u][2 * TYR_K_PRIMARY + 1] : nullptr;
+	const bool attached = c->tuning.stageTiming != 0;
+	{
+		KernelTimer t(c, TYR_K_PRIMARY, true); // (the stage's start only: its stop event goes behind the other part, below)
+		launch_primary_window(P, *split, nNew, c->stream);
+	}
+	c->primarySplits++;
+	(void)hipEventRecord(c->evWindowDone, c->stream);
+	(void)hipStreamWaitEvent(c->sideStream, c->evWindowDone, 0);
+	launch_primary_rest(P, *split, nNew, c->sideStream, attached ? stop : nullptr);
+	if (stop && !attached)
+		(void)hipEventRecord(stop, c->sideStream);
+	(void)hipEventRecord(c->evRestDone, c->sideStream);
 }
 // nSurvivors: how many of the nLive rays were in the queue before this iteration's primary rays (they still need their
 // sphere pre-pass)
@@ -288,7 +313,7 @@ void enqueue_extend(tyr_ctx* c, const FrameParams& P0, uint32_t nLive, uint32_t 
 	launch_extend(P, nLive, nSurvivors, (c->cfg.flags & TYR_FLAG_COUNT_VISITS) != 0, c->tuning, c->numCUs, c->launchCache, c->stream);
 }
 // extend of this iteration and connect of the previous one in one launch (tyr_render, TYR_TUNE_MERGE_TRACE)
-void enqueue_trace(tyr_ctx* c, const FrameParams& P0, uint32_t nLive, uint32_t nSurvivors, uint32_t maxShadowPrev) {
+void enqueue_trace(tyr_ctx* c, const FrameParams& P0, uint32_t nLive, uint32_t nSurvivors, uint32_t maxShadowPrev, const PrimaryWindow* split) {
 	FrameParams P = P0;
 	P.traceShadow = maxShadowPrev != 0 ? 1u : 0u;
 	P.prevFolded = c->lastShadeFolded ? 1u : 0u;
@@ -298,7 +323,18 @@ void enqueue_trace(tyr_ctx* c, const FrameParams& P0, uint32_t nLive, uint32_t n
 		c->scanCarried = false;
 	}
 	KernelTimer t(c, TYR_K_EXTEND);
-	launch_trace(P, nLive, nSurvivors, maxShadowPrev, c->tuning, c->numCUs, c->launchCache, c->stream);
+	if (!split) {
+		launch_trace(P, nLive, nSurvivors, maxShadowPrev, c->tuning, c->numCUs, c->launchCache, c->stream);
+		return;
+	}
+	// The top-up's other part is running on the second stream (enqueue_primary): the traversal grid leaves it room -- fewer 256-thread
+	// blocks per CU than the occupancy query admits, and no 768-thread blocks, which fill every wave slot they can
+	launch_trace_prepasses(P, nSurvivors, maxShadowPrev, c->stream, nLive);
+	Tuning t2 = c->tuning;
+	t2.wavesPerSimd = c->tuning.overlapTraceBlocks; // blocks of four waves per CU = waves per SIMD
+	t2.wideBlockMinItems = -1;
+	launch_trace_kernel(P, nLive + maxShadowPrev, t2, c->numCUs, c->launchCache, c->stream);
+	(void)hipStreamWaitEvent(c->stream, c->evRestDone, 0); // shade reads the whole top-up, and so may anything else that follows on this stream
 }
 // shade, then the scan that turns its survive bytes into the next iteration's slots
 void enqueue_shade(tyr_ctx* c, const FrameParams& P, uint32_t nLive) {
@@ -502,6 +538,14 @@ int tyr_create(tyr_ctx** out, const tyr_config* cfg) {
 	}
 	if (hipEventCreateWithFlags(&c->evSnapshot, hipEventDisableTiming) != hipSuccess)
 		return fail(TYR_ERR_NO_DEVICE);
+	{
+		int least = 0, greatest = 0;
+		(void)hipDeviceGetStreamPriorityRange(&least, &greatest);
+		if (hipStreamCreateWithPriority(&c->sideStream, hipStreamNonBlocking, least) != hipSuccess)
+			return fail(TYR_ERR_NO_DEVICE);
+		if (hipEventCreateWithFlags(&c->evWindowDone, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->evRestDone, hipEventDisableTiming) != hipSuccess)
+			return fail(TYR_ERR_NO_DEVICE);
+	}
 	if (hipHostMalloc(reinterpret_cast<void**>(&c->hK), sizeof(DevCounters), hipHostMallocDefault) != hipSuccess)
 		return fail(TYR_ERR_OOM);
 	std::memset(c->hK, 0, sizeof(DevCounters));
@@ -535,6 +579,13 @@ int tyr_destroy(tyr_ctx* c) {
 	(void)hipSetDevice(c->cfg.device);
 	if (c->stream)
 		(void)hipStreamSynchronize(c->stream);
+	if (c->sideStream) {
+		(void)hipStreamSynchronize(c->sideStream);
+		(void)hipStreamDestroy(c->sideStream);
+	}
+	for (hipEvent_t e : { c->evWindowDone, c->evRestDone })
+		if (e)
+			(void)hipEventDestroy(e);
 	query_free(c);
 	denoise_free(c);
 	temporal_free(c);

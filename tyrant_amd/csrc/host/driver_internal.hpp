@@ -50,9 +50,18 @@ void collect_timings_of(tyr_ctx* c, int set);
 void collect_timings(tyr_ctx* c);
 uint32_t planned_new(const tyr_ctx* c);
 int stage_begin(tyr_ctx* c);
-void enqueue_primary(tyr_ctx* c, const FrameParams& P, uint32_t nNew);
+// split (enqueue_primary and enqueue_trace of one iteration alike): null, or the camera window by which the top-up is made in two
+// parts -- enqueue_primary then launches the window's part on the ctx's stream and the rest on its second one, and enqueue_trace leaves
+// that one room beside its traversal kernel and has the ctx's stream wait for it behind that kernel
+void enqueue_primary(tyr_ctx* c, const FrameParams& P, uint32_t nNew, const PrimaryWindow* split = nullptr);
 void enqueue_extend(tyr_ctx* c, const FrameParams& P0, uint32_t nLive, uint32_t nSurvivors);
-void enqueue_trace(tyr_ctx* c, const FrameParams& P0, uint32_t nLive, uint32_t nSurvivors, uint32_t maxShadowPrev);
+void enqueue_trace(tyr_ctx* c, const FrameParams& P0, uint32_t nLive, uint32_t nSurvivors, uint32_t maxShadowPrev, const PrimaryWindow* split = nullptr);
+// host/primary_window.cpp: the ctx's camera window, brought up to date; and the window to make a merged iteration's top-up of at
+// most nNew rays in two parts by (behind at most nSurvivors survivors), or null when it is to be one k_primary
+void primary_window_update(tyr_ctx* c);
+// ... the same from its inputs alone (tyr_primary_window_probe): the rectangle in the frame's pixels and in the rank's rows; false = the whole frame
+bool primary_window_of(const tyr_camera& cam, uint32_t width, uint32_t height, uint32_t rank, uint32_t nranks, const float rootMin[3], const float rootMax[3], int inset, uint32_t rect[4], PrimaryWindow& local);
+const PrimaryWindow* primary_split(tyr_ctx* c, uint32_t nNew, uint32_t nSurvivors);
 void enqueue_shade(tyr_ctx* c, const FrameParams& P, uint32_t nLive);
 void enqueue_connect(tyr_ctx* c, const FrameParams& P0, uint32_t maxShadow);
 bool merged_render(const tyr_ctx* c);
@@ -83,6 +92,7 @@ int query_ticket(tyr_ctx* c, void* stream, hipStream_t& s, tyr_ctx::QueryStream*
 void camera_basis(const tyr_ctx* c, float right[3], float up[3]);
 // ... and for any camera at the ctx's width and height (tyr_render_motion's previous camera)
 void camera_basis(const tyr_ctx* c, const tyr_camera& cam, float right[3], float up[3]);
+void camera_basis(uint32_t width, uint32_t height, const tyr_camera& cam, float right[3], float up[3]);
 void query_free(tyr_ctx* c);
 // host/denoise.cpp: wait for the last tyr_denoise call; free its scratch and event (tyr_destroy)
 void denoise_free(tyr_ctx* c);

@@ -122,11 +122,12 @@ static int launch_iteration(tyr_ctx* c, bool pipelined) {
 	}
 	if (merge && c->tuning.retireSky)
 		P.retireSky = 1u;   // ... and k_primary finishes the camera rays that hit nothing
-	enqueue_primary(c, P, nNew);
+	const PrimaryWindow* const split = merge ? primary_split(c, nNew, nLive - nNew) : nullptr; // the top-up in two parts, the second beside the traversal launch
+	enqueue_primary(c, P, nNew, split);
 	if (merge) { // every traversal launch of a merged render is k_trace_flat; the first one has no shadow rays to carry yet
 		const uint32_t carried = c->shadowPending ? c->shadowPendingMax : 0u;
 		c->shadowPending = false;
-		enqueue_trace(c, P, nLive, nLive - nNew, carried);
+		enqueue_trace(c, P, nLive, nLive - nNew, carried, split);
 		enqueue_shade(c, P, nLive);
 	} else {
 		if ((rc = flush_pending_shadow(c))) // (a render whose merge setting changed between iterations: never, but cheap)
@@ -233,9 +234,10 @@ static int enqueue_merged_iteration(tyr_ctx* c, const IterationPlan& p, bool beg
 		P.hostSnap = c->hostSnapDev[set];
 		P.snapSeq = c->snapSeq;
 	}
+	const PrimaryWindow* const split = prologueDone ? nullptr : primary_split(c, p.nNew, p.nSurvivors); // the top-up in two parts, the second beside the traversal launch
 	if (!prologueDone)
-		enqueue_primary(c, P, p.nNew);
-	enqueue_trace(c, P, p.nLive, p.nSurvivors, p.carried);
+		enqueue_primary(c, P, p.nNew, split);
+	enqueue_trace(c, P, p.nLive, p.nSurvivors, p.carried, split);
 	enqueue_shade(c, P, p.nLive);
 	if (!kernelSnap) {
 		HIPCHK(hipMemcpyAsync(c->hSnap[set], c->dK, sizeof(DevCounters), hipMemcpyDeviceToHost, c->stream));

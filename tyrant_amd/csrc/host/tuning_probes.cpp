@@ -215,6 +215,10 @@ int tyr_set_tuning(tyr_ctx* c, int key, int value) {
 		{ TYR_TUNE_SCAN_IN_TRACE, 0, 1, &Tuning::scanInTrace },
 		{ TYR_TUNE_KERNEL_SNAPSHOT, 0, 1, &Tuning::kernelSnapshot },
 		{ TYR_TUNE_STAGE_TIMING, 0, 1, &Tuning::stageTiming },
+		{ TYR_TUNE_PRIMARY_OVERLAP, 0, 1, &Tuning::primaryOverlap },
+		{ TYR_TUNE_OVERLAP_TRACE_BLOCKS, 3, 5, &Tuning::overlapTraceBlocks },
+		{ TYR_TUNE_OVERLAP_MIN_NEW, 0, 0x7fffffff, &Tuning::overlapMinNew },
+		{ TYR_TUNE_WINDOW_INSET, 0, 1024, &Tuning::windowInset },
 	};
 	for (const Knob& k : knobs) {
 		if (k.key != key)
@@ -225,6 +229,19 @@ int tyr_set_tuning(tyr_ctx* c, int key, int value) {
 		return TYR_OK;
 	}
 	return TYR_ERR_INVALID;
+}
+
+int tyr_primary_window(tyr_ctx* c, tyr_primary_window_info* out) {
+	if (!c || !out)
+		return TYR_ERR_INVALID;
+	primary_window_update(c);
+	*out = tyr_primary_window_info{};
+	out->x0 = c->windowRect[0], out->x1 = c->windowRect[1], out->y0 = c->windowRect[2], out->y1 = c->windowRect[3];
+	out->local_y0 = c->window.yl0, out->local_y1 = c->window.yl1;
+	out->whole_frame = c->windowWhole ? 1u : 0u;
+	out->strays = c->hK->primary_strays;
+	out->splits = c->primarySplits;
+	return TYR_OK;
 }
 
 int tyr_get_timings(tyr_ctx* c, tyr_timings* out, int reset) {
