@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -680,6 +680,61 @@ typedef struct tyr_hits_out {
 } tyr_hits_out;
 int tyr_query_hits(tyr_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* tmax /* n or NULL = VERY_FAR */, uint32_t max_hits, uint32_t flags,
                    const tyr_hits_out* out, void* stream);
+
+/* ---- occlusion queries (extension) ----------------------------------------------------------------------------------------
+ * "How much of its hemisphere does this point see?" for a caller's batch of points with normals, against the scene the ctx
+ * holds: `samples` cosine-weighted any-hit rays per point, made on the device and answered as one integer per point -- ambient
+ * occlusion and sky-view factors at mesh vertices, lightmap texels, particles or a frame's first-hit points (AO = visible /
+ * samples), and with the mask or the bent sum which directions are open.  The samples are part of the contract: a result is
+ * pinned by (seed, the point's index, the point's data) alone.
+ *
+ * All arithmetic is binary32, one IEEE operation per operation written, nothing contracted, divisions and square roots correctly
+ * rounded; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z, normalize(v) = v * (1 / sqrtf(dot(v, v))) and the vector operators are
+ * componentwise (glm's, as the render uses them).  For point i (its index in the caller's batch, as uint32) and sample s:
+ *   valid(i) = every component of point and normal finite, and dot(normal, normal) finite and > 0
+ *   w = normalize(normal),  o = point + w * bias
+ *   h(x):  x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16      (uint32, wrapping)
+ *   state = h(h(seed ^ i) + s)                                                             (a state of 0 is used as it is)
+ *   u1 = RandomFloat(state),  u2 = RandomFloat(state)                                      (kernel.cu:23-36, in this order)
+ *   r1 = (2.f * PI) * u1,  r2s = sqrtf(u2),  (u, v) = orthonormal_basis_naive(w) (kernel.cu:181-189),  s1 = sin(r1), c1 = cos(r1)
+ *   d = normalize(((u * c1) * r2s + (v * s1) * r2s) + w * sqrtf(1 - u2))
+ * -- the diffuse bounce of shade (kernel.cu:446-452) about w, with the render's sin and cos (DESIGN.md "Numeric contract").
+ *
+ * Sample (i, s) is BLOCKED exactly when tyr_query_any answers 1 for the ray (o, d, tmax = max_dist[i], or VERY_FAR without
+ * max_dist) with the same flags, bit for bit: the accept rule t > 1e-3 and (tmax - t) > 1e-3 (bvh.h:229-238), back faces do not
+ * block (loader.h:21-46), the ctx's spheres block with TYR_QUERY_SPHERES ((t + 1e-3) < tmax, kernel.cu:168-172), a ray with a
+ * NaN or infinite component is not blocked, and max_dist goes through as tmax unexamined (0, negative and NaN block nothing).
+ *
+ * Answer, per point:  visible = the number of its samples that are not blocked;  mask = those samples as bits, W = (samples +
+ * 31) / 32 words per point, bit (s % 32) of word s / 32 for sample s, the unused high bits of the last word 0;  bent = ((0 +
+ * d_s0) + d_s1) + ... per component over the visible samples in ascending s, not normalised;  origin = o;  direction = every
+ * sample's d, blocked or not.  An invalid point: visible = 0, mask words 0, bent = 0, origin = the point as given, direction rows
+ * of 0.  A scene without triangles answers from the spheres alone (TYR_QUERY_SPHERES), or all visible.  The answer for (i, s)
+ * depends on nothing but i, s, seed and the point's data: not on the batch size, the launch shape or other points -- the first m
+ * points of a batch give the rows a batch of just those m gives.
+ *
+ * Arrays, streams and state follow tyr_query_hits: every array pointer is a DEVICE pointer, contiguous, float32 / uint32,
+ * indexed with 64-bit offsets -- points, normals n x 3; max_dist n, or NULL.  n up to 2^31 - 1, independent of queue_size (a
+ * batch of more than 2^31 / samples points goes out as several launches); n == 0: TYR_OK and nothing launched.  The work is
+ * enqueued on `stream` (NULL: the ctx's stream): visible and mask are cleared there first and, with bent, a second pass follows
+ * the first.  The call uses the ctx's device, restores the caller's and touches no render state.  A later tyr_scene_refit waits
+ * for it, a query issued after a refit sees the refitted scene, and a traversal stack overflow sets bit 1 of tyr_query_error.
+ * TYR_ERR_INVALID: ctx, points, normals, out or out->visible NULL, out->bent without out->mask, samples 0 or above
+ * TYR_QUERY_OCCLUSION_MAX_SAMPLES, a flag other than TYR_QUERY_SPHERES, n >= 2^31, or a bias that is not finite;
+ * TYR_ERR_NO_SCENE: nothing uploaded.
+ * Not part of it: stratified or low-discrepancy samples, uniform-hemisphere or cone sampling, two-sided occluders, a falloff
+ * with distance, irradiance weighted by the sky's radiance (the mask and direction let a caller do it), a per-pixel AO guide. */
+#define TYR_QUERY_OCCLUSION_MAX_SAMPLES 1024
+typedef struct tyr_occlusion_out {
+	uint32_t* visible;   /* n: samples of the point that nothing blocks (required) */
+	uint32_t* mask;      /* n x W words, W = (samples + 31) / 32: bit (s % 32) of word s / 32 set = sample s is visible; NULL ok */
+	float*    bent;      /* n x 3: the sum, in sample order, of the visible samples' directions (not normalised); NULL ok, needs mask */
+	float*    origin;    /* n x 3: the origin the point's rays start from; NULL ok */
+	float*    direction; /* n x samples x 3: every sample's direction, visible or not; NULL ok */
+} tyr_occlusion_out;
+int tyr_query_occlusion(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 */, const float* normals /* n x 3 */,
+                        const float* max_dist /* n, or NULL: VERY_FAR */, uint32_t samples /* 1 .. 1024 */, float bias, uint32_t seed,
+                        uint32_t flags /* 0 or TYR_QUERY_SPHERES */, const tyr_occlusion_out* out, void* stream);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

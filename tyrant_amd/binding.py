@@ -32,6 +32,7 @@ TYR_QUERY_SPHERES = 1
 TYR_QUERY_TWO_SIDED = 2  # tyr_query_hits only
 TYR_QUERY_HITS_MAX = 32
 TYR_QUERY_NEAREST_K_MAX = 32
+TYR_QUERY_OCCLUSION_MAX_SAMPLES = 1024
 AOV_CHAIN_MAX = 8  # TYR_AOV_CHAIN_MAX
 TYR_REFIT_DEVICE = 1
 TYR_DENOISE_RESOLVE = 1
@@ -141,6 +142,12 @@ class HitsOut(C.Structure):
     """tyr_hits_out: device pointers of tyr_query_hits's outputs; uv, side, back_count may be NULL"""
 
     _fields_ = [("count", P), ("t", P), ("prim", P), ("uv", P), ("side", P), ("back_count", P)]
+
+
+class OcclusionOut(C.Structure):
+    """tyr_occlusion_out: device pointers of tyr_query_occlusion's outputs; mask, bent, origin, direction may be NULL"""
+
+    _fields_ = [("visible", P), ("mask", P), ("bent", P), ("origin", P), ("direction", P)]
 
 
 class AovChainOut(C.Structure):
@@ -291,6 +298,7 @@ SYMBOLS = {
     "tyr_query_nearest": (C.c_int, [P, c_u32, P, P, c_u32, P, P]),
     "tyr_query_nearest_k": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
+    "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
     "tyr_render_aov_chain": (C.c_int, [P, c_u32, c_u32, P, P, P]),
@@ -804,6 +812,40 @@ class Renderer:
         self._on_stream(stream, lambda h: self.L.tyr_query_hits(self.h, n, o.data_ptr(), d.data_ptr(), tp, k, flags, C.byref(out), h), staged)
         self._query_finish()
         return count, t, prim, uv, side, back
+
+    def query_occlusion(self, points, normals, samples=64, max_dist=None, bias=1e-3, seed=0, spheres=False, mask=False, bent=False, rays=False, stream=None):
+        """tyr_query_occlusion: for every point, `samples` cosine-weighted any-hit rays over the hemisphere of its normal, made on
+        the device (include/tyr_c.h "Occlusion queries").  points, normals: (N, 3) float32, max_dist: (N,) or None (VERY_FAR) --
+        torch tensors on this ctx's device, taken as they are, or numpy arrays.  Returns torch tensors (visible, mask, bent, origin,
+        direction), None for what was not asked for: visible (N,) int32 (the library's uint32), the samples nothing blocks -- AO =
+        visible / samples; mask (N, (samples + 31) // 32) int32 (uint32 words), bit s % 32 of word s // 32 set for a visible
+        sample; bent (N, 3), the sum of the visible samples' directions in sample order (bent=True implies the mask); with
+        rays=True origin (N, 3) and direction (N, samples, 3), every sample's ray.  An invalid point (a NaN, infinite or zero
+        normal, a NaN point) has visible = 0."""
+        import torch
+
+        if not 1 <= int(samples) <= TYR_QUERY_OCCLUSION_MAX_SAMPLES:
+            raise ValueError(f"samples: 1 .. {TYR_QUERY_OCCLUSION_MAX_SAMPLES}")
+        S = int(samples)
+        dev = torch.device("cuda", self.device)
+        take = self._query_take
+        staged = not all(isinstance(a, torch.Tensor) for a in (points, normals, max_dist) if a is not None)
+        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
+        n = p.shape[0] if p.ndim == 2 else -1
+        p = take(p, "points", (n, 3))
+        nr = take(normals, "normals", (n, 3))
+        md = take(max_dist, "max_dist", (n,)) if max_dist is not None else None
+        visible = torch.empty(n, dtype=torch.int32, device=dev)
+        m = torch.empty((n, (S + 31) // 32), dtype=torch.int32, device=dev) if (mask or bent) else None
+        b = torch.empty((n, 3), dtype=torch.float32, device=dev) if bent else None
+        origin = torch.empty((n, 3), dtype=torch.float32, device=dev) if rays else None
+        direction = torch.empty((n, S, 3), dtype=torch.float32, device=dev) if rays else None
+        out = OcclusionOut(*(None if t is None else t.data_ptr() for t in (visible, m, b, origin, direction)))
+        flags = TYR_QUERY_SPHERES if spheres else 0
+        mp = md.data_ptr() if md is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_occlusion(self.h, n, p.data_ptr(), nr.data_ptr(), mp, S, float(bias), int(seed) & 0xFFFFFFFF, flags, C.byref(out), h), staged)
+        self._query_finish()
+        return visible, m, b, origin, direction
 
     def render_aov(self, spp, albedo=True, normal=True, depth=True, ids=True, stream=None, max_chain=None) -> dict:
         """tyr_render_aov: first-hit guide buffers of the current camera at the current frame counter, spp camera rays per pixel
