@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_query_winding, tyr_scene_moments, TYR_FLAG_WINDING and tyr_vecmath_probe ops 50-52; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -141,6 +141,8 @@ typedef struct tyr_config {
                                         * intersect_debug bvh.h:164-209) -- spheres ignored, and the blit_buffer receives, per ray, green = steps x 0.0002 x 255.99
                                         * (red instead from 70 steps on), a = 1 -- and tyr_launch_kernels / tyr_render run primary + that stage only */
 #define TYR_FLAG_REFIT 64u             /* every scene upload keeps what tyr_scene_refit needs on the device (counted in tyr_scene_info.device_bytes) */
+#define TYR_FLAG_WINDING 128u          /* every scene upload (and, with TYR_FLAG_REFIT, every tyr_scene_refit) also builds the moment tree of
+                                          tyr_query_winding on the device, beside the scene (counted in tyr_scene_info.device_bytes) */
 
 typedef struct tyr_ctx tyr_ctx;
 
@@ -277,7 +279,7 @@ typedef struct tyr_scene_info {
 	uint32_t max_quad_nodes;   /* 1 << 25 */
 	uint32_t max_prim_offset;  /* 1 << 26 */
 	uint32_t quad_max_stack;   /* the most stack entries any traversal of this tree can need (the drain's four-lanes-to-a-ray form holds 48 and is used only below that) */
-	uint64_t device_bytes;     /* quad nodes + pair nodes + 48-byte triangles resident in HBM (+ the refit plan with TYR_FLAG_REFIT) */
+	uint64_t device_bytes;     /* quad nodes + pair nodes + 48-byte triangles resident in HBM (+ the refit plan with TYR_FLAG_REFIT, + the moment tree with TYR_FLAG_WINDING) */
 	double upload_layout_s;    /* the last tyr_scene_upload / tyr_scene_build_upload: seconds in the layout passes (on the device, or on the threads of tyr_set_build_threads) ... */
 	double upload_copy_s;      /* ... and in device allocation + the copies to HBM */
 	uint32_t layout_on_device; /* 1: that layout ran on the device (TYR_TUNE_LAYOUT_ON_DEVICE; hip/bvh_layout_dev.hip), 0: on the host */
@@ -307,7 +309,9 @@ int tyr_scene_hash(tyr_ctx* ctx, tyr_layout_stats* out);
  * Ops 32-49 are the project's own and have no glm counterpart: the numeric contract's sin / cos / exp / pow (hip/detmath.hpp)
  * with the binary64 values they round, and the samplers of hip/device_common.hpp, listed at contract_probe in
  * hip/frame.hip.  They write three 32-bit WORDS per element into out (binary64 values as two words, low first; seeds and
- * integers as they are) and read seeds as the bit patterns of a's first component.  Ops 20-31 are TYR_ERR_INVALID. */
+ * integers as they are) and read seeds as the bit patterns of a's first component.  Ops 50-52 are the binary64 building blocks
+ * of the winding numbers ("Winding numbers" below), each [0, value]: 50 atan2_det((double)a.x, (double)b.x), 51 (double)a.x /
+ * (double)b.x, 52 sqrt((double)a.x * (double)b.x).  Ops 20-31 and everything above 52 are TYR_ERR_INVALID. */
 int tyr_vecmath_probe(int32_t device, int32_t op, const float* a, const float* b, const float* c, uint32_t n, float* out);
 
 /* The atmosphere as the shade kernel evaluates it (hip/sunsky.hpp, hip/device_common.hpp cone_sample), run ON THE DEVICE
@@ -735,6 +739,83 @@ typedef struct tyr_occlusion_out {
 int tyr_query_occlusion(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 */, const float* normals /* n x 3 */,
                         const float* max_dist /* n, or NULL: VERY_FAR */, uint32_t samples /* 1 .. 1024 */, float bias, uint32_t seed,
                         uint32_t flags /* 0 or TYR_QUERY_SPHERES */, const tyr_occlusion_out* out, void* stream);
+
+/* ---- winding numbers (extension) ------------------------------------------------------------------------------------------
+ * "Is this point inside?" for a caller's batch of points, against the triangles of the scene a ctx with TYR_FLAG_WINDING holds:
+ * the generalised winding number (Jacobson et al. 2013), the solid angle the triangles subtend at the point over 4 pi -- 1 inside
+ * a closed mesh whose e1 x e2 normals point outward, 0 outside, the integer count of enclosing shells for nested or overlapping
+ * ones (an inward-facing shell counts -1), and a value that degrades smoothly for a mesh with holes or a soup.
+ * (tyr_query_closest culls the triangles whose e1 x e2 normal points along the ray, loader.h:21-46: the faces it reports are
+ * those seen from the side w counts as outside.)  inside = w > 0.5; a signed distance is (1 - 2 * inside) * sqrt(dist2 of
+ * tyr_query_nearest).  Far from a node of the tree its triangles are summed as one dipole (Barill et al. 2018, first order);
+ * `accuracy` is how many box reaches away "far" begins.  The ctx's spheres take no part.
+ *
+ * All arithmetic is binary64, one IEEE operation per operation written, nothing contracted, divisions and square roots correctly
+ * rounded; dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x);
+ * vector +, - and scaling are componentwise; max(a, b) = b > a ? b : a.  Inputs (triangle records, boxes, points, accuracy) are
+ * binary32 widened exactly.
+ *
+ * Per triangle t of the uploaded array (vert, e1, e2; after a refit: the new records):
+ *   n_t = 0.5 * cross(e1, e2),  a_t = sqrt(dot(n_t, n_t)),  c_t = vert + (e1 + e2) / 3.0
+ * Per node i of the uploaded node array (tyr_bvh_node: depth-first, left child i + 1, right child `offset`, a leaf has
+ * primitiveCount > 0 and the primitives offset .. offset + primitiveCount - 1):
+ *   moments N_i = sum n_t, S_i = sum a_t, M_i = sum a_t * c_t: a leaf folds them from 0 over its primitives in array order
+ *   (N = 0 + n_t0, then + n_t1, ...); an interior node is left + right, componentwise
+ *   p_i = M_i / S_i per component when S_i > 0, else the box centre 0.5 * (lo + hi)
+ *   r2_i = (m_x + m_y) + m_z,  m_k = max((lo_k - p_k) * (lo_k - p_k), (hi_k - p_k) * (hi_k - p_k)),  lo / hi the node's box (after
+ *   a refit: the refitted box)
+ *   skip(i) = the index after i's subtree: nNodes for the root, the parent's offset for a left child, the parent's skip for a
+ *   right child
+ * Per point q, with B2 = accuracy * accuracy:
+ *   sum = 0; i = 0
+ *   while i < nNodes:
+ *       d = p_i - q;  d2 = dot(d, d)
+ *       if d2 > B2 * r2_i:          (far; a comparison with a NaN is false)
+ *           sum = sum + dot(d, N_i) / (d2 * sqrt(d2));  dipoles += 1;  i = skip(i)
+ *       else if i is a leaf:
+ *           for t in its primitives, array order:  sum = sum + omega(q, t);  triangles += 1
+ *           i = skip(i)
+ *       else:  i = i + 1
+ *   w = (float)(sum * INV_4PI),  INV_4PI = 0x1.45f306dc9c883p-4
+ * omega(q, t):  a = vert - q,  b = (vert + e1) - q,  c = (vert + e2) - q;  la = sqrt(dot(a, a)), lb, lc likewise
+ *   det = dot(a, cross(b, c))
+ *   den = ((la * lb) * lc + dot(a, b) * lc) + (dot(b, c) * la + dot(c, a) * lb)
+ *   omega = 2 * atan2_det(det, den)
+ * atan2_det(y, x) (hip/detmath.hpp), within 2^-45 of atan2:
+ *   ax = |x|, ay = |y|;  steep = ay > ax;  mx = steep ? ay : ax,  mn = steep ? ax : ay;  t = mx == 0 ? 0 : mn / mx
+ *   fold = t > 0x1.a827999fcef32p-2 (sqrt(2) - 1);  u = fold ? (t - 1) / (t + 1) : t;  base = fold ? PI/4 : 0;  z = u * u
+ *   p = c_16;  p = p * z + c_k for k = 15 .. 0,  c_k = the binary64 nearest (-1)^k / (2k + 1)
+ *   r = base + u * p;  if steep: r = PI/2 - r;  if x < 0: r = PI - r;  if y < 0: r = -r        (PI = 0x1.921fb54442d18p+1,
+ *   PI/2 and PI/4 its halves)
+ * So atan2_det(0, 0) = 0: a triangle with the point on one of its vertices or edges, or a degenerate triangle, adds nothing; a
+ * triangle with the point in its plane and inside it adds +2 pi whichever way it faces (atan2_det(+-0, negative) = PI), as seen
+ * from the side its normal points away from.  Hence w = 0.5 on an open sheet, w = 1 on a face of a closed outward-facing mesh
+ * (the rest of the mesh adds the other 2 pi; an inward-facing one: 0), and on an edge or a vertex the angle the other triangles
+ * subtend (0.25 and 0.125 on a box's).  The sum with libm's atan2 gives the same values.
+ *
+ * Answer, per point: w; and optionally terms = (dipoles, triangles), the counts of the loop above -- they pin the walk.  A point
+ * with a NaN or infinite component: w = the quiet NaN 0x7fc00000, terms (0, 0).  A scene without triangles: w = 0, terms (0, 0).
+ * accuracy = +inf never takes the far branch: the exact sum over every triangle in the order the leaves are met.  accuracy = 0
+ * is allowed (every node whose centre is not the point itself is far).  The answer for a point depends on the point and
+ * accuracy alone: not on the batch, the launch shape or other points.  About 2 is enough to round to the right integer next to
+ * a closed mesh; the error against the exact sum and the terms per point are tabulated in DESIGN.md "Winding numbers".
+ *
+ * Arrays, streams and state follow tyr_query_hits: points (n x 3), w_out (n) and terms_out (n x 2, NULL ok) are DEVICE pointers,
+ * contiguous, float32 / uint32, indexed with 64-bit offsets; n up to 2^31 - 1; n == 0: TYR_OK and nothing launched.  Points are
+ * dealt to the lanes in the batch's order, so a batch in a spatially coherent order (a grid, a Morton sort) runs faster than a
+ * shuffled one and answers the same.  The work is enqueued on `stream` (NULL: the ctx's); the call uses the ctx's device,
+ * restores the caller's and touches no render state.  A later tyr_scene_refit waits for it, and a query issued after a refit
+ * sees the refitted scene and its rebuilt moments.
+ * TYR_ERR_INVALID: ctx, points or w_out NULL, n >= 2^31, an accuracy that is NaN or negative; TYR_ERR_UNSUPPORTED: a ctx
+ * without TYR_FLAG_WINDING; TYR_ERR_NO_SCENE: nothing uploaded.
+ * Not part of it: higher-order expansions, the spheres, a signed-distance call, a voxel-grid helper, point clouds. */
+int tyr_query_winding(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3, device */, float accuracy, float* w_out /* n */,
+                      uint32_t* terms_out /* n x 2, NULL ok */, void* stream);
+/* Test hook in the spirit of tyr_scene_hash: nodes first .. first + count - 1 of the moment tree the ctx holds, read back into
+ * the HOST array host_out as 8 binary64 values each: p xyz, N xyz, r2, S.  TYR_ERR_INVALID: ctx NULL, a negative first or count,
+ * a range past the node count (0 for a scene without triangles), host_out NULL with count > 0; TYR_ERR_UNSUPPORTED: a ctx
+ * without TYR_FLAG_WINDING; TYR_ERR_NO_SCENE: nothing uploaded. */
+int tyr_scene_moments(tyr_ctx* ctx, int32_t first, int32_t count, double* host_out /* count x 8 */);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

@@ -23,6 +23,7 @@ TYR_FLAG_LIGHT_LIST = 8
 TYR_FLAG_TRIANGLE_COLORS = 16
 TYR_FLAG_DEBUG_BVH = 32
 TYR_FLAG_REFIT = 64
+TYR_FLAG_WINDING = 128
 TYR_ERR_INVALID = -1
 TYR_ERR_NO_DEVICE = -2
 TYR_ERR_NO_SCENE = -3
@@ -299,6 +300,8 @@ SYMBOLS = {
     "tyr_query_nearest_k": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
+    "tyr_query_winding": (C.c_int, [P, c_u32, P, C.c_float, P, P, P]),
+    "tyr_scene_moments": (C.c_int, [P, c_i32, c_i32, P]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
     "tyr_render_aov_chain": (C.c_int, [P, c_u32, c_u32, P, P, P]),
@@ -847,6 +850,35 @@ class Renderer:
         self._query_finish()
         return visible, m, b, origin, direction
 
+    def query_winding(self, points, accuracy=2.0, terms=False, stream=None):
+        """tyr_query_winding: the generalised winding number of the uploaded triangles at every point (include/tyr_c.h "Winding
+        numbers"; the ctx needs TYR_FLAG_WINDING) -- 1 inside a closed outward-facing mesh, 0 outside, 0.5 on it, so `w > 0.5` is
+        the inside test.  points: (N, 3) float32, a torch tensor on this ctx's device, taken as it is, or a numpy array; accuracy:
+        how many box reaches away a node counts as far (math.inf: the exact sum).  Returns the torch tensor w (N,) float32, or with
+        terms=True (w, terms) with terms (N, 2) int32 (the library's uint32): the dipoles and triangles summed for the point."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        staged = not isinstance(points, torch.Tensor)
+        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
+        n = p.shape[0] if p.ndim == 2 else -1
+        p = self._query_take(p, "points", (n, 3))
+        w = torch.empty(n, dtype=torch.float32, device=dev)
+        t = torch.empty((n, 2), dtype=torch.int32, device=dev) if terms else None
+        tp = t.data_ptr() if t is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_winding(self.h, n, p.data_ptr(), float(accuracy), w.data_ptr(), tp, h), staged, "tyr_query_winding")
+        self._query_finish()
+        return (w, t) if terms else w
+
+    def scene_moments(self, first=0, count=None) -> np.ndarray:
+        """tyr_scene_moments: (count, 8) float64 -- p xyz, N xyz, r2, S of nodes first .. first + count - 1 of the moment tree this
+        ctx holds (count=None: up to the last node of the scene uploaded through this Renderer)"""
+        if count is None:
+            count = max(self._n_nodes - int(first), 0)
+        out = np.zeros((int(count), 8), dtype=np.float64)
+        _check(self.L.tyr_scene_moments(self.h, int(first), int(count), _ptr(out) if count else None), "tyr_scene_moments")
+        return out
+
     def render_aov(self, spp, albedo=True, normal=True, depth=True, ids=True, stream=None, max_chain=None) -> dict:
         """tyr_render_aov: first-hit guide buffers of the current camera at the current frame counter, spp camera rays per pixel
         (the rays of a render's first wavefront from an empty queue).  Returns a dict of torch tensors on this ctx's device:
@@ -1097,10 +1129,11 @@ def vecmath_probe(op: int, a: np.ndarray, b: np.ndarray, c: np.ndarray, device: 
 
 
 def contract_probe(op: int, a: np.ndarray, b: np.ndarray | None = None, device: int = 0) -> np.ndarray:
-    """tyr_vecmath_probe's own ops (32-49: hip/detmath.hpp and the samplers, listed at contract_probe in hip/frame.hip) over
+    """tyr_vecmath_probe's own ops (32-52: hip/detmath.hpp, the samplers and the winding numbers' binary64 building blocks,
+    listed at contract_probe in hip/frame.hip) over
     (n, 3) arrays of 32-bit words -- float32, or uint32 where the op reads seeds -- into (n, 3) uint32 words"""
     a, b = (np.ascontiguousarray(x).reshape(-1, 3) for x in (a, a if b is None else b))
-    assert all(x.dtype in (np.float32, np.uint32) for x in (a, b)) and a.shape == b.shape and 32 <= op <= 49
+    assert all(x.dtype in (np.float32, np.uint32) for x in (a, b)) and a.shape == b.shape and 32 <= op <= 52
     out = np.zeros(a.shape, dtype=np.uint32)
     _check(lib().tyr_vecmath_probe(device, op, _ptr(a), _ptr(b), _ptr(a), a.shape[0], _ptr(out)), "tyr_vecmath_probe")
     return out

@@ -182,5 +182,42 @@ __device__ __forceinline__ float powf_det(float xf, float yf) {
 	return (float)(exp_poly(w) * pow2i((int)kd));
 }
 
+// atan2_det (include/tyr_c.h "Winding numbers"): the angle of (x, y) in binary64, within 2^-45 of atan2.  The quotient of the
+// smaller by the larger magnitude is folded once at tan(pi/8), so |u| <= sqrt(2) - 1 and the 17-term series
+// atan(u) = u * sum (-1)^k z^k / (2k + 1), z = u*u, ends below 2^-48; the octant, the half plane and the sign are undone in that
+// order.  atan2_det(0, 0) = 0 (for either sign of the zeros), and a NaN comes out as a NaN.
+__device__ static constexpr double kAtanSeries[17] = {
+	0x1.0000000000000p+0,  -0x1.5555555555555p-2, 0x1.999999999999ap-3,  -0x1.2492492492492p-3, 0x1.c71c71c71c71cp-4,  -0x1.745d1745d1746p-4,
+	0x1.3b13b13b13b14p-4,  -0x1.1111111111111p-4, 0x1.e1e1e1e1e1e1ep-5,  -0x1.af286bca1af28p-5, 0x1.8618618618618p-5,  -0x1.642c8590b2164p-5,
+	0x1.47ae147ae147bp-5,  -0x1.2f684bda12f68p-5, 0x1.1a7b9611a7b96p-5,  -0x1.0842108421084p-5, 0x1.f07c1f07c1f08p-6,
+};
+constexpr double kPi = 0x1.921fb54442d18p+1;
+constexpr double kPio2 = 0x1.921fb54442d18p+0;
+constexpr double kPio4 = 0x1.921fb54442d18p-1;
+constexpr double kTanPio8 = 0x1.a827999fcef32p-2; // sqrt(2) - 1
+constexpr double kInv4Pi = 0x1.45f306dc9c883p-4;
+
+__device__ __forceinline__ double atan2_det(double y, double x) {
+	const double ax = __builtin_fabs(x), ay = __builtin_fabs(y);
+	const bool steep = ay > ax;
+	const double mx = steep ? ay : ax, mn = steep ? ax : ay;
+	const double t = mx == 0.0 ? 0.0 : mn / mx;
+	const bool fold = t > kTanPio8;
+	const double u = fold ? (t - 1.0) / (t + 1.0) : t;
+	const double z = u * u;
+	double p = kAtanSeries[16];
+#pragma unroll
+	for (int k = 15; k >= 0; --k)
+		p = p * z + kAtanSeries[k];
+	double r = (fold ? kPio4 : 0.0) + u * p;
+	if (steep)
+		r = kPio2 - r;
+	if (x < 0.0)
+		r = kPi - r;
+	if (y < 0.0)
+		r = -r;
+	return r;
+}
+
 } // namespace dm
 } // namespace tyr

@@ -618,6 +618,10 @@ __device__ void contract_probe(int op, f3 A, f3 B, uint32_t seedWord, uint32_t* 
 		w[2] = __float_as_uint(r.z);
 		break;
 	}
+	// the winding numbers' binary64 building blocks (include/tyr_c.h "Winding numbers"): [0, value]
+	case 50: put64(w, dm::atan2_det((double)x, (double)B.x)); break;
+	case 51: put64(w, (double)x / (double)B.x); break;
+	case 52: put64(w, __builtin_sqrt((double)x * (double)B.x)); break;
 	default: break;
 	}
 }

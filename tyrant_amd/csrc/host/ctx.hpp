@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../hip/refit.hpp"
+#include "../hip/winding.hpp"
 #include "host.hpp"
 
 using tyr::ConnectCounters;
@@ -165,6 +166,8 @@ struct tyr_ctx {
 
 	// TYR_FLAG_REFIT: what every scene upload keeps for tyr_scene_refit (host/refit.cpp)
 	tyr::RefitPlan refit{};
+	// TYR_FLAG_WINDING: the moment tree every scene upload and refit builds for tyr_query_winding (host/winding.cpp)
+	tyr::WindingTree winding{};
 
 	hipEvent_t ev[2][2 * TYR_K_COUNT]{}; // TYR_FLAG_PROFILE: start / stop per stage, two sets (iteration i uses set i & 1: two iterations may be queued)
 	bool evUsed[2][TYR_K_COUNT]{};

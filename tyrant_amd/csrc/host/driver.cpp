@@ -614,6 +614,7 @@ int tyr_destroy(tyr_ctx* c) {
 	dev_free(c->dLights);
 	dev_free(c->dPalette);
 	refit_free(c);
+	winding_free(c);
 	if (c->ownBlit)
 		dev_free(c->blit);
 	if (c->hK)
@@ -668,6 +669,7 @@ int drop_scene(tyr_ctx* c) {
 	dev_free(c->dTris);
 	dev_free(c->dLights);
 	refit_free(c);
+	winding_free(c);
 	c->nLights = 0;
 	c->scene = DevScene{};
 	c->scene.rootRef = kRefDone;
@@ -704,9 +706,9 @@ int adopt_device_layout(tyr_ctx* c, DeviceTreeLayout& L, int32_t nPrims, const t
 	c->scene.nPairs = 0;
 	c->scene.nPrims = static_cast<uint32_t>(nPrims);
 	if (c->cfg.flags & TYR_FLAG_REFIT)
-		return refit_keep(c, hostNodes, dNodes, nNodes, nullptr, L.slotNode, L.nQuads * 4u, nullptr, 0);
+		rc = refit_keep(c, hostNodes, dNodes, nNodes, nullptr, L.slotNode, L.nQuads * 4u, nullptr, 0);
 	dev_free(L.slotNode);
-	return TYR_OK;
+	return rc ? rc : winding_build(c, dNodes, hostNodes, nNodes);
 }
 
 // tyr_scene_upload with the layout pass on the device (TYR_TUNE_LAYOUT_ON_DEVICE): the reference's arrays cross the bus as they
@@ -808,6 +810,8 @@ int tyr_scene_upload(tyr_ctx* c, const tyr_bvh_node* nodes, int32_t nNodes, cons
 		if ((rc = refit_keep(c, nodes, nullptr, nNodes, L.slotNode.data(), noSlots, static_cast<uint32_t>(L.slotNode.size()), L.pairNode.data(), static_cast<uint32_t>(L.pairNode.size()))))
 			return rc;
 	}
+	if ((rc = winding_build(c, c->refit.nodes, nodes, nNodes))) // (the plan's copy of the node array when there is one)
+		return rc;
 	c->uploadCopyS = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count(); // (hipMemcpy from pageable memory returns when the data is on its way from a staging buffer at the latest; the three arrays, allocation included)
 	return upload_light_list(c, prims, nPrims);
 }

@@ -82,6 +82,11 @@ struct DeviceScope {
 int refit_keep(tyr_ctx* c, const tyr_bvh_node* nodes, const tyr_bvh_node* dNodes, int32_t nNodes, const int32_t* slotNode, int32_t*& dSlotNode, uint32_t nSlots,
                const int32_t* pairNode, uint32_t nPairSides);
 void refit_free(tyr_ctx* c);
+// host/winding.cpp: (re)build the moment tree of the scene the ctx holds (TYR_FLAG_WINDING; nothing without it) from the reference's
+// node array -- dNodes on the device, or null (then staged from hostNodes) -- and the ctx's triangle records, on the ctx's
+// stream, which is idle on return
+int winding_build(tyr_ctx* c, const tyr_bvh_node* dNodes, const tyr_bvh_node* hostNodes, int32_t nNodes);
+void winding_free(tyr_ctx* c);
 // host/query.cpp: wait for the ctx's queries in flight on any stream; free their device words (tyr_destroy)
 int query_wait(tyr_ctx* c);
 // ... and open a launch of a query-like pass (tyr_query_*, tyr_render_aov) on the caller's `stream` (NULL: the ctx's): s = the

@@ -233,6 +233,8 @@ int tyr_scene_refit(tyr_ctx* c, const tyr_triangle* prims, const tyr_bbox* bboxe
 	HIPCHK(hipStreamSynchronize(s));
 	std::memcpy(c->scene.rootMin, root.bounds[0], 12);
 	std::memcpy(c->scene.rootMax, root.bounds[1], 12);
+	if (int rc = winding_build(c, R.nodes, nullptr, R.nNodes)) // TYR_FLAG_WINDING: the moments of the new triangles and boxes
+		return rc;
 	if (nodes_out)
 		HIPCHK(hipMemcpy(nodes_out, R.nodes, static_cast<size_t>(R.nNodes) * sizeof(tyr_bvh_node), hipMemcpyDeviceToHost));
 	return TYR_OK;

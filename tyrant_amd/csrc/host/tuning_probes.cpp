@@ -21,7 +21,7 @@ using namespace tyr::drv;
 extern "C" {
 
 int tyr_vecmath_probe(int32_t device, int32_t op, const float* a, const float* b, const float* c, uint32_t n, float* out) {
-	if (!a || !b || !c || !out || n == 0 || op < 0 || (op > 19 && op < 32) || op > 49)
+	if (!a || !b || !c || !out || n == 0 || op < 0 || (op > 19 && op < 32) || op > 52)
 		return TYR_ERR_INVALID;
 	int ndev = 0;
 	if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
@@ -105,7 +105,8 @@ int tyr_get_scene_info(tyr_ctx* c, tyr_scene_info* out) {
 	out->max_prim_offset = kMaxPrimOffset;
 	const bool havePairs = (c->cfg.flags & (TYR_FLAG_COUNT_VISITS | TYR_FLAG_DEBUG_BVH)) != 0;
 	out->device_bytes = static_cast<uint64_t>(c->scene.nQuads) * 128 + (havePairs ? static_cast<uint64_t>(c->scene.nPairs) * 64 : 0) + static_cast<uint64_t>(c->scene.nPrims) * 48
-	                    + c->refit.bytes; // TYR_FLAG_REFIT's plan (host/refit.cpp); 0 without the flag
+	                    + c->refit.bytes    // TYR_FLAG_REFIT's plan (host/refit.cpp); 0 without the flag
+	                    + c->winding.bytes; // TYR_FLAG_WINDING's moment tree (host/winding.cpp); 0 without the flag
 	out->upload_layout_s = c->uploadLayoutS;
 	out->upload_copy_s = c->uploadCopyS;
 	out->layout_on_device = c->layoutOnDevice ? 1u : 0u;
