@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_query_winding, tyr_scene_moments, TYR_FLAG_WINDING and tyr_vecmath_probe ops 50-52; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_query_winding, tyr_scene_moments, TYR_FLAG_WINDING and tyr_vecmath_probe ops 50-52; tyr_query_sweep and tyr_sweep_out; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -816,6 +816,75 @@ int tyr_query_winding(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3, de
  * a range past the node count (0 for a scene without triangles), host_out NULL with count > 0; TYR_ERR_UNSUPPORTED: a ctx
  * without TYR_FLAG_WINDING; TYR_ERR_NO_SCENE: nothing uploaded. */
 int tyr_scene_moments(tyr_ctx* ctx, int32_t first, int32_t count, double* host_out /* count x 8 */);
+
+/* ---- swept-sphere queries (extension) -------------------------------------------------------------------------------------
+ * "A sphere of radius r moves from o along d: when does it first touch the mesh, where, and on which triangle?" for a caller's
+ * batch of sweeps, against the scene the ctx holds -- the sphere cast (time of impact) of collision code.  A ray slips between
+ * what a sphere would catch, and a radius search at the start misses what the sphere meets on the way.  The contract is an
+ * argmin over all triangles of the uploaded array with no traversal order in it.
+ *
+ * All arithmetic is binary64, one IEEE operation per operation written, nothing contracted, divisions and square roots
+ * correctly rounded; dot and cross are the "Winding numbers" block's; vector +, - and scaling are componentwise.  Inputs
+ * (triangle records, o, d, r, tmax) are binary32 widened exactly.  A comparison with a NaN is false.
+ *
+ * Triangle corners: A = vert, B = the BINARY32 sum vert + e1, C = the binary32 sum vert + e2, all widened -- exactly the corners
+ * tyr_triangle_bboxes bounds.  e1' = B - A, e2' = C - A (binary64).
+ *
+ * Value of a (sweep, triangle) pair.  The centre moves as c(t) = o + t*d (per component o_k + t*d_k) for t in [0, tmax]; d need
+ * not be unit length: t is in units of d, as for tyr_query_closest.  The value is the smallest t at which the centre is within
+ * r of the triangle.  With rr = r*r, dd = dot(d, d), ap = o - A:
+ *  1. Initial overlap.  The "Closest-point queries" block's rules, clamp, q and c in binary64 with vert, e1, e2 := A, e1', e2' and
+ *     p := o.  When dot(q, q) <= rr:  t = 0, region = that block's region, contact = its c.
+ *  2. Otherwise the candidates, each offered in this order; a candidate is taken when its conditions hold, 0 <= t <= tmax and
+ *     t < the t taken so far (strict: of equal t the lower region code stays):
+ *     the face, region 0:
+ *       n = cross(e1', e2'),  nn = dot(n, n),  ln = sqrt(nn),  h = dot(n, ap),  s = h >= 0 ? 1 : -1,  sdn = s * dot(n, d)
+ *       ah = |h|,  rl = r * ln,  t = (ah - rl) / (-sdn),  k = (s * r) / ln
+ *       q_k = (o_k + t*d_k) - n_k*k,  w = q - A,  bv = dot(cross(w, e2'), n),  bw = dot(cross(e1', w), n)
+ *       conditions: nn > 0, sdn < 0, ah > rl, bv >= 0, bw >= 0, bv + bw <= nn;   contact = q
+ *     a vertex P, regions 1, 2, 3 = A, B, C:
+ *       m = o - P,  b = dot(m, d),  c = dot(m, m) - rr,  disc = b*b - dd*c,  t = (-b - sqrt(disc)) / dd
+ *       conditions: dd > 0, b < 0, c > 0, disc >= 0;   contact = P
+ *     an edge P0 -> P1, regions 4, 5, 6 = A -> B, A -> C, B -> C (as tyr_query_nearest numbers them):
+ *       e = P1 - P0,  m = o - P0,  ee = dot(e, e),  de = dot(d, e),  me = dot(m, e),  md = dot(m, d),  mm = dot(m, m)
+ *       a = ee*dd - de*de,  b = ee*md - de*me,  c = ee*(mm - rr) - me*me,  disc = b*b - a*c,  t = (-b - sqrt(disc)) / a
+ *       sg = (me + t*de) / ee
+ *       conditions: ee > 0, a > 0, b < 0, c > 0, disc >= 0, 0 <= sg <= 1;   contact_k = P0_k + e_k*sg
+ *  3. No candidate taken: the pair has no value.
+ *
+ * Answer per sweep: t32 = (float)t.  Over all triangles i of the uploaded array the winner is the smallest pair (t32_i, i) in
+ * lexicographic order: of bit-equal t32 the lowest build-order index wins -- in particular among several triangles overlapped
+ * at the start.
+ *   a winner:  t = t32, prim = i, region;  point = contact;  center_k = o_k + t*d_k with the binary64 t;  normal_k = (center_k -
+ *              contact_k) / r, or (0, 0, 0) when r == 0 -- unit length at a contact, shorter at an initial overlap, where its
+ *              length is distance / r.  Each is rounded to binary32 once.
+ *   none:      t = tmax as given (1 when tmax is NULL), prim = -1, region = 0, center = point = o_k + tmax*d_k, normal = 0
+ *   invalid:   t = +inf, prim = -1, region = 0, center = point = o as given, normal = 0.  A sweep is invalid when o or d has a
+ *              NaN or infinite component, or its radius or its tmax is NaN, negative or infinite.
+ * r = 0 is allowed (a two-sided swept point); d = 0 is allowed (only the overlap rule can answer).  A scene without triangles
+ * answers every valid sweep with "none".  The value is within 4e-12 units of t of a sampled-and-bisected
+ * binary64 truth on the test families (DESIGN.md "Swept-sphere queries" has the table); hit or miss can differ from it only for a path that grazes:
+ * least clearance within rounding of r.
+ *
+ * Scope of the guarantee, arrays (DEVICE pointers, contiguous, indexed with 64-bit offsets), n up to 2^31 - 1 and n == 0,
+ * streams, the device, "touches no render state", tyr_scene_refit and bit 1 of tyr_query_error are tyr_query_nearest's:
+ * origins, directions n x 3; radius n; tmax n or NULL; out->t, out->prim n (required); out->region n, out->point, out->center,
+ * out->normal n x 3 (each may be NULL).
+ * TYR_ERR_INVALID: ctx, origins, directions, radius, out, out->t or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE:
+ * nothing uploaded.
+ * Not part of it: the sphere table (flags must be 0), capsules and boxes, all contacts rather than the first, rotating or
+ * deforming bodies, triangles that move during the sweep, penetration depth beyond what `normal` carries. */
+typedef struct tyr_sweep_out {
+	float*   t;       /* n, required */
+	int32_t* prim;    /* n, required: build-order index, -1 = none */
+	uint8_t* region;  /* n or NULL: 0 face, 1 2 3 vertices, 4 5 6 edges, numbered as tyr_query_nearest's */
+	float*   point;   /* n x 3 or NULL: the contact point on the triangle */
+	float*   center;  /* n x 3 or NULL: the sphere's centre at t */
+	float*   normal;  /* n x 3 or NULL: (center - point) / r */
+} tyr_sweep_out;
+int tyr_query_sweep(tyr_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* radius /* n */,
+                    const float* tmax /* n, or NULL: 1 = the whole displacement d */, uint32_t flags /* must be 0 */,
+                    const tyr_sweep_out* out, void* stream);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

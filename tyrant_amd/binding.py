@@ -139,6 +139,12 @@ class NearestKOut(C.Structure):
     _fields_ = [("dist2", P), ("prim", P), ("count", P), ("uv", P), ("region", P), ("point", P)]
 
 
+class SweepOut(C.Structure):
+    """tyr_sweep_out: device pointers of tyr_query_sweep's outputs; region, point, center, normal may be NULL"""
+
+    _fields_ = [("t", P), ("prim", P), ("region", P), ("point", P), ("center", P), ("normal", P)]
+
+
 class HitsOut(C.Structure):
     """tyr_hits_out: device pointers of tyr_query_hits's outputs; uv, side, back_count may be NULL"""
 
@@ -298,6 +304,7 @@ SYMBOLS = {
     "tyr_query_error": (C.c_int, [P, C.POINTER(c_u32), C.c_int]),
     "tyr_query_nearest": (C.c_int, [P, c_u32, P, P, c_u32, P, P]),
     "tyr_query_nearest_k": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
+    "tyr_query_sweep": (C.c_int, [P, c_u32, P, P, P, P, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
     "tyr_query_winding": (C.c_int, [P, c_u32, P, C.c_float, P, P, P]),
@@ -756,6 +763,33 @@ class Renderer:
         self._on_stream(stream, lambda h: self.L.tyr_query_nearest(self.h, n, p.data_ptr(), mp, 0, C.byref(out), h), staged)
         self._query_finish()
         return dist2, prim, uv, region, point
+
+    def query_sweep(self, origins, directions, radius, tmax=None, normal=False, stream=None):
+        """tyr_query_sweep: for every sphere of radius `radius` whose centre moves from `origins` along `directions`, the first
+        contact with the uploaded scene (include/tyr_c.h "Swept-sphere queries").  origins, directions: (N, 3) float32, radius: a
+        number or (N,), tmax: (N,) or None (1: the whole displacement) -- torch tensors on this ctx's device, taken as they are,
+        or numpy arrays.  Returns torch tensors (t, prim, region, point, center), and normal behind them with normal=True: without
+        a contact t = tmax, prim = -1 and center = point = the end of the path; an invalid sweep has t = +inf."""
+        import torch
+
+        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
+        if isinstance(radius, (int, float, np.floating, np.integer)):
+            r = torch.full((max(n, 0),), float(radius), dtype=torch.float32, device=dev)
+            staged = True  # filled on torch's current stream: `stream` has to wait for it like for a copied numpy input
+        else:
+            staged = staged or not isinstance(radius, torch.Tensor)
+            r = self._query_take(radius, "radius", (n,))
+        t = torch.empty(n, dtype=torch.float32, device=dev)
+        prim = torch.empty(n, dtype=torch.int32, device=dev)
+        region = torch.empty(n, dtype=torch.uint8, device=dev)
+        point = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        center = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if normal else None
+        out = SweepOut(t.data_ptr(), prim.data_ptr(), region.data_ptr(), point.data_ptr(), center.data_ptr(), nrm.data_ptr() if normal else None)
+        tp = tm.data_ptr() if tm is not None else None
+        self._on_stream(stream, lambda h: self.L.tyr_query_sweep(self.h, n, o.data_ptr(), d.data_ptr(), r.data_ptr(), tp, 0, C.byref(out), h), staged)
+        self._query_finish()
+        return (t, prim, region, point, center, nrm) if normal else (t, prim, region, point, center)
 
     def query_nearest_k(self, points, k, max_dist=None, count=False, stream=None):
         """tyr_query_nearest_k: for every point the k nearest triangles of the uploaded scene inside max_dist (include/tyr_c.h
