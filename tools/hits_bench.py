@@ -25,17 +25,10 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402  (before the library: one HIP runtime in the process, see tests/conftest.py)
 
-import numpy as np  # noqa: E402
-
+from query_bench_common import camera_rays, stats, timed_rounds  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
 N = 1 << 21
-
-
-def stats(samples_ms, n):
-    s = np.sort(np.asarray(samples_ms))
-    med, p10, p90 = float(np.median(s)), float(np.percentile(s, 10)), float(np.percentile(s, 90))
-    return {"items": int(n), "median_ms": med, "p10_ms": p10, "p90_ms": p90, "mitems_s": n / med / 1e3, "mitems_s_p10_p90": [n / p90 / 1e3, n / p10 / 1e3]}
 
 
 def main():
@@ -47,13 +40,7 @@ def main():
     sc = scenes.mesh_scene()
     g = binding.Renderer(64, 64, 4096)
     g.build_upload(sc.triangles)
-    cam = sc.camera
-    ys, xs = np.meshgrid(np.linspace(-0.6, 0.6, 1024, dtype=np.float32), np.linspace(-0.9, 0.9, 2048, dtype=np.float32), indexing="ij")
-    fwd, up = np.asarray(cam.direction, np.float32), np.asarray(cam.up, np.float32)
-    right = np.cross(fwd, up).astype(np.float32)
-    dirs = fwd[None, :] + xs.reshape(-1, 1) * right[None, :] + ys.reshape(-1, 1) * up[None, :]
-    dirs = (dirs / np.linalg.norm(dirs, axis=1, keepdims=True)).astype(np.float32)
-    origins = np.tile(np.asarray(cam.position, np.float32), (N, 1))
+    origins, dirs = camera_rays(sc.camera)  # (2048 x 1024 = N)
 
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
@@ -104,21 +91,8 @@ def main():
     for b in ("empty_miss", "empty_short"):
         launches[f"{b}/any"] = any_(b)
         launches[f"{b}/hits_4"] = hits(b, 4, 0)
-    torch.cuda.synchronize()
-    samples = {k: [] for k in launches}
-    for rep in range(args.reps + 2):  # two warm-up rounds
-        for name, (n, launch) in launches.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            rc = launch()
-            b.record(stream)
-            if rc:
-                raise binding.TyrError(rc, name)
-            b.synchronize()
-            if rep >= 2:
-                samples[name].append(a.elapsed_time(b))
-    assert g.query_error() == 0
-    res = {k: stats(v, launches[k][0]) for k, v in samples.items()}
+    samples = timed_rounds(g, {k: launch for k, (_, launch) in launches.items()}, stream, args.reps)
+    res = {k: stats(v, launches[k][0], count=True) for k, v in samples.items()}
     ratio = {b: res[f"{b}/hits_4"]["median_ms"] / res[f"{b}/any"]["median_ms"] for b in ("empty_miss", "empty_short")}
     c = count.to(torch.int64)
     result = {"scene": sc.name, "triangles": int(sc.triangles.shape[0]), "device": torch.cuda.get_device_name(0), "reps": args.reps, "rays": N,

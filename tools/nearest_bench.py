@@ -25,15 +25,10 @@ import torch  # noqa: E402  (before the library: one HIP runtime in the process,
 
 import numpy as np  # noqa: E402
 
+from query_bench_common import c3_points, camera_rays, stats, timed_rounds  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
 N = 1 << 21
-
-
-def stats(samples_ms, n):
-    s = np.sort(np.asarray(samples_ms))
-    med, p10, p90 = float(np.median(s)), float(np.percentile(s, 10)), float(np.percentile(s, 90))
-    return {"median_ms": med, "p10_ms": p10, "p90_ms": p90, "mitems_s": n / med / 1e3, "mitems_s_p10_p90": [n / p90 / 1e3, n / p10 / 1e3]}
 
 
 def main():
@@ -45,27 +40,14 @@ def main():
     sc = scenes.mesh_scene()
     g = binding.Renderer(64, 64, 4096)
     nodes, prims, _ = g.build_upload(sc.triangles)
-    rng = np.random.default_rng(2025)
-    lo, hi = nodes[0]["bounds"][0].astype(np.float32), nodes[0]["bounds"][1].astype(np.float32)
-    pad = (hi - lo) * np.float32(0.1)
-    uniform = ((lo - pad) + (hi - lo + 2 * pad) * rng.random((N, 3))).astype(np.float32)
-    i = rng.integers(0, prims.shape[0], N)
-    u = rng.random(N)
-    v = rng.random(N) * (1 - u)
-    surface = (prims["vert"][i] + u[:, None] * prims["e1"][i] + v[:, None] * prims["e2"][i] + rng.uniform(-0.5, 0.5, (N, 3))).astype(np.float32)
-    cam = sc.camera
-    ys, xs = np.meshgrid(np.linspace(-0.6, 0.6, 1024, dtype=np.float32), np.linspace(-0.9, 0.9, 2048, dtype=np.float32), indexing="ij")
-    fwd, up = np.asarray(cam.direction, np.float32), np.asarray(cam.up, np.float32)
-    right = np.cross(fwd, up).astype(np.float32)
-    dirs = fwd[None, :] + xs.reshape(-1, 1) * right[None, :] + ys.reshape(-1, 1) * up[None, :]
-    dirs = (dirs / np.linalg.norm(dirs, axis=1, keepdims=True)).astype(np.float32)
-    origins = np.tile(np.asarray(cam.position, np.float32), (N, 1))
+    points = c3_points(nodes, prims, N)
+    origins, dirs = camera_rays(sc.camera)
 
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
     h = stream.cuda_stream
     on = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-    pu, ps, ro, rd = on(uniform), on(surface), on(origins), on(dirs)
+    pu, ps, ro, rd = on(points["uniform"]), on(points["surface"]), on(origins), on(dirs)
     d2, prim, uv = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.int32, device=dev), torch.empty((N, 2), dtype=torch.float32, device=dev)
     region, point = torch.empty(N, dtype=torch.uint8, device=dev), torch.empty((N, 3), dtype=torch.float32, device=dev)
     rt, rprim, rgeom = torch.empty(N, dtype=torch.float32, device=dev), torch.empty(N, dtype=torch.int32, device=dev), torch.empty(N, dtype=torch.int32, device=dev)
@@ -80,20 +62,7 @@ def main():
         "nearest_surface": nearest(ps),
         "closest_camera_rays": lambda: L.tyr_query_closest(g.h, N, ro.data_ptr(), rd.data_ptr(), None, 0, rt.data_ptr(), rprim.data_ptr(), rgeom.data_ptr(), None, h),
     }
-    torch.cuda.synchronize()
-    samples = {k: [] for k in launches}
-    for rep in range(args.reps + 2):  # two warm-up rounds
-        for name, launch in launches.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            rc = launch()
-            b.record(stream)
-            if rc:
-                raise binding.TyrError(rc, name)
-            b.synchronize()
-            if rep >= 2:
-                samples[name].append(a.elapsed_time(b))
-    assert g.query_error() == 0
+    samples = timed_rounds(g, launches, stream, args.reps)
     result = {"scene": sc.name, "triangles": int(sc.triangles.shape[0]), "device": torch.cuda.get_device_name(0), "reps": args.reps, "items": N,
               "batches": {k: stats(v, N) for k, v in samples.items()}, "kernel_time": "not measured here: rocprofv3 --kernel-trace --stats in a run of its own"}
     # what the last nearest launch (the surface batch) found

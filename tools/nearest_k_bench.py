@@ -26,19 +26,12 @@ sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402  (before the library: one HIP runtime in the process, see tests/conftest.py)
 
-import numpy as np  # noqa: E402
-
+from query_bench_common import c3_points, stats, timed_rounds  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
 N = 1 << 21
 KS = (1, 8, 32)
 K_COUNT = 8
-
-
-def stats(samples_ms, n):
-    s = np.sort(np.asarray(samples_ms))
-    med, p10, p90 = float(np.median(s)), float(np.percentile(s, 10)), float(np.percentile(s, 90))
-    return {"median_ms": med, "p10_ms": p10, "p90_ms": p90, "mitems_s": n / med / 1e3, "mitems_s_p10_p90": [n / p90 / 1e3, n / p10 / 1e3]}
 
 
 def main():
@@ -51,19 +44,11 @@ def main():
     sc = scenes.mesh_scene()
     g = binding.Renderer(64, 64, 4096)
     nodes, prims, _ = g.build_upload(sc.triangles)
-    rng = np.random.default_rng(2025)
-    lo, hi = nodes[0]["bounds"][0].astype(np.float32), nodes[0]["bounds"][1].astype(np.float32)
-    pad = (hi - lo) * np.float32(0.1)
-    uniform = ((lo - pad) + (hi - lo + 2 * pad) * rng.random((N, 3))).astype(np.float32)
-    i = rng.integers(0, prims.shape[0], N)
-    u = rng.random(N)
-    v = rng.random(N) * (1 - u)
-    surface = (prims["vert"][i] + u[:, None] * prims["e1"][i] + v[:, None] * prims["e2"][i] + rng.uniform(-0.5, 0.5, (N, 3))).astype(np.float32)
 
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
     h = stream.cuda_stream
-    sets = {"uniform": torch.from_numpy(uniform).to(dev), "surface": torch.from_numpy(surface).to(dev)}
+    sets = {name: torch.from_numpy(p).to(dev) for name, p in c3_points(nodes, prims, N).items()}
     radius = torch.full((N,), args.radius, dtype=torch.float32, device=dev)
     kmax = max(KS)
     d2, prim, uv = torch.empty((N, kmax), dtype=torch.float32, device=dev), torch.empty((N, kmax), dtype=torch.int32, device=dev), torch.empty((N, kmax, 2), dtype=torch.float32, device=dev)
@@ -81,23 +66,13 @@ def main():
         for k in KS:
             launches[f"nearest_k{k}_{name}"] = lambda p=p, k=k: L.tyr_query_nearest_k(g.h, N, p.data_ptr(), None, k, 0, C.byref(rows), h)
         launches[f"nearest_k{K_COUNT}_count_{name}"] = lambda p=p: L.tyr_query_nearest_k(g.h, N, p.data_ptr(), radius.data_ptr(), K_COUNT, 0, C.byref(counted), h)
-    torch.cuda.synchronize()
-    samples = {k: [] for k in launches}
     mean_count = {}
-    for rep in range(args.reps + 2):  # two warm-up rounds
-        for name, launch in launches.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            rc = launch()
-            b.record(stream)
-            if rc:
-                raise binding.TyrError(rc, name)
-            b.synchronize()
-            if rep >= 2:
-                samples[name].append(a.elapsed_time(b))
-            elif "_count_" in name:
-                mean_count[name] = float(count.double().mean().item())
-    assert g.query_error() == 0
+
+    def read_count(name, rep):
+        if rep < 2 and "_count_" in name:
+            mean_count[name] = float(count.double().mean().item())
+
+    samples = timed_rounds(g, launches, stream, args.reps, after=read_count)
     batches = {k: stats(v, N) for k, v in samples.items() if not k.startswith("untimed")}
     derived = {}
     for name in sets:

@@ -28,22 +28,8 @@ import torch  # noqa: E402  (before the library: one HIP runtime in the process,
 
 import numpy as np  # noqa: E402
 
+from query_bench_common import camera_rays, stats, timed_rounds  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
-
-
-def stats(samples_ms, n):
-    s = np.sort(np.asarray(samples_ms))
-    med, p10, p90 = float(np.median(s)), float(np.percentile(s, 10)), float(np.percentile(s, 90))
-    return {"items": int(n), "median_ms": med, "p10_ms": p10, "p90_ms": p90, "mitems_s": n / med / 1e3, "mitems_s_p10_p90": [n / p90 / 1e3, n / p10 / 1e3]}
-
-
-def camera_rays(cam, n_x=2048, n_y=1024):
-    ys, xs = np.meshgrid(np.linspace(-0.6, 0.6, n_y, dtype=np.float32), np.linspace(-0.9, 0.9, n_x, dtype=np.float32), indexing="ij")
-    fwd, up = np.asarray(cam.direction, np.float32), np.asarray(cam.up, np.float32)
-    right = np.cross(fwd, up).astype(np.float32)
-    dirs = fwd[None, :] + xs.reshape(-1, 1) * right[None, :] + ys.reshape(-1, 1) * up[None, :]
-    dirs = (dirs / np.linalg.norm(dirs, axis=1, keepdims=True)).astype(np.float32)
-    return np.tile(np.asarray(cam.position, np.float32), (n_x * n_y, 1)), dirs
 
 
 def main():
@@ -114,21 +100,8 @@ def main():
         launches[f"{k}/c_any_same_rays"] = (n * S, any_(k))
         launches[f"{k}/d_any_same_rays_reduced"] = (n * S, any_reduced(k))
     launches["camera/any"] = (co.shape[0], lambda: L.tyr_query_any(g.h, co.shape[0], co.data_ptr(), cd.data_ptr(), None, 0, occ_cam.data_ptr(), h))
-    torch.cuda.synchronize()
-    samples = {k: [] for k in launches}
-    for rep in range(args.reps + 2):  # two warm-up rounds
-        for name, (_, launch) in launches.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            rc = launch()
-            b.record(stream)
-            if rc:
-                raise binding.TyrError(rc, name)
-            b.synchronize()
-            if rep >= 2:
-                samples[name].append(a.elapsed_time(b))
-    assert g.query_error() == 0
-    res = {k: stats(v, launches[k][0]) for k, v in samples.items()}
+    samples = timed_rounds(g, {k: launch for k, (_, launch) in launches.items()}, stream, args.reps)
+    res = {k: stats(v, launches[k][0], count=True) for k, v in samples.items()}
     ratio = {}
     for k in dist:
         a, c = res[f"{k}/a_occlusion"], res[f"{k}/c_any_same_rays"]

@@ -17,7 +17,6 @@ import argparse
 import ctypes as C
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,15 +26,10 @@ import torch  # noqa: E402  (before the library: one HIP runtime in the process,
 
 import numpy as np  # noqa: E402
 
+from query_bench_common import stats  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
 W, H = 1920, 1080
-
-
-def stats(samples_ms, n):
-    med = statistics.median(samples_ms)
-    return {"median_ms": med, "min_ms": min(samples_ms), "max_ms": max(samples_ms), "mrays_s": n / med / 1e3,
-            "mrays_s_spread": [n / max(samples_ms) / 1e3, n / min(samples_ms) / 1e3]}
 
 
 def time_query(g, kind, o, d, outs, flags, reps, stream):
@@ -63,7 +57,7 @@ def time_query(g, kind, o, d, outs, flags, reps, stream):
         b.synchronize()
         samples.append(a.elapsed_time(b))
     assert g.query_error() == 0
-    return stats(samples, n)
+    return stats(samples, n, unit="rays", spread="min_max")
 
 
 def time_extend(g, rays, reps):
@@ -83,7 +77,7 @@ def time_extend(g, rays, reps):
         else:
             samples.append(ms)
         g.stage("end")
-    return stats(samples, n), q
+    return stats(samples, n, unit="rays", spread="min_max"), q
 
 
 def main():

@@ -25,28 +25,11 @@ import torch  # noqa: E402  (before the library: one HIP runtime in the process,
 
 import numpy as np  # noqa: E402
 
+from query_bench_common import c3_points, morton_order, stats, timed_rounds  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
 N = 1 << 21
 RADII = (0.0, 0.1, 1.0)
-
-
-def stats(samples_ms, n):
-    s = np.sort(np.asarray(samples_ms))
-    med, p10, p90 = float(np.median(s)), float(np.percentile(s, 10)), float(np.percentile(s, 90))
-    return {"median_ms": med, "p10_ms": p10, "p90_ms": p90, "mitems_s": n / med / 1e3, "mitems_s_p10_p90": [n / p90 / 1e3, n / p10 / 1e3]}
-
-
-def morton_order(p, lo, hi):
-    q = np.clip(((p - lo) / (hi - lo) * 1023.0), 0, 1023).astype(np.uint64)
-
-    def spread(x):
-        x = (x | (x << 16)) & 0x030000FF
-        x = (x | (x << 8)) & 0x0300F00F
-        x = (x | (x << 4)) & 0x030C30C3
-        return (x | (x << 2)) & 0x09249249
-
-    return np.argsort(spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2), kind="stable")
 
 
 def main():
@@ -58,15 +41,10 @@ def main():
     sc = scenes.mesh_scene()
     g = binding.Renderer(64, 64, 4096)
     nodes, prims, _ = g.build_upload(sc.triangles)
-    rng = np.random.default_rng(2025)
-    rng.random((N, 3))  # (tools/nearest_bench.py draws its uniform batch first)
-    i = rng.integers(0, prims.shape[0], N)
-    u = rng.random(N)
-    v = rng.random(N) * (1 - u)
-    surface = (prims["vert"][i] + u[:, None] * prims["e1"][i] + v[:, None] * prims["e2"][i] + rng.uniform(-0.5, 0.5, (N, 3))).astype(np.float32)
+    surface = c3_points(nodes, prims, N)["surface"]
     disp = np.random.default_rng(2026).uniform(-3.0, 3.0, (N, 3)).astype(np.float32)
     lo, hi = nodes[0]["bounds"][0].astype(np.float32), nodes[0]["bounds"][1].astype(np.float32)
-    order = morton_order(surface, lo, hi)
+    order = morton_order(np.clip((surface - lo) / (hi - lo) * 1023.0, 0, 1023))
 
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
@@ -85,23 +63,13 @@ def main():
         for r in RADII:
             launches[f"sweep_{name}_r{r:g}"] = lambda o=o, d=d, r=r: L.tyr_query_sweep(g.h, N, o.data_ptr(), d.data_ptr(), radius[r].data_ptr(), None, 0, C.byref(out), h)
         launches[f"closest_{name}"] = lambda o=o, d=d: L.tyr_query_closest(g.h, N, o.data_ptr(), d.data_ptr(), None, 0, rt.data_ptr(), rprim.data_ptr(), rgeom.data_ptr(), None, h)
-    torch.cuda.synchronize()
-    samples = {k: [] for k in launches}
     found = {}
-    for rep in range(args.reps + 2):  # two warm-up rounds
-        for name, launch in launches.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            rc = launch()
-            b.record(stream)
-            if rc:
-                raise binding.TyrError(rc, name)
-            b.synchronize()
-            if rep >= 2:
-                samples[name].append(a.elapsed_time(b))
-            if rep == 0 and name.startswith("sweep_"):
-                found[name] = {"hit_share": float((prim >= 0).float().mean().item()), "overlap_share_of_hits": float(((prim >= 0) & (t == 0)).sum().item() / max(int((prim >= 0).sum().item()), 1))}
-    assert g.query_error() == 0
+
+    def read_found(name, rep):
+        if rep == 0 and name.startswith("sweep_"):
+            found[name] = {"hit_share": float((prim >= 0).float().mean().item()), "overlap_share_of_hits": float(((prim >= 0) & (t == 0)).sum().item() / max(int((prim >= 0).sum().item()), 1))}
+
+    samples = timed_rounds(g, launches, stream, args.reps, after=read_found)
     result = {"scene": sc.name, "triangles": int(sc.triangles.shape[0]), "device": torch.cuda.get_device_name(0), "reps": args.reps, "items": N,
               "displacement": "uniform in [-3, 3] per axis", "batches": {k: stats(v, N) for k, v in samples.items()}, "found": found,
               "kernel_time": "not measured here: event times around each launch"}

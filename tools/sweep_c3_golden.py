@@ -23,16 +23,15 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import numpy as np  # noqa: E402
 
+from query_bench_common import surface_points  # noqa: E402
+
 N = 256
 F = np.float32
 
 
 def c3_sweeps(prims):
     rng = np.random.default_rng(31)
-    i = rng.integers(0, prims.shape[0], N)
-    u = rng.random(N)
-    v = rng.random(N) * (1 - u)
-    o = (prims["vert"][i] + u[:, None] * prims["e1"][i] + v[:, None] * prims["e2"][i] + rng.uniform(-1.5, 1.5, (N, 3))).astype(F)
+    o = surface_points(rng, prims, N, 1.5)
     d = rng.uniform(-3.0, 3.0, (N, 3)).astype(F)
     r = rng.uniform(0.0, 1.0, N).astype(F)
     r[::16] = 0

@@ -27,25 +27,8 @@ import torch  # noqa: E402  (before the library: one HIP runtime in the process,
 
 import numpy as np  # noqa: E402
 
+from query_bench_common import morton_order, stats, timed_rounds  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
-
-
-def stats(samples_ms, n):
-    s = np.sort(np.asarray(samples_ms))
-    med, p10, p90 = float(np.median(s)), float(np.percentile(s, 10)), float(np.percentile(s, 90))
-    return {"points": int(n), "median_ms": med, "p10_ms": p10, "p90_ms": p90, "mpoints_s": n / med / 1e3, "mpoints_s_p10_p90": [n / p90 / 1e3, n / p10 / 1e3]}
-
-
-def morton_order(points, lo, hi):
-    q = np.clip(((points.astype(np.float64) - lo) / (hi - lo) * 1024.0).astype(np.int64), 0, 1023)
-
-    def spread(x):
-        x = (x | (x << 16)) & 0x030000FF
-        x = (x | (x << 8)) & 0x0300F00F
-        x = (x | (x << 4)) & 0x030C30C3
-        return (x | (x << 2)) & 0x09249249
-
-    return np.argsort(spread(q[:, 0]) | (spread(q[:, 1]) << 1) | (spread(q[:, 2]) << 2), kind="stable")
 
 
 def lane_efficiency(terms):
@@ -82,7 +65,8 @@ def main():
     lo, hi = nodes[0]["bounds"][0].astype(np.float64), nodes[0]["bounds"][1].astype(np.float64)
     rng = np.random.default_rng(91)
     pts = (lo + (hi - lo) * rng.random((n, 3))).astype(np.float32)
-    orders = {"random": pts, "morton": pts[morton_order(pts, lo, hi)]}
+    cells = np.clip(((pts.astype(np.float64) - lo) / (hi - lo) * 1024.0).astype(np.int64), 0, 1023)
+    orders = {"random": pts, "morton": pts[morton_order(cells)]}
 
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
@@ -100,23 +84,9 @@ def main():
             launches[f"{order}/accuracy_{acc:g}"] = (n, lambda tp=tp, acc=acc: L.tyr_query_winding(g.h, n, tp.data_ptr(), acc, w.data_ptr(), None, h))
         m = args.exact_points
         launches[f"{order}/exact"] = (m, lambda tp=tp, m=m: L.tyr_query_winding(g.h, m, tp.data_ptr(), math.inf, w.data_ptr(), terms.data_ptr(), h))
-    torch.cuda.synchronize()
-    samples = {k: [] for k in launches}
-    for rep in range(args.reps + 2):  # two warm-up rounds
-        for name, (_, launch) in launches.items():
-            if name.endswith("exact") and rep > 3:
-                continue  # (seconds each: two timed rounds are enough for a scale)
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            rc = launch()
-            b.record(stream)
-            if rc:
-                raise binding.TyrError(rc, name)
-            b.synchronize()
-            if rep >= 2:
-                samples[name].append(a.elapsed_time(b))
-    assert g.query_error() == 0
-    res = {k: dict(stats(v, launches[k][0]), **walk.get(k, {})) for k, v in samples.items()}
+    # (the exact launches take seconds each: two timed rounds are enough for a scale)
+    samples = timed_rounds(g, {k: launch for k, (_, launch) in launches.items()}, stream, args.reps, rounds={k: 4 for k in launches if k.endswith("exact")})
+    res = {k: dict(stats(v, launches[k][0], unit="points", count=True), **walk.get(k, {})) for k, v in samples.items()}
     result = {"scene": sc.name, "triangles": int(sc.triangles.shape[0]), "device": torch.cuda.get_device_name(0), "reps": args.reps, "points": n,
               "moment_build": build, "launches": res, "kernel_time": "not measured here: event times around each launch"}
     g.close()

@@ -356,6 +356,11 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(P)
 
 
+def _dptrs(*tensors):
+    """the device pointers of torch tensors, None (a null pointer) for None"""
+    return [None if t is None else t.data_ptr() for t in tensors]
+
+
 # ---- host side of the hot path ---------------------------------------------------------------
 
 
@@ -626,20 +631,36 @@ class Renderer:
             raise ValueError(f"{what}: a contiguous float32 tensor of shape {shape} on {dev}, not {tuple(a.shape)} {a.dtype} on {a.device}")
         return a
 
+    def _query_inputs(self, *inputs, optional=()):
+        """a query's inputs, each (name, value, trailing shape): (n, tensors, staged).  n is the leading dimension of the first
+        input, which is (N, 3) -- or -1, a length no tensor has, so that another shape fails in _query_take; every value goes
+        through _query_take with the shape (n, *trailing), but an `optional` one that is None stays None; staged: some value
+        was not a tensor, so its copy was made on torch's current stream."""
+        import torch
+
+        staged = not all(isinstance(a, torch.Tensor) for _, a, _ in inputs if a is not None)
+        what, first, tail = inputs[0]
+        first = first if isinstance(first, torch.Tensor) else np.asarray(first)
+        n = first.shape[0] if first.ndim == 2 else -1
+        inputs = ((what, first, tail),) + inputs[1:]
+        return n, [None if a is None and what in optional else self._query_take(a, what, (n, *tail)) for what, a, tail in inputs], staged
+
     def _query_rays(self, origins, directions, tmax):
         """the caller's (N, 3) float32 CUDA tensors as they are (numpy arrays are copied to the ctx's device first)"""
+        return self._query_inputs(("origins", origins, (3,)), ("directions", directions, (3,)), ("tmax", tmax, ()), optional=("tmax",))
+
+    def _query_outputs(self, n, *specs):
+        """a query's outputs: one uninitialised (n, *shape) tensor on the ctx's device per (shape, dtype), None for a spec of None"""
         import torch
 
         dev = torch.device("cuda", self.device)
-        take = self._query_take
+        return [None if s is None else torch.empty((n, *s[0]), dtype=s[1], device=dev) for s in specs]
 
-        staged = not all(isinstance(a, torch.Tensor) for a in (origins, directions, tmax) if a is not None)
-        o = origins if isinstance(origins, torch.Tensor) else np.asarray(origins)
-        n = o.shape[0] if o.ndim == 2 else -1
-        o = take(o, "origins", (n, 3))
-        d = take(directions, "directions", (n, 3))
-        t = take(tmax, "tmax", (n,)) if tmax is not None else None
-        return dev, n, o, d, t, staged
+    def _query_call(self, name, stream, staged, *args):
+        """the C call `name`(ctx, *args, stream handle) on `stream` (see _on_stream), then the queries' device error bits"""
+        fn = getattr(self.L, name)
+        self._on_stream(stream, lambda h: fn(self.h, *args, h), staged, name)
+        self._query_finish()
 
     def _on_stream(self, stream, launch, staged, what="tyr_query"):
         """launch(handle) on `stream` (default: torch's current stream).  The default stream has no handle of its own (0 means
@@ -681,15 +702,8 @@ class Renderer:
             n = prims.numel() * prims.element_size() // 40
             if bboxes is not None and bboxes.numel() * bboxes.element_size() != 24 * n:
                 raise ValueError("bboxes: one 24-byte box per triangle")
-            s = stream if stream is not None else torch.cuda.current_stream(self.device)
-            h = s.cuda_stream
-            if h == 0:  # (0 would name the ctx's stream to the library: a side stream behind the default one carries the wait)
-                if self._side is None:
-                    self._side = torch.cuda.Stream(self.device)
-                self._side.wait_stream(s)
-                h = self._side.cuda_stream
-            bp = None if bboxes is None else bboxes.data_ptr()
-            _check(self.L.tyr_scene_refit(self.h, prims.data_ptr(), bp, n, TYR_REFIT_DEVICE, h, out), "tyr_scene_refit")
+            pp, bp = _dptrs(prims, bboxes)
+            self._on_stream(stream, lambda h: self.L.tyr_scene_refit(self.h, pp, bp, n, TYR_REFIT_DEVICE, h, out), False, "tyr_scene_refit")
         else:
             p = np.ascontiguousarray(prims, dtype=scenes.TRIANGLE_DTYPE)
             bb = None if bboxes is None else np.ascontiguousarray(bboxes, dtype=scenes.BBOX_DTYPE)
@@ -715,28 +729,19 @@ class Renderer:
         t = tmax with prim = geom = -1 and uv = (0, 0); geom 0 = sphere (prim = its index), 1 = triangle (prim = build order)."""
         import torch
 
-        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
-        t = torch.empty(n, dtype=torch.float32, device=dev)
-        prim = torch.empty(n, dtype=torch.int32, device=dev)
-        geom = torch.empty(n, dtype=torch.int32, device=dev)
-        uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
-        flags = TYR_QUERY_SPHERES if spheres else 0
-        tp = tm.data_ptr() if tm is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_closest(self.h, n, o.data_ptr(), d.data_ptr(), tp, flags, t.data_ptr(), prim.data_ptr(), geom.data_ptr(), uv.data_ptr(), h), staged)
-        self._query_finish()
-        return t, prim, geom, uv
+        n, ins, staged = self._query_rays(origins, directions, tmax)
+        outs = self._query_outputs(n, ((), torch.float32), ((), torch.int32), ((), torch.int32), ((2,), torch.float32))
+        self._query_call("tyr_query_closest", stream, staged, n, *_dptrs(*ins), TYR_QUERY_SPHERES if spheres else 0, *_dptrs(*outs))
+        return tuple(outs)
 
     def query_any(self, origins, directions, tmax=None, spheres=False, stream=None):
         """is anything hit within tmax (CachedBVH::intersectSimple, bvh.h:213-256; with spheres=True intersect_scene_simple,
         kernel.cu:163-174)?  Returns a bool torch tensor."""
         import torch
 
-        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
-        occ = torch.empty(n, dtype=torch.bool, device=dev)
-        flags = TYR_QUERY_SPHERES if spheres else 0
-        tp = tm.data_ptr() if tm is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_any(self.h, n, o.data_ptr(), d.data_ptr(), tp, flags, occ.data_ptr(), h), staged)
-        self._query_finish()
+        n, ins, staged = self._query_rays(origins, directions, tmax)
+        (occ,) = self._query_outputs(n, ((), torch.bool))
+        self._query_call("tyr_query_any", stream, staged, n, *_dptrs(*ins), TYR_QUERY_SPHERES if spheres else 0, occ.data_ptr())
         return occ
 
     def query_nearest(self, points, max_dist=None, stream=None):
@@ -746,23 +751,11 @@ class Renderer:
         an invalid point or max_dist), prim = -1, uv = (0, 0), region = 0 and point = the query point."""
         import torch
 
-        dev = torch.device("cuda", self.device)
-        take = self._query_take
-        staged = not all(isinstance(a, torch.Tensor) for a in (points, max_dist) if a is not None)
-        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
-        n = p.shape[0] if p.ndim == 2 else -1
-        p = take(p, "points", (n, 3))
-        md = take(max_dist, "max_dist", (n,)) if max_dist is not None else None
-        dist2 = torch.empty(n, dtype=torch.float32, device=dev)
-        prim = torch.empty(n, dtype=torch.int32, device=dev)
-        uv = torch.empty((n, 2), dtype=torch.float32, device=dev)
-        region = torch.empty(n, dtype=torch.uint8, device=dev)
-        point = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        out = NearestOut(dist2.data_ptr(), prim.data_ptr(), uv.data_ptr(), region.data_ptr(), point.data_ptr())
-        mp = md.data_ptr() if md is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_nearest(self.h, n, p.data_ptr(), mp, 0, C.byref(out), h), staged)
-        self._query_finish()
-        return dist2, prim, uv, region, point
+        n, ins, staged = self._query_inputs(("points", points, (3,)), ("max_dist", max_dist, ()), optional=("max_dist",))
+        outs = self._query_outputs(n, ((), torch.float32), ((), torch.int32), ((2,), torch.float32), ((), torch.uint8), ((3,), torch.float32))
+        out = NearestOut(*_dptrs(*outs))
+        self._query_call("tyr_query_nearest", stream, staged, n, *_dptrs(*ins), 0, C.byref(out))
+        return tuple(outs)
 
     def query_sweep(self, origins, directions, radius, tmax=None, normal=False, stream=None):
         """tyr_query_sweep: for every sphere of radius `radius` whose centre moves from `origins` along `directions`, the first
@@ -772,24 +765,18 @@ class Renderer:
         a contact t = tmax, prim = -1 and center = point = the end of the path; an invalid sweep has t = +inf."""
         import torch
 
-        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
+        n, (o, d, tm), staged = self._query_rays(origins, directions, tmax)
         if isinstance(radius, (int, float, np.floating, np.integer)):
-            r = torch.full((max(n, 0),), float(radius), dtype=torch.float32, device=dev)
+            r = torch.full((max(n, 0),), float(radius), dtype=torch.float32, device=o.device)
             staged = True  # filled on torch's current stream: `stream` has to wait for it like for a copied numpy input
         else:
             staged = staged or not isinstance(radius, torch.Tensor)
             r = self._query_take(radius, "radius", (n,))
-        t = torch.empty(n, dtype=torch.float32, device=dev)
-        prim = torch.empty(n, dtype=torch.int32, device=dev)
-        region = torch.empty(n, dtype=torch.uint8, device=dev)
-        point = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        center = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if normal else None
-        out = SweepOut(t.data_ptr(), prim.data_ptr(), region.data_ptr(), point.data_ptr(), center.data_ptr(), nrm.data_ptr() if normal else None)
-        tp = tm.data_ptr() if tm is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_sweep(self.h, n, o.data_ptr(), d.data_ptr(), r.data_ptr(), tp, 0, C.byref(out), h), staged)
-        self._query_finish()
-        return (t, prim, region, point, center, nrm) if normal else (t, prim, region, point, center)
+        vec = ((3,), torch.float32)
+        outs = self._query_outputs(n, ((), torch.float32), ((), torch.int32), ((), torch.uint8), vec, vec, vec if normal else None)
+        out = SweepOut(*_dptrs(*outs))
+        self._query_call("tyr_query_sweep", stream, staged, n, *_dptrs(o, d, r, tm), 0, C.byref(out))
+        return tuple(outs) if normal else tuple(outs[:5])
 
     def query_nearest_k(self, points, k, max_dist=None, count=False, stream=None):
         """tyr_query_nearest_k: for every point the k nearest triangles of the uploaded scene inside max_dist (include/tyr_c.h
@@ -804,23 +791,11 @@ class Renderer:
         if not 1 <= int(k) <= TYR_QUERY_NEAREST_K_MAX:
             raise ValueError(f"k: 1 .. {TYR_QUERY_NEAREST_K_MAX}")
         k = int(k)
-        dev = torch.device("cuda", self.device)
-        take = self._query_take
-        staged = not all(isinstance(a, torch.Tensor) for a in (points, max_dist) if a is not None)
-        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
-        n = p.shape[0] if p.ndim == 2 else -1
-        p = take(p, "points", (n, 3))
-        md = take(max_dist, "max_dist", (n,)) if max_dist is not None else None
-        dist2 = torch.empty((n, k), dtype=torch.float32, device=dev)
-        prim = torch.empty((n, k), dtype=torch.int32, device=dev)
-        cnt = torch.empty(n, dtype=torch.int32, device=dev) if count else None
-        uv = torch.empty((n, k, 2), dtype=torch.float32, device=dev)
-        region = torch.empty((n, k), dtype=torch.uint8, device=dev)
-        point = torch.empty((n, k, 3), dtype=torch.float32, device=dev)
-        out = NearestKOut(dist2.data_ptr(), prim.data_ptr(), cnt.data_ptr() if count else None, uv.data_ptr(), region.data_ptr(), point.data_ptr())
-        mp = md.data_ptr() if md is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_nearest_k(self.h, n, p.data_ptr(), mp, k, 0, C.byref(out), h), staged)
-        self._query_finish()
+        n, ins, staged = self._query_inputs(("points", points, (3,)), ("max_dist", max_dist, ()), optional=("max_dist",))
+        dist2, prim, cnt, uv, region, point = self._query_outputs(
+            n, ((k,), torch.float32), ((k,), torch.int32), ((), torch.int32) if count else None, ((k, 2), torch.float32), ((k,), torch.uint8), ((k, 3), torch.float32))
+        out = NearestKOut(*_dptrs(dist2, prim, cnt, uv, region, point))
+        self._query_call("tyr_query_nearest_k", stream, staged, n, *_dptrs(*ins), k, 0, C.byref(out))
         return (dist2, prim, uv, region, point, cnt) if count else (dist2, prim, uv, region, point)
 
     def query_hits(self, origins, directions, tmax=None, max_hits=4, two_sided=False, stream=None):
@@ -836,19 +811,11 @@ class Renderer:
         if not 1 <= int(max_hits) <= TYR_QUERY_HITS_MAX:
             raise ValueError(f"max_hits: 1 .. {TYR_QUERY_HITS_MAX}")
         k = int(max_hits)
-        dev, n, o, d, tm, staged = self._query_rays(origins, directions, tmax)
-        count = torch.empty(n, dtype=torch.int32, device=dev)
-        t = torch.empty((n, k), dtype=torch.float32, device=dev)
-        prim = torch.empty((n, k), dtype=torch.int32, device=dev)
-        uv = torch.empty((n, k, 2), dtype=torch.float32, device=dev)
-        side = torch.empty((n, k), dtype=torch.uint8, device=dev)
-        back = torch.empty(n, dtype=torch.int32, device=dev)
-        out = HitsOut(count.data_ptr(), t.data_ptr(), prim.data_ptr(), uv.data_ptr(), side.data_ptr(), back.data_ptr())
-        flags = TYR_QUERY_TWO_SIDED if two_sided else 0
-        tp = tm.data_ptr() if tm is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_hits(self.h, n, o.data_ptr(), d.data_ptr(), tp, k, flags, C.byref(out), h), staged)
-        self._query_finish()
-        return count, t, prim, uv, side, back
+        n, ins, staged = self._query_rays(origins, directions, tmax)
+        outs = self._query_outputs(n, ((), torch.int32), ((k,), torch.float32), ((k,), torch.int32), ((k, 2), torch.float32), ((k,), torch.uint8), ((), torch.int32))
+        out = HitsOut(*_dptrs(*outs))
+        self._query_call("tyr_query_hits", stream, staged, n, *_dptrs(*ins), k, TYR_QUERY_TWO_SIDED if two_sided else 0, C.byref(out))
+        return tuple(outs)
 
     def query_occlusion(self, points, normals, samples=64, max_dist=None, bias=1e-3, seed=0, spheres=False, mask=False, bent=False, rays=False, stream=None):
         """tyr_query_occlusion: for every point, `samples` cosine-weighted any-hit rays over the hemisphere of its normal, made on
@@ -864,25 +831,18 @@ class Renderer:
         if not 1 <= int(samples) <= TYR_QUERY_OCCLUSION_MAX_SAMPLES:
             raise ValueError(f"samples: 1 .. {TYR_QUERY_OCCLUSION_MAX_SAMPLES}")
         S = int(samples)
-        dev = torch.device("cuda", self.device)
-        take = self._query_take
-        staged = not all(isinstance(a, torch.Tensor) for a in (points, normals, max_dist) if a is not None)
-        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
-        n = p.shape[0] if p.ndim == 2 else -1
-        p = take(p, "points", (n, 3))
-        nr = take(normals, "normals", (n, 3))
-        md = take(max_dist, "max_dist", (n,)) if max_dist is not None else None
-        visible = torch.empty(n, dtype=torch.int32, device=dev)
-        m = torch.empty((n, (S + 31) // 32), dtype=torch.int32, device=dev) if (mask or bent) else None
-        b = torch.empty((n, 3), dtype=torch.float32, device=dev) if bent else None
-        origin = torch.empty((n, 3), dtype=torch.float32, device=dev) if rays else None
-        direction = torch.empty((n, S, 3), dtype=torch.float32, device=dev) if rays else None
-        out = OcclusionOut(*(None if t is None else t.data_ptr() for t in (visible, m, b, origin, direction)))
-        flags = TYR_QUERY_SPHERES if spheres else 0
-        mp = md.data_ptr() if md is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_occlusion(self.h, n, p.data_ptr(), nr.data_ptr(), mp, S, float(bias), int(seed) & 0xFFFFFFFF, flags, C.byref(out), h), staged)
-        self._query_finish()
-        return visible, m, b, origin, direction
+        n, ins, staged = self._query_inputs(("points", points, (3,)), ("normals", normals, (3,)), ("max_dist", max_dist, ()), optional=("max_dist",))
+        outs = self._query_outputs(
+            n,
+            ((), torch.int32),
+            (((S + 31) // 32,), torch.int32) if (mask or bent) else None,
+            ((3,), torch.float32) if bent else None,
+            ((3,), torch.float32) if rays else None,
+            ((S, 3), torch.float32) if rays else None,
+        )
+        out = OcclusionOut(*_dptrs(*outs))
+        self._query_call("tyr_query_occlusion", stream, staged, n, *_dptrs(*ins), S, float(bias), int(seed) & 0xFFFFFFFF, TYR_QUERY_SPHERES if spheres else 0, C.byref(out))
+        return tuple(outs)
 
     def query_winding(self, points, accuracy=2.0, terms=False, stream=None):
         """tyr_query_winding: the generalised winding number of the uploaded triangles at every point (include/tyr_c.h "Winding
@@ -892,16 +852,9 @@ class Renderer:
         terms=True (w, terms) with terms (N, 2) int32 (the library's uint32): the dipoles and triangles summed for the point."""
         import torch
 
-        dev = torch.device("cuda", self.device)
-        staged = not isinstance(points, torch.Tensor)
-        p = points if isinstance(points, torch.Tensor) else np.asarray(points)
-        n = p.shape[0] if p.ndim == 2 else -1
-        p = self._query_take(p, "points", (n, 3))
-        w = torch.empty(n, dtype=torch.float32, device=dev)
-        t = torch.empty((n, 2), dtype=torch.int32, device=dev) if terms else None
-        tp = t.data_ptr() if t is not None else None
-        self._on_stream(stream, lambda h: self.L.tyr_query_winding(self.h, n, p.data_ptr(), float(accuracy), w.data_ptr(), tp, h), staged, "tyr_query_winding")
-        self._query_finish()
+        n, (p,), staged = self._query_inputs(("points", points, (3,)))
+        w, t = self._query_outputs(n, ((), torch.float32), ((2,), torch.int32) if terms else None)
+        self._query_call("tyr_query_winding", stream, staged, n, p.data_ptr(), float(accuracy), *_dptrs(w, t))
         return (w, t) if terms else w
 
     def scene_moments(self, first=0, count=None) -> np.ndarray:
@@ -938,15 +891,14 @@ class Renderer:
             res["geom"] = torch.zeros((self.H, self.W), dtype=torch.int32, device=dev)
         out = AovOut(*(res[k].data_ptr() if k in res else None for k in ("albedo", "normal", "depth", "prim", "geom")))
         if max_chain is None:
-            self._on_stream(stream, lambda h: self.L.tyr_render_aov(self.h, spp, C.byref(out), h), True)
+            self._query_call("tyr_render_aov", stream, True, spp, C.byref(out))
         else:
             for k in ("chain", "end_prim", "end_geom"):
                 res[k] = torch.zeros((self.H, self.W), dtype=torch.int32, device=dev)
             for k in ("length0", "depth_first"):
                 res[k] = torch.zeros((self.H, self.W), dtype=torch.float32, device=dev)
             ext = AovChainOut(*(res[k].data_ptr() for k in ("chain", "end_prim", "end_geom", "length0", "depth_first")))
-            self._on_stream(stream, lambda h: self.L.tyr_render_aov_chain(self.h, spp, max_chain, C.byref(out), C.byref(ext), h), True)
-        self._query_finish()
+            self._query_call("tyr_render_aov_chain", stream, True, spp, max_chain, C.byref(out), C.byref(ext))
         return res
 
     def denoise(self, albedo, normal, depth, accum=None, passes=DENOISE_PASSES, sigma_color=DENOISE_SIGMA_COLOR, sigma_depth=DENOISE_SIGMA_DEPTH,

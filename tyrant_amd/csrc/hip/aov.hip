@@ -274,13 +274,11 @@ __global__ void __launch_bounds__(kBlock, 5) k_render_aov(const AovParams P) { a
 __global__ void __launch_bounds__(kBlock, 4) k_render_chain(const AovChainParams P) { aov_body<true>(P.a); }
 
 void launch_aov(const AovParams& P, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{}; // the occupancy query's answer, as the queries' launches
-	hipLaunchKernelGGL(k_render_aov, dim3(persistent_blocks(k_render_aov, P.nPixels, t, numCUs, lc.perCU[kLcQuery][4])), dim3(kBlock), 0, stream, P);
+	launch_persistent(k_render_aov, P, P.nPixels, numCUs, lc.perCU[kLcQuery][4], stream);
 }
 
 void launch_aov_chain(const AovChainParams& P, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{};
-	hipLaunchKernelGGL(k_render_chain, dim3(persistent_blocks(k_render_chain, P.a.nPixels, t, numCUs, lc.perCU[kLcQuery][5])), dim3(kBlock), 0, stream, P);
+	launch_persistent(k_render_chain, P, P.a.nPixels, numCUs, lc.perCU[kLcQuery][5], stream);
 }
 
 } // namespace tyr

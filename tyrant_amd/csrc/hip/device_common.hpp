@@ -300,4 +300,12 @@ static inline uint32_t persistent_blocks(K kernel, uint32_t nItems, const Tuning
 	return needed < resident ? (needed ? needed : 1) : resident;
 }
 
+// a query-like pass's launch (tyr_query_*, tyr_render_aov): `kernel` on a persistent grid for nItems with the ctx's cached
+// occupancy answer
+template <class K, class P>
+static inline void launch_persistent(K kernel, const P& params, uint32_t nItems, int numCUs, int& cachedPerCU, hipStream_t stream) {
+	const Tuning t{}; // the occupancy query's answer, never a tuning override: queries do not follow the render's launch shape
+	hipLaunchKernelGGL(kernel, dim3(persistent_blocks(kernel, nItems, t, numCUs, cachedPerCU)), dim3(kBlock), 0, stream, params);
+}
+
 } // namespace tyr

@@ -240,12 +240,7 @@ __global__ void __launch_bounds__(kBlock, 5) k_query_hits(const HitsParams P0) {
 }
 
 void launch_hits(const HitsParams& P, bool twoSided, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{}; // the occupancy query's answer, never a tuning override: queries do not follow the render's launch shape
-	int& cached = lc.perCU[kLcHits][twoSided ? 1 : 0];
-	if (twoSided)
-		hipLaunchKernelGGL((k_query_hits<true>), dim3(persistent_blocks(k_query_hits<true>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
-	else
-		hipLaunchKernelGGL((k_query_hits<false>), dim3(persistent_blocks(k_query_hits<false>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
+	launch_persistent(twoSided ? k_query_hits<true> : k_query_hits<false>, P, P.n, numCUs, lc.perCU[kLcHits][twoSided ? 1 : 0], stream);
 }
 
 } // namespace tyr

@@ -116,8 +116,7 @@ __global__ void __launch_bounds__(kBlock, 5) k_query_nearest(const NearestParams
 }
 
 void launch_nearest(const NearestParams& P, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{}; // the occupancy query's answer, never a tuning override: queries do not follow the render's launch shape
-	hipLaunchKernelGGL(k_query_nearest, dim3(persistent_blocks(k_query_nearest, P.n, t, numCUs, lc.perCU[kLcNearest][0])), dim3(kBlock), 0, stream, P);
+	launch_persistent(k_query_nearest, P, P.n, numCUs, lc.perCU[kLcNearest][0], stream);
 }
 
 } // namespace tyr

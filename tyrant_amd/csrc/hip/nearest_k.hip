@@ -172,12 +172,7 @@ __global__ void __launch_bounds__(kBlock, 5) k_query_nearest_k(const NearestKPar
 }
 
 void launch_nearest_k(const NearestKParams& P, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{}; // the occupancy query's answer, never a tuning override: queries do not follow the render's launch shape
-	int& cached = lc.perCU[kLcNearestK][P.count ? 1 : 0];
-	if (P.count)
-		hipLaunchKernelGGL((k_query_nearest_k<true>), dim3(persistent_blocks(k_query_nearest_k<true>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
-	else
-		hipLaunchKernelGGL((k_query_nearest_k<false>), dim3(persistent_blocks(k_query_nearest_k<false>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
+	launch_persistent(P.count ? k_query_nearest_k<true> : k_query_nearest_k<false>, P, P.n, numCUs, lc.perCU[kLcNearestK][P.count ? 1 : 0], stream);
 }
 
 } // namespace tyr

@@ -170,12 +170,7 @@ __global__ void __launch_bounds__(kBlock) k_occlusion_bent(const OcclusionBentPa
 }
 
 void launch_occlusion(const OcclusionParams& P, bool spheres, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{}; // the occupancy query's answer, never a tuning override: queries do not follow the render's launch shape
-	int& cached = lc.perCU[kLcOcclusion][spheres ? 1 : 0];
-	if (spheres)
-		hipLaunchKernelGGL((k_occlusion<true>), dim3(persistent_blocks(k_occlusion<true>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
-	else
-		hipLaunchKernelGGL((k_occlusion<false>), dim3(persistent_blocks(k_occlusion<false>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
+	launch_persistent(spheres ? k_occlusion<true> : k_occlusion<false>, P, P.n, numCUs, lc.perCU[kLcOcclusion][spheres ? 1 : 0], stream);
 }
 
 void launch_occlusion_bent(const OcclusionBentParams& P, hipStream_t stream) {

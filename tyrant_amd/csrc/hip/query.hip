@@ -135,19 +135,8 @@ template <bool SPHERES>
 __global__ void __launch_bounds__(kBlock, 5) k_query_any(const QueryParams P) { query_body<true, SPHERES>(P); }
 
 void launch_query(const QueryParams& P, bool any, bool spheres, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{}; // the occupancy query's answer, never a tuning override: queries do not follow the render's launch shape
-	int& cached = lc.perCU[kLcQuery][(any ? 2 : 0) + (spheres ? 1 : 0)];
-	if (any) {
-		if (spheres)
-			hipLaunchKernelGGL((k_query_any<true>), dim3(persistent_blocks(k_query_any<true>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
-		else
-			hipLaunchKernelGGL((k_query_any<false>), dim3(persistent_blocks(k_query_any<false>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
-	} else {
-		if (spheres)
-			hipLaunchKernelGGL((k_query_closest<true>), dim3(persistent_blocks(k_query_closest<true>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
-		else
-			hipLaunchKernelGGL((k_query_closest<false>), dim3(persistent_blocks(k_query_closest<false>, P.n, t, numCUs, cached)), dim3(kBlock), 0, stream, P);
-	}
+	const auto kernel = any ? (spheres ? k_query_any<true> : k_query_any<false>) : (spheres ? k_query_closest<true> : k_query_closest<false>);
+	launch_persistent(kernel, P, P.n, numCUs, lc.perCU[kLcQuery][(any ? 2 : 0) + (spheres ? 1 : 0)], stream);
 }
 
 } // namespace tyr

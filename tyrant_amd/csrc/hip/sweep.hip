@@ -391,8 +391,7 @@ __global__ void __launch_bounds__(kBlock, 3) k_query_sweep(const SweepParams P0)
 }
 
 void launch_sweep(const SweepParams& P, int numCUs, LaunchCache& lc, hipStream_t stream) {
-	const Tuning t{}; // the occupancy query's answer, never a tuning override: queries do not follow the render's launch shape
-	hipLaunchKernelGGL(k_query_sweep, dim3(persistent_blocks(k_query_sweep, P.n, t, numCUs, lc.perCU[kLcSweep][0])), dim3(kBlock), 0, stream, P);
+	launch_persistent(k_query_sweep, P, P.n, numCUs, lc.perCU[kLcSweep][0], stream);
 }
 
 } // namespace tyr

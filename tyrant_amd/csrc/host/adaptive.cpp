@@ -155,8 +155,7 @@ int tyr_allocate_samples(tyr_ctx* c, const float* error, const tyr_allocate_para
 	if (p.min_spp > p.max_spp || p.max_spp < 1u || p.max_spp > kMaxSpp || p.total >= (1ull << 32))
 		return TYR_ERR_INVALID;
 	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
+	if (int rc = scope.enter(c))
 		return rc;
 	const uint32_t P = c->localPixels, tiles = tiles_of(P);
 	// scratch: the per-block scans (8 bytes per pixel), the blocks' totals, the largest error's bits and the map's sum

@@ -3,7 +3,6 @@
 // guides"; the kernels are hip/aov.hip).  Each pass behaves like a query (host/query.cpp): it runs on the
 // caller's stream with a ticket word of that stream, its stack overflow bit goes to tyr_query_error, and a later refit or
 // scene change waits for it.  No render state is read back or written: the camera basis is computed here, not stored.
-#include <algorithm>
 #include <cstring>
 
 #include <hip/hip_runtime.h>
@@ -16,24 +15,18 @@ using namespace tyr::drv;
 
 namespace {
 
-// the checks, the stream's ticket and the kernel argument both passes share; `any`: the caller asked for some output
-int aov_setup(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, bool any, void* stream, DeviceScope& scope, hipStream_t& s, tyr_ctx::QueryStream*& qs, AovParams& P) {
+// the checks, the opened launch and the kernel argument both passes share; `any`: the caller asked for some output
+int aov_setup(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, bool any, void* stream, QueryLaunch& L, AovParams& P) {
 	if (!c || !out || spp == 0 || !any)
 		return TYR_ERR_INVALID;
 	if (static_cast<uint64_t>(spp) * c->localPixels >= (1ull << 32)) // the tickets s * P + p are 32-bit, as k_primary's
 		return TYR_ERR_INVALID;
 	if (!c->haveScene)
 		return TYR_ERR_NO_SCENE;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
-		return rc;
-	uint32_t* ticket = nullptr;
-	if (int rc = query_ticket(c, stream, s, qs, ticket))
+	if (int rc = L.open(c, stream))
 		return rc;
 
-	P.scene = c->scene;
-	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0))); // as the render's launches stage them
-	std::memcpy(P.spheres, c->spheres, sizeof(P.spheres));
+	query_fields(P, c, L);
 	P.W = c->cfg.width;
 	P.H = c->cfg.height;
 	P.rank = c->cfg.rank;
@@ -51,8 +44,6 @@ int aov_setup(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, bool any, void* 
 	P.depth = out->depth;
 	P.prim = out->prim;
 	P.geom = out->geom;
-	P.ticket = ticket;
-	P.error = c->dQuery;
 	P.nPixels = c->localPixels;
 	P.spp = spp;
 	return TYR_OK;
@@ -61,28 +52,22 @@ int aov_setup(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, bool any, void* 
 } // namespace
 
 int tyr_render_aov(tyr_ctx* c, uint32_t spp, const tyr_aov_out* out, void* stream) {
-	DeviceScope scope;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
+	QueryLaunch L;
 	AovParams P{};
 	const bool any = out && (out->albedo || out->normal || out->depth || out->prim || out->geom);
-	if (int rc = aov_setup(c, spp, out, any, stream, scope, s, qs, P))
+	if (int rc = aov_setup(c, spp, out, any, stream, L, P))
 		return rc;
-	launch_aov(P, c->numCUs, c->launchCache, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	launch_aov(P, c->numCUs, c->launchCache, L.s);
+	return L.close();
 }
 
 int tyr_render_aov_chain(tyr_ctx* c, uint32_t spp, uint32_t max_chain, const tyr_aov_out* out, const tyr_aov_chain_out* ext, void* stream) {
 	if (max_chain > TYR_AOV_CHAIN_MAX)
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
+	QueryLaunch L;
 	AovChainParams P{};
 	const bool any = out && (out->albedo || out->normal || out->depth || out->prim || out->geom || (ext && (ext->chain || ext->end_prim || ext->end_geom || ext->length0 || ext->depth_first)));
-	if (int rc = aov_setup(c, spp, out, any, stream, scope, s, qs, P.a))
+	if (int rc = aov_setup(c, spp, out, any, stream, L, P.a))
 		return rc;
 	if (ext) {
 		P.chain = ext->chain;
@@ -93,8 +78,6 @@ int tyr_render_aov_chain(tyr_ctx* c, uint32_t spp, uint32_t max_chain, const tyr
 	}
 	P.maxChain = max_chain;
 	P.triMaterials = (c->cfg.flags & TYR_FLAG_TRIANGLE_MATERIALS) ? 1u : 0u;
-	launch_aov_chain(P, c->numCUs, c->launchCache, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	launch_aov_chain(P, c->numCUs, c->launchCache, L.s);
+	return L.close();
 }

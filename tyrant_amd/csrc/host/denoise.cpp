@@ -61,8 +61,7 @@ int tyr_denoise(tyr_ctx* c, const tyr_denoise_in* in, const tyr_denoise_params* 
 	if (!accum)
 		return TYR_ERR_NO_BUFFER;
 	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
+	if (int rc = scope.enter(c))
 		return rc;
 	const size_t n = static_cast<size_t>(c->cfg.width) * c->cfg.height;
 	if (!c->dDenoise) {

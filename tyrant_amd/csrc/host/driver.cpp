@@ -97,6 +97,11 @@ int push_counters(tyr_ctx* c) {
 	return TYR_OK;
 }
 
+DevScene launch_scene(const tyr_ctx* c) {
+	DevScene sc = c->scene;
+	sc.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0)));
+	return sc;
+}
 
 FrameParams make_params(const tyr_ctx* c) {
 	FrameParams P{};
@@ -117,8 +122,7 @@ FrameParams make_params(const tyr_ctx* c) {
 	P.lensRadius = c->cam.lensRadius;
 	std::memcpy(P.spheres, c->spheres, sizeof(P.spheres));
 	P.sun = c->sun;
-	P.scene = c->scene;
-	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0)));
+	P.scene = launch_scene(c);
 	P.work = c->q[c->cur];
 	P.next = c->q[c->cur ^ 1];
 	P.shadow = c->shadow[c->iter & 1u];

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -45,6 +46,8 @@ bool finite_n(const float* p, int n);
 int use_device(tyr_ctx* c);
 int sync_counters(tyr_ctx* c);
 int push_counters(tyr_ctx* c);
+// the scene as a launch sees it (the render's and the queries' alike): the top of the tree staged as far as the tuning allows
+DevScene launch_scene(const tyr_ctx* c);
 FrameParams make_params(const tyr_ctx* c);
 void collect_timings_of(tyr_ctx* c, int set);
 void collect_timings(tyr_ctx* c);
@@ -68,9 +71,14 @@ bool merged_render(const tyr_ctx* c);
 int flush_pending_shadow(tyr_ctx* c);
 void stage_end(tyr_ctx* c);
 int check_device_error(const tyr_ctx* c);
-// restores the caller's current device on the way out (tyr_query_*, tyr_scene_refit, as tyr_bvh_build_device does)
+// enter(): makes the ctx's device current; the caller's is restored on the way out (tyr_query_*, tyr_scene_refit and the frame
+// filters, as tyr_bvh_build_device does)
 struct DeviceScope {
 	int prev = -1;
+	int enter(tyr_ctx* c) {
+		HIPCHK(hipGetDevice(&prev));
+		return use_device(c);
+	}
 	~DeviceScope() {
 		if (prev >= 0)
 			(void)hipSetDevice(prev);
@@ -89,10 +97,35 @@ int winding_build(tyr_ctx* c, const tyr_bvh_node* dNodes, const tyr_bvh_node* ho
 void winding_free(tyr_ctx* c);
 // host/query.cpp: wait for the ctx's queries in flight on any stream; free their device words (tyr_destroy)
 int query_wait(tyr_ctx* c);
-// ... and open a launch of a query-like pass (tyr_query_*, tyr_render_aov) on the caller's `stream` (NULL: the ctx's): s = the
-// stream, qs = its entry (record qs->done behind the launch: tyr_query_error, tyr_scene_refit and tyr_destroy wait for it),
-// ticket = its chunk ticket word, cleared on s.  The ctx's device must be current.
-int query_ticket(tyr_ctx* c, void* stream, hipStream_t& s, tyr_ctx::QueryStream*& qs, uint32_t*& ticket);
+// ... and the bracket round every launch of a query-like pass (tyr_query_*, tyr_render_aov, tyr_render_motion) on the caller's
+// `stream` (NULL: the ctx's).  open() goes in front of the launch: it makes the ctx's device current (the caller's comes back
+// when the object goes, on every way out), takes the stream's entry and clears its chunk ticket word on s.  close() goes behind
+// it: the launch's error, then the stream's `done` event, which tyr_query_error, tyr_scene_refit and tyr_destroy wait for.  An
+// entry with several launches opens and closes once per launch; work enqueued behind a close() needs a close() of its own.
+struct QueryLaunch {
+	hipStream_t s = nullptr;
+	uint32_t* ticket = nullptr;
+	int open(tyr_ctx* c, void* stream);
+	int close();
+
+private:
+	DeviceScope scope;
+	hipEvent_t done = nullptr;
+};
+// the fields every query's Params share, for a launch that is open
+template <class P>
+auto query_spheres(P& p, const tyr_ctx* c, int) -> decltype((void)p.spheres) {
+	std::memcpy(p.spheres, c->spheres, sizeof(p.spheres));
+}
+template <class P>
+void query_spheres(P&, const tyr_ctx*, long) {}
+template <class P>
+void query_fields(P& p, const tyr_ctx* c, const QueryLaunch& L) {
+	p.scene = launch_scene(c);
+	query_spheres(p, c, 0);
+	p.ticket = L.ticket;
+	p.error = c->dQuery;
+}
 // host/driver.cpp: the camera basis of the staged prologue (kernel.cu:699-700) for the ctx's current camera
 void camera_basis(const tyr_ctx* c, float right[3], float up[3]);
 // ... and for any camera at the ctx's width and height (tyr_render_motion's previous camera)

@@ -1,9 +1,7 @@
 // hits.cpp -- tyr_query_hits: batched multi-hit ray queries on the ctx's scene (include/tyr_c.h "Multi-hit queries"; the
 // kernel is hip/hits.hip).  A query like the ray queries of host/query.cpp: it reads and writes no render state, runs on the
-// caller's stream and goes through the same per-stream bookkeeping (query_ticket: the stream's chunk ticket and its `done`
+// caller's stream and goes through the same per-stream bookkeeping (QueryLaunch: the stream's chunk ticket and its `done`
 // event, which tyr_query_error, tyr_scene_refit and tyr_destroy wait for).
-#include <algorithm>
-
 #include <hip/hip_runtime.h>
 
 #include "../hip/hits.hpp"
@@ -21,19 +19,12 @@ int tyr_query_hits(tyr_ctx* c, uint32_t n, const float* origins, const float* di
 		return TYR_OK;
 	if (!origins || !directions || !out || !out->count || !out->t || !out->prim)
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
-		return rc;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
-	uint32_t* ticket = nullptr;
-	if (int rc = query_ticket(c, stream, s, qs, ticket))
+	QueryLaunch L;
+	if (int rc = L.open(c, stream))
 		return rc;
 
 	HitsParams P{};
-	P.scene = c->scene;
-	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0))); // as the render's launches stage them
+	query_fields(P, c, L);
 	P.origins = origins;
 	P.directions = directions;
 	P.tmax = tmax;
@@ -43,12 +34,8 @@ int tyr_query_hits(tyr_ctx* c, uint32_t n, const float* origins, const float* di
 	P.uv = out->uv;
 	P.side = out->side;
 	P.backCount = out->back_count;
-	P.ticket = ticket;
-	P.error = c->dQuery;
 	P.n = n;
 	P.maxHits = max_hits;
-	launch_hits(P, (flags & TYR_QUERY_TWO_SIDED) != 0u, c->numCUs, c->launchCache, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	launch_hits(P, (flags & TYR_QUERY_TWO_SIDED) != 0u, c->numCUs, c->launchCache, L.s);
+	return L.close();
 }

@@ -1,9 +1,7 @@
 // nearest.cpp -- tyr_query_nearest: batched closest-point queries on the ctx's scene (include/tyr_c.h "Closest-point
 // queries"; the kernel is hip/nearest.hip).  A query like the ray queries of host/query.cpp: it reads and writes no render
-// state, runs on the caller's stream and goes through the same per-stream bookkeeping (query_ticket: the stream's chunk ticket
+// state, runs on the caller's stream and goes through the same per-stream bookkeeping (QueryLaunch: the stream's chunk ticket
 // and its `done` event, which tyr_query_error, tyr_scene_refit and tyr_destroy wait for).
-#include <algorithm>
-
 #include <hip/hip_runtime.h>
 
 #include "../hip/nearest.hpp"
@@ -21,19 +19,12 @@ int tyr_query_nearest(tyr_ctx* c, uint32_t n, const float* points, const float* 
 		return TYR_OK;
 	if (!points || !out || !out->dist2 || !out->prim)
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
-		return rc;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
-	uint32_t* ticket = nullptr;
-	if (int rc = query_ticket(c, stream, s, qs, ticket))
+	QueryLaunch L;
+	if (int rc = L.open(c, stream))
 		return rc;
 
 	NearestParams P{};
-	P.scene = c->scene;
-	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0))); // as the render's launches stage them
+	query_fields(P, c, L);
 	P.points = points;
 	P.maxDist = max_dist;
 	P.dist2 = out->dist2;
@@ -41,11 +32,7 @@ int tyr_query_nearest(tyr_ctx* c, uint32_t n, const float* points, const float* 
 	P.uv = out->uv;
 	P.region = out->region;
 	P.point = out->point;
-	P.ticket = ticket;
-	P.error = c->dQuery;
 	P.n = n;
-	launch_nearest(P, c->numCUs, c->launchCache, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	launch_nearest(P, c->numCUs, c->launchCache, L.s);
+	return L.close();
 }

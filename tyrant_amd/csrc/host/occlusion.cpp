@@ -1,6 +1,6 @@
 // occlusion.cpp -- tyr_query_occlusion: batched ambient-occlusion queries on the ctx's scene (include/tyr_c.h "Occlusion
 // queries"; the kernels are hip/occlusion.hip).  A query like those of host/query.cpp and host/hits.cpp: it reads and writes no
-// render state, runs on the caller's stream and goes through the same per-stream bookkeeping (query_ticket: the stream's chunk
+// render state, runs on the caller's stream and goes through the same per-stream bookkeeping (QueryLaunch: the stream's chunk
 // ticket and its `done` event, which tyr_query_error, tyr_scene_refit and tyr_destroy wait for).
 //
 // A work item is a (point, sample) pair with a 32-bit index, so a batch goes out as launches of whole points with at most 2^31
@@ -8,7 +8,6 @@
 // front of the first launch: the kernel only ever adds to them.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include <hip/hip_runtime.h>
 
@@ -28,15 +27,8 @@ int tyr_query_occlusion(tyr_ctx* c, uint32_t n, const float* points, const float
 		return TYR_OK;
 	if (!points || !normals || !out || !out->visible || (out->bent && !out->mask))
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
-		return rc;
 
 	OcclusionParams P{};
-	P.scene = c->scene;
-	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0))); // as the render's launches stage them
-	std::memcpy(P.spheres, c->spheres, sizeof(P.spheres));
 	P.points = points;
 	P.normals = normals;
 	P.maxDist = max_dist;
@@ -50,24 +42,21 @@ int tyr_query_occlusion(tyr_ctx* c, uint32_t n, const float* points, const float
 
 	const size_t words = (samples + 31u) / 32u;
 	const uint32_t pointsPerLaunch = (1u << 31) / samples; // whole points, at most 2^31 items
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
+	QueryLaunch L;
 	for (uint32_t first = 0; first < n; first += pointsPerLaunch) {
-		uint32_t* ticket = nullptr;
-		if (int rc = query_ticket(c, stream, s, qs, ticket)) // (every launch: its ticket word is zero when it starts)
+		if (int rc = L.open(c, stream)) // (every launch: its ticket word is zero when it starts)
 			return rc;
 		if (first == 0) {
-			HIPCHK(hipMemsetAsync(out->visible, 0, static_cast<size_t>(n) * sizeof(uint32_t), s));
+			HIPCHK(hipMemsetAsync(out->visible, 0, static_cast<size_t>(n) * sizeof(uint32_t), L.s));
 			if (out->mask)
-				HIPCHK(hipMemsetAsync(out->mask, 0, static_cast<size_t>(n) * words * sizeof(uint32_t), s));
+				HIPCHK(hipMemsetAsync(out->mask, 0, static_cast<size_t>(n) * words * sizeof(uint32_t), L.s));
 		}
-		P.error = c->dQuery; // (query_ticket allocates the words on a ctx's first query)
-		P.ticket = ticket;
+		query_fields(P, c, L);
 		P.first = first;
 		P.n = std::min(pointsPerLaunch, n - first) * samples;
-		launch_occlusion(P, (flags & TYR_QUERY_SPHERES) != 0u, c->numCUs, c->launchCache, s);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(qs->done, s));
+		launch_occlusion(P, (flags & TYR_QUERY_SPHERES) != 0u, c->numCUs, c->launchCache, L.s);
+		if (int rc = L.close())
+			return rc;
 	}
 	if (out->bent) {
 		OcclusionBentParams B{};
@@ -79,9 +68,8 @@ int tyr_query_occlusion(tyr_ctx* c, uint32_t n, const float* points, const float
 		B.samples = samples;
 		B.bias = bias;
 		B.seed = seed;
-		launch_occlusion_bent(B, s);
-		HIPCHK(hipGetLastError());
-		HIPCHK(hipEventRecord(qs->done, s));
+		launch_occlusion_bent(B, L.s);
+		return L.close(); // (a record of its own: `done` has to lie behind this pass too)
 	}
 	return TYR_OK;
 }

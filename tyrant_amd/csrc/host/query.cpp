@@ -6,9 +6,6 @@
 // run one after another, so each stream the queries use gets a word of its own, cleared in front of every launch on that
 // stream.  Once every word has an owner, the least recently used one changes hands, and its new stream first waits for
 // the last launch that used it.
-#include <algorithm>
-#include <cstring>
-
 #include <hip/hip_runtime.h>
 
 #include "../hip/query.hpp"
@@ -69,20 +66,12 @@ int query_launch(tyr_ctx* c, bool any, uint32_t n, const float* origins, const f
 		return TYR_OK;
 	if (!origins || !directions || (any ? !occluded_out : (!t_out || !prim_out)))
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
-		return rc;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
-	uint32_t* ticket = nullptr;
-	if (int rc = query_ticket(c, stream, s, qs, ticket))
+	QueryLaunch L;
+	if (int rc = L.open(c, stream))
 		return rc;
 
 	QueryParams P{};
-	P.scene = c->scene;
-	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0))); // as the render's launches stage them
-	std::memcpy(P.spheres, c->spheres, sizeof(P.spheres));
+	query_fields(P, c, L);
 	P.origins = origins;
 	P.directions = directions;
 	P.tmax = tmax;
@@ -91,13 +80,9 @@ int query_launch(tyr_ctx* c, bool any, uint32_t n, const float* origins, const f
 	P.geom = geom_out;
 	P.uv = uv_out;
 	P.occluded = occluded_out;
-	P.ticket = ticket;
-	P.error = c->dQuery;
 	P.n = n;
-	launch_query(P, any, (flags & TYR_QUERY_SPHERES) != 0u, c->numCUs, c->launchCache, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	launch_query(P, any, (flags & TYR_QUERY_SPHERES) != 0u, c->numCUs, c->launchCache, L.s);
+	return L.close();
 }
 
 } // namespace
@@ -105,15 +90,26 @@ int query_launch(tyr_ctx* c, bool any, uint32_t n, const float* origins, const f
 namespace tyr {
 namespace drv {
 
-int query_ticket(tyr_ctx* c, void* stream, hipStream_t& s, tyr_ctx::QueryStream*& qs, uint32_t*& ticket) {
+int QueryLaunch::open(tyr_ctx* c, void* stream) {
+	if (scope.prev < 0) // (an entry's first launch)
+		if (int rc = scope.enter(c))
+			return rc;
 	if (int rc = query_words(c))
 		return rc;
 	s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+	tyr_ctx::QueryStream* qs = nullptr;
 	if (int rc = query_stream(c, s, qs))
 		return rc;
 	qs->lastUse = ++c->querySeq;
+	done = qs->done;
 	ticket = c->dQuery + (1 + qs->word) * kQueryWordStride;
 	HIPCHK(hipMemsetAsync(ticket, 0, sizeof(uint32_t), s));
+	return TYR_OK;
+}
+
+int QueryLaunch::close() {
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(done, s));
 	return TYR_OK;
 }
 
@@ -150,8 +146,7 @@ int tyr_query_error(tyr_ctx* ctx, uint32_t* bits_out, int reset) {
 	if (!ctx->dQuery)
 		return TYR_OK;
 	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(ctx))
+	if (int rc = scope.enter(ctx))
 		return rc;
 	if (int rc = query_wait(ctx))
 		return rc;

@@ -158,8 +158,7 @@ int tyr_scene_refit(tyr_ctx* c, const tyr_triangle* prims, const tyr_bbox* bboxe
 	if (!R.nodes)
 		return TYR_ERR_UNSUPPORTED; // (the upload could not keep its plan and said so)
 	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
+	if (int rc = scope.enter(c))
 		return rc;
 	hipStream_t s = c->stream;
 	// drop_scene's rules: behind everything queued on the ctx's stream (stream order) and the ctx's queries on other streams

@@ -1,9 +1,7 @@
 // sweep.cpp -- tyr_query_sweep: batched swept-sphere queries on the ctx's scene (include/tyr_c.h "Swept-sphere queries"; the
 // kernel is hip/sweep.hip).  A query like the closest-point queries of host/nearest.cpp: it reads and writes no render state,
-// runs on the caller's stream and goes through the same per-stream bookkeeping (query_ticket: the stream's chunk ticket and its
+// runs on the caller's stream and goes through the same per-stream bookkeeping (QueryLaunch: the stream's chunk ticket and its
 // `done` event, which tyr_query_error, tyr_scene_refit and tyr_destroy wait for).
-#include <algorithm>
-
 #include <hip/hip_runtime.h>
 
 #include "../hip/sweep.hpp"
@@ -22,19 +20,12 @@ int tyr_query_sweep(tyr_ctx* c, uint32_t n, const float* origins, const float* d
 		return TYR_OK;
 	if (!origins || !directions || !radius || !out || !out->t || !out->prim)
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
-		return rc;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
-	uint32_t* ticket = nullptr;
-	if (int rc = query_ticket(c, stream, s, qs, ticket))
+	QueryLaunch L;
+	if (int rc = L.open(c, stream))
 		return rc;
 
 	SweepParams P{};
-	P.scene = c->scene;
-	P.scene.nStaged = std::min(c->scene.nStaged, static_cast<uint32_t>(std::max(c->tuning.stagedNodes, 0))); // as the render's launches stage them
+	query_fields(P, c, L);
 	P.origins = origins;
 	P.directions = directions;
 	P.radius = radius;
@@ -45,11 +36,7 @@ int tyr_query_sweep(tyr_ctx* c, uint32_t n, const float* origins, const float* d
 	P.point = out->point;
 	P.center = out->center;
 	P.normal = out->normal;
-	P.ticket = ticket;
-	P.error = c->dQuery;
 	P.n = n;
-	launch_sweep(P, c->numCUs, c->launchCache, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	launch_sweep(P, c->numCUs, c->launchCache, L.s);
+	return L.close();
 }

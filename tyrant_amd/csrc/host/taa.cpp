@@ -45,8 +45,7 @@ int tyr_taa(tyr_ctx* c, const tyr_taa_in* in, const tyr_taa_params* params, void
 	if (!(p.alpha > 0.f && p.alpha <= 1.f) || !(p.gamma >= 0.f && std::isfinite(p.gamma)) || (p.flags & ~(TYR_TAA_RESET | TYR_TAA_BILINEAR)) != 0u)
 		return TYR_ERR_INVALID;
 	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
+	if (int rc = scope.enter(c))
 		return rc;
 	const size_t n = static_cast<size_t>(c->cfg.width) * c->cfg.height;
 	if (!c->dTaaHist) {

@@ -60,14 +60,8 @@ int render_motion(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_chain_in
 		return TYR_ERR_INVALID;
 	if (!c->haveScene)
 		return TYR_ERR_NO_SCENE;
-	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
-		return rc;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
-	uint32_t* ticket = nullptr;
-	if (int rc = query_ticket(c, stream, s, qs, ticket))
+	QueryLaunch L; // (for its `done` event: a refit waits for the pass; the ticket word goes unused)
+	if (int rc = L.open(c, stream))
 		return rc;
 
 	MotionParams P{};
@@ -91,13 +85,11 @@ int render_motion(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_chain_in
 	P.prevDepth = out->prev_depth;
 	if (c->localPixels != 0) {
 		if (via)
-			launch_motion_chain(P, via->chain, via->length0, s);
+			launch_motion_chain(P, via->chain, via->length0, L.s);
 		else
-			launch_motion(P, s);
-		HIPCHK(hipGetLastError());
+			launch_motion(P, L.s);
 	}
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	return L.close();
 }
 
 } // namespace
@@ -123,8 +115,7 @@ int tyr_temporal(tyr_ctx* c, const tyr_temporal_in* in, const tyr_temporal_param
 	if (!accum)
 		return TYR_ERR_NO_BUFFER;
 	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
+	if (int rc = scope.enter(c))
 		return rc;
 	const size_t n = static_cast<size_t>(c->cfg.width) * c->cfg.height;
 	if (!c->dTemporal) {

@@ -1,7 +1,7 @@
 // winding.cpp -- tyr_query_winding and tyr_scene_moments: generalised winding numbers of the ctx's scene (include/tyr_c.h
 // "Winding numbers"; the kernels are hip/winding.hip).  A ctx with TYR_FLAG_WINDING keeps a moment tree beside its scene
 // (hip/winding.hpp WindingTree), built on the device by every upload path and rebuilt by tyr_scene_refit.  The query is one like
-// those of host/query.cpp: no render state, the caller's stream, the same per-stream bookkeeping (query_ticket: the stream's
+// those of host/query.cpp: no render state, the caller's stream, the same per-stream bookkeeping (QueryLaunch: the stream's
 // `done` event, which tyr_scene_refit, a scene change and tyr_destroy wait for; its ticket word goes unused -- the points are
 // dealt by block index).
 #include <cmath>
@@ -95,15 +95,10 @@ int tyr_query_winding(tyr_ctx* c, uint32_t n, const float* points, float accurac
 		return TYR_OK;
 	if (!points || !w_out)
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
+	QueryLaunch L;
+	if (int rc = L.open(c, stream))
 		return rc;
-	hipStream_t s = nullptr;
-	tyr_ctx::QueryStream* qs = nullptr;
-	uint32_t* ticket = nullptr;
-	if (int rc = query_ticket(c, stream, s, qs, ticket))
-		return rc;
+
 	WindingParams P{};
 	P.nodes = c->winding.nodes;
 	P.tris = c->dTris;
@@ -113,10 +108,8 @@ int tyr_query_winding(tyr_ctx* c, uint32_t n, const float* points, float accurac
 	P.n = n;
 	P.nNodes = c->winding.nNodes; // 0: a scene without triangles, every w = 0
 	P.accuracy = accuracy;
-	launch_winding(P, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(qs->done, s));
-	return TYR_OK;
+	launch_winding(P, L.s);
+	return L.close();
 }
 
 int tyr_scene_moments(tyr_ctx* c, int32_t first, int32_t count, double* host_out) {
@@ -133,8 +126,7 @@ int tyr_scene_moments(tyr_ctx* c, int32_t first, int32_t count, double* host_out
 	if (!host_out)
 		return TYR_ERR_INVALID;
 	DeviceScope scope;
-	HIPCHK(hipGetDevice(&scope.prev));
-	if (int rc = use_device(c))
+	if (int rc = scope.enter(c))
 		return rc;
 	try {
 		std::vector<WindingNode> rec(static_cast<size_t>(count));
