@@ -17,16 +17,16 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-import torch  # noqa: E402  (before the library: one HIP runtime in the process)
-
-from tyrant_amd import binding, scenes  # noqa: E402
-
-W, H, SPP = 1920, 1080, 8
+import frame_bench_common as fb  # noqa: E402  (torch before the library: one HIP runtime in the process)
+import torch  # noqa: E402
+from frame_bench_common import SPP, H, W  # noqa: E402
+from tyrant_amd import binding  # noqa: E402
 
 
 def summary(ms):
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "max_ms": max(ms), "n": len(ms)}
+    return fb.summary(ms, percentiles=False)
 
 
 def main():
@@ -35,28 +35,9 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "aov_bench_c3.json"))
     args = ap.parse_args()
-    sc = scenes.mesh_scene(args.cells)
-    g = binding.Renderer(W, H, SPP * W * H, flags=binding.TYR_FLAG_PROFILE | binding.TYR_FLAG_TRIANGLE_MATERIALS)
-    g.set_spheres(sc.spheres)
-    g.set_camera(sc.camera)
-    g.set_sun_position(*sc.sun_position)
-    nodes, prims, _ = g.build_upload(sc.triangles)
-
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
-    aov = {}
-    for spp in (1, SPP):
-        for _ in range(3):
-            g.render_aov(spp, stream=stream)
-        ms = []
-        for _ in range(args.reps):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            g.render_aov(spp, stream=stream)
-            b.record(stream)
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        aov[f"spp{spp}"] = summary(ms)
+    g, sc, nodes, prims = fb.c3_renderer(flags=binding.TYR_FLAG_PROFILE, cells=args.cells)
+    stream = torch.cuda.Stream(torch.device("cuda", 0))
+    aov = {f"spp{spp}": fb.timed(stream, args.reps, 3, lambda: g.render_aov(spp, stream=stream), percentiles=False) for spp in (1, SPP)}
 
     # the render's camera-ray launches: the first iteration of the same job, each on a fresh ctx (an empty queue at frame 1)
     prim_ms, ext_ms = [], []

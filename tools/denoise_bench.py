@@ -20,26 +20,20 @@ import argparse
 import csv
 import json
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402  (before the library: one HIP runtime in the process)
 
+import frame_bench_common as fb  # noqa: E402  (torch before the library: one HIP runtime in the process)
+import torch  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
-W, H, SPP = 1920, 1080, 8
 SIGMA_COLOR = (0.5, 1.0, 2.0, 4.0, 8.0, 16.0, 32.0, 64.0)
 SIGMA_DEPTH = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)
-
-
-def summary(ms):
-    q = np.percentile(ms, [10, 90])
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "p10_ms": float(q[0]), "p90_ms": float(q[1]), "max_ms": max(ms), "n": len(ms)}
 
 
 def guides(aov):
@@ -47,39 +41,17 @@ def guides(aov):
 
 
 def timing(calls, warmup):
-    sc = scenes.mesh_scene(706)
-    g = binding.Renderer(W, H, SPP * W * H, flags=binding.TYR_FLAG_TRIANGLE_MATERIALS)
-    g.set_spheres(sc.spheres)
-    g.set_camera(sc.camera)
-    g.set_sun_position(*sc.sun_position)
-    g.build_upload(sc.triangles)
-    aov = g.render_aov(SPP, ids=False)
-    render_ms = []
-    for _ in range(3):
-        g.reset_accum()
-        g.set_frame(1)
-        t0 = time.perf_counter()
-        g.render(SPP)
-        render_ms.append((time.perf_counter() - t0) * 1e3)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
+    g, _, _, _ = fb.c3_renderer()
+    aov = g.render_aov(fb.SPP, ids=False)
+    render = fb.timed_renders(g)
+    stream = torch.cuda.Stream(torch.device("cuda", 0))
     res = {}
     for resolve in (False, True):
-        for _ in range(warmup):
-            g.denoise(**guides(aov), resolve=resolve, stream=stream)
-        ms = []
-        for _ in range(calls):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record(stream)
-            g.denoise(**guides(aov), resolve=resolve, stream=stream)
-            b.record(stream)
-            b.synchronize()
-            ms.append(a.elapsed_time(b))
-        res["resolve" if resolve else "linear"] = summary(ms)
+        res["resolve" if resolve else "linear"] = fb.timed(stream, calls, warmup, lambda: g.denoise(**guides(aov), resolve=resolve, stream=stream))
     acc = g.blit_buffer()
     z = aov["depth"].cpu().numpy().reshape(-1)
     res["valid_pixel_fraction"] = float(((acc[:, 3] > 0) & (z < 1e20)).mean())
-    res["render_8spp"] = {"ms": render_ms, "median_ms": statistics.median(render_ms)}
+    res["render_8spp"] = render
     g.close()
     return res
 
@@ -93,28 +65,21 @@ def quality():
     aov = g.render_aov(4, ids=False)
     g.render(4)
     noisy = g.blit_buffer()
-    r = binding.Renderer(Wq, Hq, 1 << 20)
-    r.load_scene(sc, nodes, prims)
-    r.render(2048)
-    conv = r.blit_buffer()
-    r.close()
-    seen = (noisy[:, 3] > 0) & (conv[:, 3] > 0)
-    want = conv[seen, :3].astype(np.float64) / conv[seen, 3:]
-    mse = lambda a: float(((a.astype(np.float64) - want) ** 2).mean())
-    noisy_mse = mse(noisy[seen, :3] / noisy[seen, 3:])
+    _, mse = fb.reference(noisy, fb.converged(sc, nodes, prims, None, Wq, Hq, 2048, queue=1 << 20))
+    noisy_mse = mse(noisy[:, :3] / np.maximum(noisy[:, 3:], 1))
     grid = []
     for sc_ in SIGMA_COLOR:
         for sd in SIGMA_DEPTH:
-            out = g.denoise(**guides(aov), sigma_color=sc_, sigma_depth=sd).cpu().numpy().reshape(-1, 4)
-            grid.append({"sigma_color": sc_, "sigma_depth": sd, "mse": mse(out[seen, :3]), "ratio": mse(out[seen, :3]) / noisy_mse})
-    out = g.denoise(**guides(aov)).cpu().numpy().reshape(-1, 4)
+            out = g.denoise(**guides(aov), sigma_color=sc_, sigma_depth=sd).cpu().numpy()
+            grid.append({"sigma_color": sc_, "sigma_depth": sd, "mse": mse(out), "ratio": mse(out) / noisy_mse})
+    out = g.denoise(**guides(aov)).cpu().numpy()
     g.close()
     best = min(grid, key=lambda e: e["ratio"])
     return {"workload": "cornell_box, 256x256, 4 spp (guides: render_aov(4) at frame 1) against 2048 spp; linear rgb MSE", "noisy_mse": noisy_mse,
             "grid": grid, "best": best,
             "defaults": {"passes": binding.DENOISE_PASSES, "sigma_color": binding.DENOISE_SIGMA_COLOR, "sigma_depth": binding.DENOISE_SIGMA_DEPTH,
                          "normal_power_log2": binding.DENOISE_NORMAL_POWER_LOG2},
-            "ratio_at_defaults": mse(out[seen, :3]) / noisy_mse}
+            "ratio_at_defaults": mse(out) / noisy_mse}
 
 
 def kernel_stats(path):

@@ -32,9 +32,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402  (before the library: one HIP runtime in the process)
 
-import temporal_bench as tb  # noqa: E402
+import frame_bench_common as fb  # noqa: E402  (torch before the library: one HIP runtime in the process)
+import torch  # noqa: E402
 from tyrant_amd import binding, scenes  # noqa: E402
 
 MAX_CHAIN = 8
@@ -57,7 +57,7 @@ def mirror_room():
 
 def pan(cam, k):
     """tests/test_temporal.py's pan: 0.4 units along x and 0.002 rad about z per frame"""
-    return tb.moved(cam, k)
+    return fb.moved(cam, k)
 
 
 def guides(g, spp, prev, chain):
@@ -72,13 +72,7 @@ def guides(g, spp, prev, chain):
 
 
 def converged(sc, nodes, prims, cam, W, H, spp):
-    r = binding.Renderer(W, H, 1 << 18, flags=binding.TYR_FLAG_TRIANGLE_MATERIALS)
-    r.load_scene(sc, nodes, prims)
-    r.set_camera(cam)
-    r.render(spp)
-    b = r.blit_buffer()
-    r.close()
-    return b
+    return fb.converged(sc, nodes, prims, cam, W, H, spp, flags=binding.TYR_FLAG_TRIANGLE_MATERIALS)
 
 
 def quality(W=128, H=72, frames=16, ref_spp=1024):
@@ -169,16 +163,11 @@ def mirror_reprojection(W=128, H=72, steps=8, depth_tolerance=binding.TEMPORAL_D
 
 
 def timing(calls, warmup):
-    sc = scenes.mesh_scene(706)
-    g = binding.Renderer(tb.W, tb.H, 1 << 16, flags=binding.TYR_FLAG_TRIANGLE_MATERIALS)
-    g.set_spheres(sc.spheres)
-    g.set_sun_position(*sc.sun_position)
-    g.build_upload(sc.triangles)
-    g.set_camera(tb.moved(sc.camera, 3))
+    g, sc, _, _ = fb.c3_renderer(steps=3, queue=1 << 16)
     g.set_frame(1)
     dev = torch.device("cuda", 0)
     stream = torch.cuda.Stream(dev)
-    n = tb.W * tb.H
+    n = fb.W * fb.H
     f32 = lambda k: torch.zeros(n * k, dtype=torch.float32, device=dev)  # noqa: E731
     i32 = lambda: torch.zeros(n, dtype=torch.int32, device=dev)  # noqa: E731
     bufs = {"albedo": f32(3), "normal": f32(3), "depth": f32(1), "prim": i32(), "geom": i32(), "chain": i32(), "end_prim": i32(), "end_geom": i32(), "length0": f32(1), "depth_first": f32(1)}
@@ -188,17 +177,17 @@ def timing(calls, warmup):
     ext = binding.AovChainOut(*(bufs[k].data_ptr() for k in ("chain", "end_prim", "end_geom", "length0", "depth_first")))
     res = {}
     for spp in (1, 8):
-        r = {"render_aov": tb.timed(stream, calls, warmup, lambda: g.L.tyr_render_aov(g.h, spp, C.byref(out), stream.cuda_stream))}
+        r = {"render_aov": fb.timed(stream, calls, warmup, lambda: g.L.tyr_render_aov(g.h, spp, C.byref(out), stream.cuda_stream))}
         for mc in (0, 1, 4, 8):
-            r[f"render_aov_chain_{mc}"] = tb.timed(stream, calls, warmup, lambda: g.L.tyr_render_aov_chain(g.h, spp, mc, C.byref(out), C.byref(ext), stream.cuda_stream))
+            r[f"render_aov_chain_{mc}"] = fb.timed(stream, calls, warmup, lambda: g.L.tyr_render_aov_chain(g.h, spp, mc, C.byref(out), C.byref(ext), stream.cuda_stream))
             r[f"render_aov_chain_{mc}_over_render_aov"] = r[f"render_aov_chain_{mc}"]["median_ms"] / r["render_aov"]["median_ms"]
         res[f"spp{spp}"] = r
     torch.cuda.synchronize()
     aov = g.render_aov(1, max_chain=MAX_CHAIN)
     chain = aov["chain"].cpu().numpy().reshape(-1)
     res["coverage"] = {"share_chain_pixels": float((chain > 0).mean()), "histogram": np.bincount(chain, minlength=MAX_CHAIN + 1).tolist()}
-    res["render_motion"] = tb.timed(stream, calls, warmup, lambda: g.render_motion(aov["prim"], aov["geom"], sc.camera, stream=stream))
-    res["render_motion_chain"] = tb.timed(stream, calls, warmup, lambda: g.render_motion(aov["prim"], aov["geom"], sc.camera, chain=aov["chain"], length0=aov["length0"], stream=stream))
+    res["render_motion"] = fb.timed(stream, calls, warmup, lambda: g.render_motion(aov["prim"], aov["geom"], sc.camera, stream=stream))
+    res["render_motion_chain"] = fb.timed(stream, calls, warmup, lambda: g.render_motion(aov["prim"], aov["geom"], sc.camera, chain=aov["chain"], length0=aov["length0"], stream=stream))
     res["render_motion_chain_over_render_motion"] = res["render_motion_chain"]["median_ms"] / res["render_motion"]["median_ms"]
     assert g.query_error() == 0
     g.close()

@@ -15,7 +15,6 @@ tests/test_svgf.py bounds.  The grid runs svgf over the same rendered frames for
 from __future__ import annotations
 
 import argparse
-import dataclasses
 import json
 import os
 import sys
@@ -26,10 +25,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402  (before the library: one HIP runtime in the process)
 
-import temporal_bench as tb  # noqa: E402
-from tyrant_amd import binding, scenes  # noqa: E402
+import frame_bench_common as fb  # noqa: E402  (torch before the library: one HIP runtime in the process)
+import torch  # noqa: E402
+from tyrant_amd import binding  # noqa: E402
 
 MAX_HISTORY = (4, 8, 16)
 SIGMA_LUMINANCE = (1.0, 2.0, 4.0, 8.0, 16.0)
@@ -37,28 +36,19 @@ PASSES = (2, 3, 4, 5)
 
 
 def timing(calls, warmup):
-    sc = scenes.mesh_scene(706)
-    g = binding.Renderer(tb.W, tb.H, tb.SPP * tb.W * tb.H, flags=binding.TYR_FLAG_TRIANGLE_MATERIALS)
-    g.set_spheres(sc.spheres)
-    g.set_sun_position(*sc.sun_position)
-    g.build_upload(sc.triangles)
-    g.set_camera(tb.moved(sc.camera, 3))
-    g.set_frame(1)
-    aov = g.render_aov(1)
-    mot = g.render_motion(aov["prim"], aov["geom"], sc.camera)
+    g, sc, _, _ = fb.c3_renderer(steps=3)
+    _, gd, mv = fb.c3_guides(g, sc)
     g.reset_accum()
     g.set_frame(1)
-    g.render(tb.SPP)
+    g.render(fb.SPP)
     stream = torch.cuda.Stream(torch.device("cuda", 0))
-    gd = {k: aov[k] for k in ("albedo", "normal", "depth")}
-    mv = {"motion": mot["motion"], "prev_depth": mot["prev_depth"]}
     res = {}
     g.svgf(**gd, **mv, reset=True)
-    res["svgf"] = tb.timed(stream, calls, warmup, lambda: g.svgf(**gd, **mv, stream=stream))
+    res["svgf"] = fb.timed(stream, calls, warmup, lambda: g.svgf(**gd, **mv, stream=stream))
     g.temporal(**gd, **mv, reset=True)
-    res["temporal_denoise"] = tb.timed(stream, calls, warmup, lambda: g.denoise(**gd, accum=g.temporal(**gd, **mv, stream=stream), stream=stream))
-    res["temporal"] = tb.timed(stream, calls, warmup, lambda: g.temporal(**gd, **mv, stream=stream))
-    res["denoise"] = tb.timed(stream, calls, warmup, lambda: g.denoise(**gd, stream=stream))
+    res["temporal_denoise"] = fb.timed(stream, calls, warmup, lambda: g.denoise(**gd, accum=g.temporal(**gd, **mv, stream=stream), stream=stream))
+    res["temporal"] = fb.timed(stream, calls, warmup, lambda: g.temporal(**gd, **mv, stream=stream))
+    res["denoise"] = fb.timed(stream, calls, warmup, lambda: g.denoise(**gd, stream=stream))
     torch.cuda.synchronize()
     _, var = g.svgf(**gd, **mv, want_variance=True)
     res["svgf_over_temporal_denoise"] = res["svgf"]["median_ms"] / res["temporal_denoise"]["median_ms"]
@@ -68,30 +58,12 @@ def timing(calls, warmup):
 
 
 def quality(frames=16, ref_spp=1024, Wq=128, Hq=72):
-    sc = dataclasses.replace(scenes.cornell_box(), camera=scenes.FRAMED_CAMERA)
-    nodes, prims = binding.bvh_build(sc.triangles)
-    cams = [tb.moved(sc.camera, k) for k in range(frames)]
+    sc, nodes, prims, cams = fb.pan_scene(frames)
     g = binding.Renderer(Wq, Hq, 1 << 16)
     g.load_scene(sc, nodes, prims)
-    seq = []
-    prev = cams[0]
-    for cam in cams:
-        g.set_camera(cam)
-        aov = g.render_aov(1)
-        mot = g.render_motion(aov["prim"], aov["geom"], prev)
-        g.render(1)
-        seq.append((aov, mot, torch.from_numpy(g.blit_buffer()).to("cuda:0")))
-        prev = cam
-    r = binding.Renderer(Wq, Hq, 1 << 18)
-    r.load_scene(sc, nodes, prims)
-    r.set_camera(cams[-1])
-    r.render(ref_spp)
-    conv = r.blit_buffer()
-    r.close()
+    seq = [(aov, mot, torch.from_numpy(acc).to("cuda:0")) for aov, mot, acc in fb.pan_frames(g, cams)]
     noisy = seq[-1][2].cpu().numpy()
-    seen = (noisy[:, 3] > 0) & (conv[:, 3] > 0)
-    want = conv[seen, :3].astype(np.float64) / conv[seen, 3:]
-    mse = lambda a: float(((a.reshape(-1, 4)[seen, :3].astype(np.float64) - want) ** 2).mean())  # noqa: E731
+    seen, mse = fb.reference(noisy, fb.converged(sc, nodes, prims, cams[-1], Wq, Hq, ref_spp))
     last = seq[-1][0]
     gd = {k: last[k] for k in ("albedo", "normal", "depth")}
     for k, (aov, mot, acc) in enumerate(seq):

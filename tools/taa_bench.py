@@ -20,7 +20,6 @@ whose panning MSE is within 5 % of the grid's best -- the rule the shipped defau
 from __future__ import annotations
 
 import argparse
-import dataclasses
 import json
 import os
 import sys
@@ -31,10 +30,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402  (before the library: one HIP runtime in the process)
 
-import temporal_bench as tb  # noqa: E402
-from tyrant_amd import binding, scenes  # noqa: E402
+import frame_bench_common as fb  # noqa: E402  (torch before the library: one HIP runtime in the process)
+import torch  # noqa: E402
+from tyrant_amd import binding  # noqa: E402
 
 ALPHA = (0.05, 0.1, 0.2, 0.4)
 GAMMA = (0.75, 1.0, 1.25, 1.5)
@@ -56,25 +55,16 @@ def alternated(stream, calls, warmup, fns):
             b.record(stream)
             b.synchronize()
             ms[k].append(a.elapsed_time(b))
-    return {k: tb.summary(v) for k, v in ms.items()}
+    return {k: fb.summary(v) for k, v in ms.items()}
 
 
 def timing(calls, warmup):
-    sc = scenes.mesh_scene(706)
-    g = binding.Renderer(tb.W, tb.H, tb.SPP * tb.W * tb.H, flags=binding.TYR_FLAG_TRIANGLE_MATERIALS)
-    g.set_spheres(sc.spheres)
-    g.set_sun_position(*sc.sun_position)
-    g.build_upload(sc.triangles)
-    g.set_camera(tb.moved(sc.camera, 3))
-    g.set_frame(1)
-    aov = g.render_aov(1)
-    mot = g.render_motion(aov["prim"], aov["geom"], sc.camera)
+    g, sc, _, _ = fb.c3_renderer(steps=3)
+    aov, gd, mv = fb.c3_guides(g, sc)
     g.reset_accum()
     g.set_frame(1)
-    g.render(tb.SPP)
+    g.render(fb.SPP)
     stream = torch.cuda.Stream(torch.device("cuda", 0))
-    gd = {k: aov[k] for k in ("albedo", "normal", "depth")}
-    mv = {"motion": mot["motion"], "prev_depth": mot["prev_depth"]}
     color = g.svgf(**gd, **mv, reset=True, resolve=True)
     g.temporal(**gd, **mv, reset=True)
     out = torch.empty_like(color)
@@ -130,19 +120,11 @@ def figures(outs, refs):
 def sequence(g, sc, nodes, prims, cams, Wq, Hq, ref_spp):
     """the recipe up to svgf(resolve=True) for every camera, and the resolved references of the last TAIL frames"""
     seq = []
-    prev = cams[0]
-    for k, cam in enumerate(cams):
-        g.set_camera(cam)
-        g.reset_accum()
-        aov = g.render_aov(1)
-        mot = g.render_motion(aov["prim"], aov["geom"], prev)
-        g.render(1)
-        acc = g.blit_buffer()
+    for k, (aov, mot, acc) in enumerate(fb.pan_frames(g, cams, reset_accum=True)):
         # (a copy of the accumulation, as tools/svgf_bench.py passes it: the filter runs on torch's stream, and the next frame's
         # reset_accum on the ctx's would otherwise clear the buffer under it)
         sv = g.svgf(aov["albedo"], aov["normal"], aov["depth"], mot["motion"], mot["prev_depth"], accum=torch.from_numpy(acc).to("cuda:0"), reset=(k == 0), resolve=True)
         seq.append((sv, aov["depth"], mot["motion"], mot["prev_depth"], acc[:, 3] > 0))
-        prev = cam
     torch.cuda.synchronize()
     refs, cache = [], {}
     for k, cam in enumerate(cams):
@@ -165,11 +147,10 @@ def run_taa(g, seq, **kw):
 
 
 def quality(frames=16, ref_spp=1024, Wq=128, Hq=72):
-    sc = dataclasses.replace(scenes.cornell_box(), camera=scenes.FRAMED_CAMERA)
-    nodes, prims = binding.bvh_build(sc.triangles)
+    sc, nodes, prims, cams = fb.pan_scene(frames)
     g = binding.Renderer(Wq, Hq, 1 << 16)
     g.load_scene(sc, nodes, prims)
-    runs = {"panning": [tb.moved(sc.camera, k) for k in range(frames)], "still": [sc.camera] * frames}
+    runs = {"panning": cams, "still": [sc.camera] * frames}
     data = {}
     for name, cams in runs.items():
         seq, refs = sequence(g, sc, nodes, prims, cams, Wq, Hq, ref_spp)

@@ -17,114 +17,49 @@ bounds -- for the defaults and a small grid of max_history and depth_tolerance o
 from __future__ import annotations
 
 import argparse
-import dataclasses
 import json
-import math
 import os
-import statistics
 import sys
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import numpy as np  # noqa: E402
-import torch  # noqa: E402  (before the library: one HIP runtime in the process)
 
-from tyrant_amd import binding, scenes  # noqa: E402
+import frame_bench_common as fb  # noqa: E402  (torch before the library: one HIP runtime in the process)
+import torch  # noqa: E402
+from tyrant_amd import binding  # noqa: E402
 
-W, H, SPP = 1920, 1080, 8
 MAX_HISTORY = (4, 8, 16, 32)
 DEPTH_TOLERANCE = (0.02, 0.05, 0.1)
 
 
-def summary(ms):
-    q = np.percentile(ms, [10, 90])
-    return {"median_ms": statistics.median(ms), "min_ms": min(ms), "p10_ms": float(q[0]), "p90_ms": float(q[1]), "max_ms": max(ms), "n": len(ms)}
-
-
-def moved(cam, k):
-    """0.4 k units along x and 0.002 k rad about z"""
-    a = 0.002 * k
-    dx, dy, dz = cam.direction
-    c, s = math.cos(a), math.sin(a)
-    return dataclasses.replace(cam, position=(cam.position[0] + 0.4 * k, cam.position[1], cam.position[2]), direction=(c * dx - s * dy, s * dx + c * dy, dz))
-
-
-def timed(stream, calls, warmup, fn):
-    for _ in range(warmup):
-        fn()
-    ms = []
-    for _ in range(calls):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        fn()
-        b.record(stream)
-        b.synchronize()
-        ms.append(a.elapsed_time(b))
-    return summary(ms)
-
-
 def timing(calls, warmup):
-    sc = scenes.mesh_scene(706)
-    g = binding.Renderer(W, H, SPP * W * H, flags=binding.TYR_FLAG_TRIANGLE_MATERIALS)
-    g.set_spheres(sc.spheres)
-    g.set_sun_position(*sc.sun_position)
-    g.build_upload(sc.triangles)
-    cur = moved(sc.camera, 3)
-    g.set_camera(cur)
-    render_ms = []
-    for _ in range(3):
-        g.reset_accum()
-        g.set_frame(1)
-        t0 = time.perf_counter()
-        g.render(SPP)
-        render_ms.append((time.perf_counter() - t0) * 1e3)
-    g.set_frame(1)
-    aov = g.render_aov(1)
-    dev = torch.device("cuda", 0)
-    stream = torch.cuda.Stream(dev)
+    g, sc, _, _ = fb.c3_renderer(steps=3)
+    render = fb.timed_renders(g)
+    aov, gd, mv = fb.c3_guides(g, sc)
+    stream = torch.cuda.Stream(torch.device("cuda", 0))
     res = {}
-    mot = g.render_motion(aov["prim"], aov["geom"], sc.camera)
-    res["render_motion"] = timed(stream, calls, warmup, lambda: g.render_motion(aov["prim"], aov["geom"], sc.camera, stream=stream))
-    gd = {k: aov[k] for k in ("albedo", "normal", "depth")}
-    g.temporal(**gd, motion=mot["motion"], prev_depth=mot["prev_depth"], reset=True)
-    res["temporal"] = timed(stream, calls, warmup, lambda: g.temporal(**gd, motion=mot["motion"], prev_depth=mot["prev_depth"], stream=stream))
-    res["denoise"] = timed(stream, calls, warmup, lambda: g.denoise(**gd, stream=stream))
+    res["render_motion"] = fb.timed(stream, calls, warmup, lambda: g.render_motion(aov["prim"], aov["geom"], sc.camera, stream=stream))
+    g.temporal(**gd, **mv, reset=True)
+    res["temporal"] = fb.timed(stream, calls, warmup, lambda: g.temporal(**gd, **mv, stream=stream))
+    res["denoise"] = fb.timed(stream, calls, warmup, lambda: g.denoise(**gd, stream=stream))
     torch.cuda.synchronize()
-    _, ln = g.temporal(**gd, motion=mot["motion"], prev_depth=mot["prev_depth"], want_history_len=True)
+    _, ln = g.temporal(**gd, **mv, want_history_len=True)
     res["history_len_gt1_fraction"] = float((ln.cpu().numpy() > 1).mean())
-    res["render_8spp"] = {"ms": render_ms, "median_ms": statistics.median(render_ms)}
+    res["render_8spp"] = render
     g.close()
     return res
 
 
 def quality(frames=16, ref_spp=1024, Wq=128, Hq=72):
-    sc = scenes.cornell_box()
-    sc = dataclasses.replace(sc, camera=scenes.FRAMED_CAMERA)
-    nodes, prims = binding.bvh_build(sc.triangles)
-    cams = [moved(sc.camera, k) for k in range(frames)]
+    sc, nodes, prims, cams = fb.pan_scene(frames)
     g = binding.Renderer(Wq, Hq, 1 << 16)
     g.load_scene(sc, nodes, prims)
-    seq = []
-    prev = cams[0]
-    for cam in cams:
-        g.set_camera(cam)
-        aov = g.render_aov(1)
-        mot = g.render_motion(aov["prim"], aov["geom"], prev)
-        g.render(1)
-        seq.append((aov, mot, torch.from_numpy(g.blit_buffer()).to("cuda:0")))
-        prev = cam
-    r = binding.Renderer(Wq, Hq, 1 << 18)
-    r.load_scene(sc, nodes, prims)
-    r.set_camera(cams[-1])
-    r.render(ref_spp)
-    conv = r.blit_buffer()
-    r.close()
+    seq = [(aov, mot, torch.from_numpy(acc).to("cuda:0")) for aov, mot, acc in fb.pan_frames(g, cams)]
     noisy = seq[-1][2].cpu().numpy()
-    seen = (noisy[:, 3] > 0) & (conv[:, 3] > 0)
-    want = conv[seen, :3].astype(np.float64) / conv[seen, 3:]
-    mse = lambda a: float(((a[seen, :3].astype(np.float64) - want) ** 2).mean())  # noqa: E731
+    _, mse = fb.reference(noisy, fb.converged(sc, nodes, prims, cams[-1], Wq, Hq, ref_spp))
     last = seq[-1][0]
     gd = {k: last[k] for k in ("albedo", "normal", "depth")}
     noisy_mse = mse(noisy[:, :3] / np.maximum(noisy[:, 3:], 1))

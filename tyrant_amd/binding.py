@@ -908,22 +908,10 @@ class Renderer:
         Returns an (H, W, 4) float32 tensor: the filtered frame in the blit buffer's layout with one sample per pixel, or
         with resolve=True tone-mapped as resolve_into writes it.  Runs on `stream` (default: torch's current stream) and
         returns without waiting for it."""
-        import torch
-
-        dev = torch.device("cuda", self.device)
-        n = self.H * self.W
-        ins = {"albedo": (albedo, 3 * n), "normal": (normal, 3 * n), "depth": (depth, n), "accum": (accum, 4 * n)}
-        for what, (t, size) in ins.items():
-            if t is None and what == "accum":
-                continue
-            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != size:
-                raise ValueError(f"{what}: a contiguous float32 tensor of {size} values on {dev}")
-        out = torch.empty((self.H, self.W, 4), dtype=torch.float32, device=dev)
-        din = DenoiseIn(None if accum is None else accum.data_ptr(), albedo.data_ptr(), normal.data_ptr(), depth.data_ptr())
+        din = DenoiseIn(*self._frame_inputs(accum=accum, albedo=albedo, normal=normal, depth=depth))
         prm = DenoiseParams(passes, sigma_color, sigma_depth, normal_power_log2, TYR_DENOISE_RESOLVE if resolve else 0)
-        self._on_stream(stream, lambda h: self.L.tyr_denoise(self.h, C.byref(din), C.byref(prm), out.data_ptr(), h), True)
-        if stream is not None:
-            out.record_stream(stream)  # written there: the allocator must not hand its memory out before that stream is done
+        (out,) = self._frame_outputs(4)
+        self._frame_call("tyr_denoise", stream, C.byref(din), C.byref(prm), out)
         return out
 
     def _frame_tensors(self, ins):
@@ -934,6 +922,42 @@ class Renderer:
             if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or not t.is_contiguous() or t.numel() != size:
                 raise ValueError(f"{what}: a contiguous {dtype} tensor of {size} values on {dev}")
         return dev
+
+    # values per pixel of the frame passes' float32 planes, by argument name; the optional ones may be None
+    _FRAME_PLANES = {"albedo": 3, "normal": 3, "depth": 1, "prev_depth": 1, "motion": 2, "accum": 4, "color": 4, "out": 4}
+    _FRAME_OPTIONAL = ("accum", "out")
+
+    def _frame_inputs(self, **ins):
+        """a frame pass's planes by argument name, checked (_frame_tensors): their addresses in the order given, None for an
+        optional one that is None"""
+        import torch
+
+        n = self.H * self.W
+        self._frame_tensors({k: (t, torch.float32, self._FRAME_PLANES[k] * n) for k, t in ins.items() if t is not None or k not in self._FRAME_OPTIONAL})
+        return [None if t is None else t.data_ptr() for t in ins.values()]
+
+    def _frame_outputs(self, *planes, dtype=None, zero=False):
+        """a frame pass's outputs: one (H, W, k) tensor on the ctx's device per k -- (H, W) for 0, None for None -- float32
+        unless `dtype` says otherwise, uninitialised unless `zero`"""
+        import torch
+
+        make = torch.zeros if zero else torch.empty
+        dev = torch.device("cuda", self.device)
+        return [None if k is None else make((self.H, self.W, k) if k else (self.H, self.W), dtype=dtype or torch.float32, device=dev) for k in planes]
+
+    def _frame_call(self, name, stream, *args):
+        """the C call `name`(ctx, *args, stream handle) on `stream` (see _on_stream).  A tensor among args is an output: its address
+        is passed, and when a stream was given it is recorded there -- it was written there: the allocator must not hand its
+        memory out before that stream is done."""
+        import torch
+
+        fn = getattr(self.L, name)
+        outs = [a for a in args if isinstance(a, torch.Tensor)]
+        args = [a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args]
+        self._on_stream(stream, lambda h: fn(self.h, *args, h), True, name)
+        if stream is not None:
+            for t in outs:
+                t.record_stream(stream)
 
     def render_motion(self, prim, geom, prev_camera, prev_prims=None, stream=None, chain=None, length0=None) -> dict:
         """tyr_render_motion: per pixel the motion to the previous frame and the depth expected there, from render_aov's sample-0
@@ -986,23 +1010,10 @@ class Renderer:
         contiguous float32 tensors on this ctx's device.  Returns the (H, W, 4) float32 frame in the blit buffer's layout with one
         sample per pixel (denoise's accum), and with want_history_len=True also the (H, W) history lengths.  reset=True discards
         the history first.  Runs on `stream` (default: torch's current stream) and returns without waiting for it."""
-        import torch
-
-        n = self.H * self.W
-        f = torch.float32
-        ins = {"albedo": (albedo, f, 3 * n), "normal": (normal, f, 3 * n), "depth": (depth, f, n), "motion": (motion, f, 2 * n), "prev_depth": (prev_depth, f, n)}
-        if accum is not None:
-            ins["accum"] = (accum, f, 4 * n)
-        dev = self._frame_tensors(ins)
-        out = torch.empty((self.H, self.W, 4), dtype=f, device=dev)
-        hl = torch.empty((self.H, self.W), dtype=f, device=dev) if want_history_len else None
-        tin = TemporalIn(None if accum is None else accum.data_ptr(), albedo.data_ptr(), normal.data_ptr(), depth.data_ptr(), motion.data_ptr(), prev_depth.data_ptr())
+        tin = TemporalIn(*self._frame_inputs(accum=accum, albedo=albedo, normal=normal, depth=depth, motion=motion, prev_depth=prev_depth))
         prm = TemporalParams(max_history, depth_tolerance, normal_cos, TYR_TEMPORAL_RESET if reset else 0)
-        self._on_stream(stream, lambda h: self.L.tyr_temporal(self.h, C.byref(tin), C.byref(prm), out.data_ptr(), None if hl is None else hl.data_ptr(), h), True)
-        if stream is not None:
-            out.record_stream(stream)
-            if hl is not None:
-                hl.record_stream(stream)
+        out, hl = self._frame_outputs(4, 0 if want_history_len else None)
+        self._frame_call("tyr_temporal", stream, C.byref(tin), C.byref(prm), out, hl)
         return (out, hl) if want_history_len else out
 
     def svgf(self, albedo, normal, depth, motion, prev_depth, accum=None, max_history=SVGF_MAX_HISTORY, depth_tolerance=SVGF_DEPTH_TOLERANCE,
@@ -1014,24 +1025,11 @@ class Renderer:
         the (H, W, 4) float32 filtered frame in the blit buffer's layout with one sample per pixel (with resolve=True tone-mapped
         as resolve_into writes it), and with want_variance=True also the (H, W) variance estimate.  reset=True discards the
         history first.  Runs on `stream` (default: torch's current stream) and returns without waiting for it."""
-        import torch
-
-        n = self.H * self.W
-        f = torch.float32
-        ins = {"albedo": (albedo, f, 3 * n), "normal": (normal, f, 3 * n), "depth": (depth, f, n), "motion": (motion, f, 2 * n), "prev_depth": (prev_depth, f, n)}
-        if accum is not None:
-            ins["accum"] = (accum, f, 4 * n)
-        dev = self._frame_tensors(ins)
-        out = torch.empty((self.H, self.W, 4), dtype=f, device=dev)
-        var = torch.empty((self.H, self.W), dtype=f, device=dev) if want_variance else None
-        sin = SvgfIn(None if accum is None else accum.data_ptr(), albedo.data_ptr(), normal.data_ptr(), depth.data_ptr(), motion.data_ptr(), prev_depth.data_ptr())
+        sin = SvgfIn(*self._frame_inputs(accum=accum, albedo=albedo, normal=normal, depth=depth, motion=motion, prev_depth=prev_depth))
         flags = (TYR_SVGF_RESET if reset else 0) | (TYR_SVGF_RESOLVE if resolve else 0)
         prm = SvgfParams(max_history, depth_tolerance, normal_cos, passes, sigma_luminance, sigma_depth, normal_power_log2, flags)
-        self._on_stream(stream, lambda h: self.L.tyr_svgf(self.h, C.byref(sin), C.byref(prm), out.data_ptr(), None if var is None else var.data_ptr(), h), True)
-        if stream is not None:
-            out.record_stream(stream)
-            if var is not None:
-                var.record_stream(stream)
+        out, var = self._frame_outputs(4, 0 if want_variance else None)
+        self._frame_call("tyr_svgf", stream, C.byref(sin), C.byref(prm), out, var)
         return (out, var) if want_variance else out
 
     def taa(self, color, depth, motion, prev_depth, alpha=TAA_ALPHA, gamma=TAA_GAMMA, bilinear=False, reset=False, out=None, stream=None):
@@ -1041,21 +1039,11 @@ class Renderer:
         float32 frame: `out` when given (it may be `color` itself: in place), else a new tensor.  bilinear=True samples the
         history with four taps instead of the 4 x 4 Catmull-Rom kernel; reset=True discards the history first.  Runs on
         `stream` (default: torch's current stream) and returns without waiting for it."""
-        import torch
-
-        n = self.H * self.W
-        f = torch.float32
-        ins = {"color": (color, f, 4 * n), "depth": (depth, f, n), "motion": (motion, f, 2 * n), "prev_depth": (prev_depth, f, n)}
-        if out is not None:
-            ins["out"] = (out, f, 4 * n)
-        dev = self._frame_tensors(ins)
-        if out is None:
-            out = torch.empty((self.H, self.W, 4), dtype=f, device=dev)
-        tin = TaaIn(color.data_ptr(), depth.data_ptr(), motion.data_ptr(), prev_depth.data_ptr())
+        tin = TaaIn(*self._frame_inputs(color=color, depth=depth, motion=motion, prev_depth=prev_depth, out=out)[:4])
         prm = TaaParams(alpha, gamma, (TYR_TAA_RESET if reset else 0) | (TYR_TAA_BILINEAR if bilinear else 0))
-        self._on_stream(stream, lambda h: self.L.tyr_taa(self.h, C.byref(tin), C.byref(prm), out.data_ptr(), h), True, "tyr_taa")
-        if stream is not None:
-            out.record_stream(stream)
+        if out is None:
+            (out,) = self._frame_outputs(4)
+        self._frame_call("tyr_taa", stream, C.byref(tin), C.byref(prm), out)
         return out
 
     # ---- adaptive sampling (include/tyr_c.h "Adaptive sampling") ----
@@ -1099,10 +1087,10 @@ class Renderer:
         import torch
 
         e = self._frame_map(error, torch.float32, "error")
-        out = torch.zeros((self.H, self.W), dtype=torch.int32, device=e.device)
-        got = c_u64(0)
         prm = AllocateParams(int(total), int(min_spp), int(max_spp))
-        self._on_stream(stream, lambda h: self.L.tyr_allocate_samples(self.h, e.data_ptr(), C.byref(prm), out.data_ptr(), C.byref(got), h), True, "tyr_allocate_samples")
+        (out,) = self._frame_outputs(0, dtype=torch.int32, zero=True)
+        got = c_u64(0)
+        self._frame_call("tyr_allocate_samples", stream, e.data_ptr(), C.byref(prm), out, C.byref(got))
         return out, got.value
 
 

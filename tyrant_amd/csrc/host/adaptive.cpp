@@ -35,14 +35,8 @@ namespace tyr {
 namespace drv {
 
 void adaptive_free(tyr_ctx* c) {
-	if (c->allocDone) {
-		(void)hipEventSynchronize(c->allocDone);
-		(void)hipEventDestroy(c->allocDone);
-		c->allocDone = nullptr;
-	}
 	dev_free(c->dTickets);
 	dev_free(c->dMapScratch);
-	dev_free(c->dAllocScratch);
 	c->ticketCap = 0;
 	c->ticketTotal = 0;
 	c->mapped = false;
@@ -154,19 +148,14 @@ int tyr_allocate_samples(tyr_ctx* c, const float* error, const tyr_allocate_para
 	const tyr_allocate_params p = *params;
 	if (p.min_spp > p.max_spp || p.max_spp < 1u || p.max_spp > kMaxSpp || p.total >= (1ull << 32))
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	if (int rc = scope.enter(c))
+	FilterLaunch L;
+	if (int rc = L.open(c, c->alloc, stream))
 		return rc;
+	const hipStream_t s = L.s;
 	const uint32_t P = c->localPixels, tiles = tiles_of(P);
 	// scratch: the per-block scans (8 bytes per pixel), the blocks' totals, the largest error's bits and the map's sum
-	if (!c->dAllocScratch) {
-		if (int rc = dev_alloc(c->dAllocScratch, static_cast<size_t>(P) + tiles + 2u))
-			return rc;
-	}
-	if (!c->allocDone)
-		HIPCHK(hipEventCreateWithFlags(&c->allocDone, hipEventDisableTiming));
-	const hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-	HIPCHK(hipStreamWaitEvent(s, c->allocDone, 0)); // the previous call's scratch (a no-op before the first record)
+	if (int rc = L.buffer(c->dAllocScratch, static_cast<size_t>(P) + tiles + 2u))
+		return rc;
 	unsigned long long* words = c->dAllocScratch + P + tiles;
 	HIPCHK(hipMemsetAsync(words, 0, 2 * sizeof(unsigned long long), s));
 	const uint64_t floorTotal = static_cast<uint64_t>(p.min_spp) * P;
@@ -186,8 +175,8 @@ int tyr_allocate_samples(tyr_ctx* c, const float* error, const tyr_allocate_para
 	A.maxBits = reinterpret_cast<uint32_t*>(words);
 	A.totalOut = words + 1;
 	launch_allocate(A, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(c->allocDone, s));
+	if (int rc = L.close())
+		return rc;
 	if (total_out) {
 		unsigned long long t = 0;
 		HIPCHK(hipMemcpyAsync(&t, words + 1, sizeof t, hipMemcpyDeviceToHost, s));

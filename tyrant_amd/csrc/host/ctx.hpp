@@ -19,6 +19,16 @@ using tyr::ShadowQ;
 using tyr::SunParams;
 using tyr::Tuning;
 
+// What a frame pass (tyr_denoise, tyr_temporal, tyr_svgf, tyr_taa, tyr_allocate_samples) keeps between calls beside its buffers,
+// which belong to the ctx (host/driver_internal.hpp FilterLaunch).  done: the event behind the last call (the next one waits for
+// it, on whatever stream).  The passes with a history keep two and alternate: history cur is the last call's output, valid only
+// when have is set.
+struct FilterState {
+	hipEvent_t done = nullptr;
+	uint32_t cur = 0;
+	bool have = false;
+};
+
 struct tyr_ctx {
 	tyr_config cfg{};
 	hipStream_t stream = nullptr;
@@ -122,47 +132,38 @@ struct tyr_ctx {
 	std::vector<QueryStream> queryStreams;
 
 	// tyr_denoise (host/denoise.cpp): scratch for width * height pixels -- two illumination buffers, then the packed guide --
-	// allocated by the first call, and the event behind the last call (the next one waits for it, on whatever stream)
+	// allocated by the first call
 	float4* dDenoise = nullptr;
-	hipEvent_t denoiseDone = nullptr;
+	FilterState denoise;
 
 	// tyr_temporal (host/temporal.cpp): two histories of width * height pixels, each a (u.xyz, length) plane then a (normal.xyz,
-	// depth) plane, allocated by the first call; history temporalCur is the last call's output (valid only when temporalHave),
-	// temporalDone the event behind that call
+	// depth) plane, allocated by the first call
 	float4* dTemporal = nullptr;
-	hipEvent_t temporalDone = nullptr;
-	uint32_t temporalCur = 0;
-	bool temporalHave = false;
+	FilterState temporal;
 
 	// tyr_svgf (host/svgf.cpp): two histories of width * height pixels, each a (u.xyz, length) plane then a (normal.xyz, depth)
-	// plane (dSvgfHist), and a (m1, m2) plane (dSvgfMom); history svgfCur is the last call's output (valid only when
-	// svgfHave).  dSvgfIllum: the a-trous passes' two (u.xyz, variance) buffers.  All allocated by the first call; svgfDone is
-	// the event behind the last call
+	// plane (dSvgfHist), and a (m1, m2) plane (dSvgfMom).  dSvgfIllum: the a-trous passes' two (u.xyz, variance) buffers.  All
+	// allocated by the first call
 	float4* dSvgfHist = nullptr;
 	float2* dSvgfMom = nullptr;
 	float4* dSvgfIllum = nullptr;
-	hipEvent_t svgfDone = nullptr;
-	uint32_t svgfCur = 0;
-	bool svgfHave = false;
+	FilterState svgf;
 
-	// tyr_taa (host/taa.cpp): two planes of width * height (rgb, validity) pixels, allocated by the first call; plane taaCur
-	// is the last call's output (valid only when taaHave), taaDone the event behind that call
+	// tyr_taa (host/taa.cpp): two planes of width * height (rgb, validity) pixels, allocated by the first call
 	float4* dTaaHist = nullptr;
-	hipEvent_t taaDone = nullptr;
-	uint32_t taaCur = 0;
-	bool taaHave = false;
+	FilterState taa;
 
 	// tyr_set_sample_map / tyr_allocate_samples (host/adaptive.cpp): the sample map's ticket list (4 bytes per ticket, grown as needed),
 	// its length T and whether the camera rays take their pixels from it (mapped mode: until tyr_set_budget / tyr_render set a
 	// budget of their own); the list build's scratch -- the map at the local pixels, the summary + histogram the host reads back,
-	// the compaction's block counts -- and the allocator's (two 64-bit scans and three words), with the event behind its last call
+	// the compaction's block counts -- and the allocator's (two 64-bit scans and three words), with its state
 	uint32_t* dTickets = nullptr;
 	uint64_t ticketCap = 0;
 	uint32_t ticketTotal = 0;
 	bool mapped = false;
 	uint32_t* dMapScratch = nullptr;
 	unsigned long long* dAllocScratch = nullptr;
-	hipEvent_t allocDone = nullptr;
+	FilterState alloc;
 
 	// TYR_FLAG_REFIT: what every scene upload keeps for tyr_scene_refit (host/refit.cpp)
 	tyr::RefitPlan refit{};

@@ -1,6 +1,7 @@
 // denoise.cpp -- tyr_denoise: the edge-avoiding a-trous filter of a frame guided by the AOV buffers (include/tyr_c.h
 // "Denoiser"; the kernels are hip/denoise.hip).  Like a query it runs on the caller's stream and touches no render state; it
-// needs no scene.  The scratch belongs to the ctx, so each call waits on its stream for the previous call's event.
+// needs no scene.  The scratch belongs to the ctx, so each call waits on its stream for the previous call's event: FilterLaunch,
+// the bracket that all the frame passes share, is defined here.
 #include <cmath>
 
 #include <hip/hip_runtime.h>
@@ -18,11 +19,10 @@ constexpr uint32_t kDefaultPasses = 5;
 constexpr float kDefaultSigmaColor = 32.0f;
 constexpr float kDefaultSigmaDepth = 0.02f;
 constexpr uint32_t kDefaultNormalPowerLog2 = 7;
-constexpr uint32_t kMaxPasses = 8, kMaxNormalPowerLog2 = 10;
 
 // 1 / (sigma * sigma) in float32, or 0 when sigma is not positive and finite or the result is not finite
 float inv_square(float sigma) {
-	if (!(sigma > 0.f) || !std::isfinite(sigma))
+	if (!positive_finite(sigma))
 		return 0.f;
 	const float sq = sigma * sigma;
 	const float k = 1.0f / sq;
@@ -34,13 +34,48 @@ float inv_square(float sigma) {
 namespace tyr {
 namespace drv {
 
-void denoise_free(tyr_ctx* c) {
-	if (c->denoiseDone) {
-		(void)hipEventSynchronize(c->denoiseDone);
-		(void)hipEventDestroy(c->denoiseDone);
-		c->denoiseDone = nullptr;
+int FilterLaunch::open(tyr_ctx* c, FilterState& state, void* stream) {
+	if (int rc = scope.enter(c))
+		return rc;
+	st = &state;
+	if (!st->done)
+		HIPCHK(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
+	s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+	HIPCHK(hipStreamWaitEvent(s, st->done, 0));
+	return TYR_OK;
+}
+
+int FilterLaunch::close() {
+	HIPCHK(hipGetLastError());
+	HIPCHK(hipEventRecord(st->done, s));
+	if (pingPong) {
+		st->cur = next;
+		st->have = true;
+	}
+	return TYR_OK;
+}
+
+void filters_free(tyr_ctx* c) {
+	for (FilterState* st : { &c->denoise, &c->temporal, &c->svgf, &c->taa, &c->alloc }) {
+		if (st->done) {
+			(void)hipEventSynchronize(st->done);
+			(void)hipEventDestroy(st->done);
+		}
+		*st = FilterState{};
 	}
 	dev_free(c->dDenoise);
+	dev_free(c->dTemporal);
+	dev_free(c->dSvgfHist);
+	dev_free(c->dSvgfMom);
+	dev_free(c->dSvgfIllum);
+	dev_free(c->dTaaHist);
+	dev_free(c->dAllocScratch);
+}
+
+bool positive_finite(float v) { return v > 0.f && std::isfinite(v); }
+
+bool reprojection_ok(uint32_t maxHistory, float depthTolerance, float normalCos) {
+	return maxHistory >= 1 && maxHistory <= kMaxHistory && positive_finite(depthTolerance) && normalCos >= -1.f && normalCos <= 1.f;
 }
 
 } // namespace drv
@@ -60,18 +95,12 @@ int tyr_denoise(tyr_ctx* c, const tyr_denoise_in* in, const tyr_denoise_params* 
 	const float4* accum = in->accum ? reinterpret_cast<const float4*>(in->accum) : c->blit;
 	if (!accum)
 		return TYR_ERR_NO_BUFFER;
-	DeviceScope scope;
-	if (int rc = scope.enter(c))
+	FilterLaunch L;
+	if (int rc = L.open(c, c->denoise, stream))
 		return rc;
 	const size_t n = static_cast<size_t>(c->cfg.width) * c->cfg.height;
-	if (!c->dDenoise) {
-		if (int rc = dev_alloc(c->dDenoise, 3 * n))
-			return rc;
-	}
-	if (!c->denoiseDone)
-		HIPCHK(hipEventCreateWithFlags(&c->denoiseDone, hipEventDisableTiming));
-	const hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-	HIPCHK(hipStreamWaitEvent(s, c->denoiseDone, 0)); // the previous call's scratch (a no-op before the first record)
+	if (int rc = L.buffer(c->dDenoise, 3 * n))
+		return rc;
 
 	DenoiseParams P{};
 	P.accum = accum;
@@ -89,8 +118,6 @@ int tyr_denoise(tyr_ctx* c, const tyr_denoise_in* in, const tyr_denoise_params* 
 	P.normalPowerLog2 = p.normal_power_log2;
 	P.passes = p.passes;
 	P.resolve = (p.flags & TYR_DENOISE_RESOLVE) != 0u;
-	launch_denoise(P, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(c->denoiseDone, s));
-	return TYR_OK;
+	launch_denoise(P, L.s);
+	return L.close();
 }

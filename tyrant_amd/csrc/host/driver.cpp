@@ -591,10 +591,7 @@ int tyr_destroy(tyr_ctx* c) {
 		if (e)
 			(void)hipEventDestroy(e);
 	query_free(c);
-	denoise_free(c);
-	temporal_free(c);
-	svgf_free(c);
-	taa_free(c);
+	filters_free(c);
 	adaptive_free(c);
 	free_rayq(c->q[0]);
 	free_rayq(c->q[1]);

@@ -132,15 +132,47 @@ void camera_basis(const tyr_ctx* c, float right[3], float up[3]);
 void camera_basis(const tyr_ctx* c, const tyr_camera& cam, float right[3], float up[3]);
 void camera_basis(uint32_t width, uint32_t height, const tyr_camera& cam, float right[3], float up[3]);
 void query_free(tyr_ctx* c);
-// host/denoise.cpp: wait for the last tyr_denoise call; free its scratch and event (tyr_destroy)
-void denoise_free(tyr_ctx* c);
-// host/temporal.cpp: wait for the last tyr_temporal call; free its history and event (tyr_destroy)
-void temporal_free(tyr_ctx* c);
-// host/svgf.cpp: wait for the last tyr_svgf call; free its history, scratch and event (tyr_destroy)
-void svgf_free(tyr_ctx* c);
-// host/taa.cpp: wait for the last tyr_taa call; free its history and event (tyr_destroy)
-void taa_free(tyr_ctx* c);
-// host/adaptive.cpp: wait for the last tyr_allocate_samples call; free the ticket list and the scratch (tyr_destroy)
+// host/denoise.cpp: the bracket round the launch of a frame pass (tyr_denoise, tyr_temporal, tyr_svgf, tyr_taa,
+// tyr_allocate_samples) on the caller's `stream` (NULL: the ctx's), once its arguments have been accepted.  The pass's buffers
+// belong to the ctx, so its calls are ordered by the event in its FilterState.  open() goes in front of the launch: it makes
+// the ctx's device current (the caller's comes back when the object goes, on every way out), creates the event on first use
+// and has s wait for the previous call (a no-op before the first record).  close() goes behind it: the launch's error, then
+// the event; a pass that asked for its history() now has history `next` as the last call's output.  An error on the way
+// leaves the state as it was.
+struct FilterLaunch {
+	hipStream_t s = nullptr;
+	uint32_t prev = 0, next = 0; // history(): the history the last call wrote and the one this call writes
+	int open(tyr_ctx* c, FilterState& state, void* stream);
+	// a buffer of the pass, allocated on first use; with a fresh one there is no history
+	template <class T>
+	int buffer(T*& p, size_t count) {
+		if (p)
+			return TYR_OK;
+		st->have = false;
+		return dev_alloc(p, count);
+	}
+	// sets prev and next; true: history prev is to be read (the pass has one and the call does not reset it)
+	bool history(bool reset) {
+		pingPong = true;
+		prev = st->cur;
+		next = prev ^ 1u;
+		return st->have && !reset;
+	}
+	int close();
+
+private:
+	DeviceScope scope;
+	FilterState* st = nullptr;
+	bool pingPong = false;
+};
+// ... wait for the last call of every pass; free their events and buffers (tyr_destroy)
+void filters_free(tyr_ctx* c);
+// the limits and checks that the passes' parameters share
+constexpr uint32_t kMaxHistory = 1024, kMaxPasses = 8, kMaxNormalPowerLog2 = 10;
+bool positive_finite(float v);
+// max_history, depth_tolerance and normal_cos of tyr_temporal and tyr_svgf
+bool reprojection_ok(uint32_t maxHistory, float depthTolerance, float normalCos);
+// host/adaptive.cpp: free the sample map's ticket list and scratch (tyr_destroy)
 void adaptive_free(tyr_ctx* c);
 // AoS import / export (host/staged_api.cpp): physical slots that hold a record, per segment counter array `seg` (device pointer)
 int valid_slots(const uint32_t* dSeg, std::vector<uint32_t>& slots, uint32_t* total = nullptr);

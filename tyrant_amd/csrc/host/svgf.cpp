@@ -22,29 +22,8 @@ constexpr uint32_t kDefaultPasses = 3;
 constexpr float kDefaultSigmaLuminance = 2.0f;
 constexpr float kDefaultSigmaDepth = 0.02f;
 constexpr uint32_t kDefaultNormalPowerLog2 = 7;
-constexpr uint32_t kMaxHistory = 1024, kMaxPasses = 8, kMaxNormalPowerLog2 = 10;
-
-bool positive_finite(float v) { return v > 0.f && std::isfinite(v); }
 
 } // namespace
-
-namespace tyr {
-namespace drv {
-
-void svgf_free(tyr_ctx* c) {
-	if (c->svgfDone) {
-		(void)hipEventSynchronize(c->svgfDone);
-		(void)hipEventDestroy(c->svgfDone);
-		c->svgfDone = nullptr;
-	}
-	dev_free(c->dSvgfHist);
-	dev_free(c->dSvgfMom);
-	dev_free(c->dSvgfIllum);
-	c->svgfHave = false;
-}
-
-} // namespace drv
-} // namespace tyr
 
 int tyr_svgf(tyr_ctx* c, const tyr_svgf_in* in, const tyr_svgf_params* params, void* device_rgba_out, float* variance_out, void* stream) {
 	if (!c || !in || !in->albedo || !in->normal || !in->depth || !in->motion || !in->prev_depth || !device_rgba_out)
@@ -52,8 +31,8 @@ int tyr_svgf(tyr_ctx* c, const tyr_svgf_in* in, const tyr_svgf_params* params, v
 	tyr_svgf_params p{ kDefaultMaxHistory, kDefaultDepthTolerance, kDefaultNormalCos, kDefaultPasses, kDefaultSigmaLuminance, kDefaultSigmaDepth, kDefaultNormalPowerLog2, 0u };
 	if (params)
 		p = *params;
-	if (p.max_history < 1 || p.max_history > kMaxHistory || !positive_finite(p.depth_tolerance) || !(p.normal_cos >= -1.f && p.normal_cos <= 1.f) || p.passes < 1 ||
-	    p.passes > kMaxPasses || p.normal_power_log2 > kMaxNormalPowerLog2 || (p.flags & ~(TYR_SVGF_RESET | TYR_SVGF_RESOLVE)) != 0u)
+	if (!reprojection_ok(p.max_history, p.depth_tolerance, p.normal_cos) || p.passes < 1 || p.passes > kMaxPasses || p.normal_power_log2 > kMaxNormalPowerLog2 ||
+	    (p.flags & ~(TYR_SVGF_RESET | TYR_SVGF_RESOLVE)) != 0u)
 		return TYR_ERR_INVALID;
 	if (!positive_finite(p.sigma_luminance) || !positive_finite(p.sigma_depth))
 		return TYR_ERR_INVALID;
@@ -65,29 +44,21 @@ int tyr_svgf(tyr_ctx* c, const tyr_svgf_in* in, const tyr_svgf_params* params, v
 	const float4* accum = in->accum ? reinterpret_cast<const float4*>(in->accum) : c->blit;
 	if (!accum)
 		return TYR_ERR_NO_BUFFER;
-	DeviceScope scope;
-	if (int rc = scope.enter(c))
+	FilterLaunch L;
+	if (int rc = L.open(c, c->svgf, stream))
 		return rc;
 	const size_t n = static_cast<size_t>(c->cfg.width) * c->cfg.height;
-	if (!c->dSvgfHist || !c->dSvgfMom || !c->dSvgfIllum) {
-		c->svgfHave = false;
-		if (!c->dSvgfHist)
-			if (int rc = dev_alloc(c->dSvgfHist, 4 * n))
-				return rc;
-		if (!c->dSvgfMom)
-			if (int rc = dev_alloc(c->dSvgfMom, 2 * n))
-				return rc;
-		if (!c->dSvgfIllum)
-			if (int rc = dev_alloc(c->dSvgfIllum, 2 * n))
-				return rc;
-	}
-	if (!c->svgfDone)
-		HIPCHK(hipEventCreateWithFlags(&c->svgfDone, hipEventDisableTiming));
-	const hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-	HIPCHK(hipStreamWaitEvent(s, c->svgfDone, 0)); // the previous call's history and scratch (a no-op before the first record)
+	// (a call that fails part of the way keeps what it allocated: the next one completes it, and starts without a history)
+	if (int rc = L.buffer(c->dSvgfHist, 4 * n))
+		return rc;
+	if (int rc = L.buffer(c->dSvgfMom, 2 * n))
+		return rc;
+	if (int rc = L.buffer(c->dSvgfIllum, 2 * n))
+		return rc;
 
-	const uint32_t prev = c->svgfCur, next = prev ^ 1u;
 	SvgfParams P{};
+	P.haveHistory = L.history((p.flags & TYR_SVGF_RESET) != 0u);
+	const uint32_t prev = L.prev, next = L.next;
 	P.accum = accum;
 	P.albedo = in->albedo;
 	P.normal = in->normal;
@@ -113,12 +84,7 @@ int tyr_svgf(tyr_ctx* c, const tyr_svgf_in* in, const tyr_svgf_params* params, v
 	P.kz = kz;
 	P.normalPowerLog2 = p.normal_power_log2;
 	P.passes = p.passes;
-	P.haveHistory = c->svgfHave && (p.flags & TYR_SVGF_RESET) == 0u;
 	P.resolve = (p.flags & TYR_SVGF_RESOLVE) != 0u;
-	launch_svgf(P, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(c->svgfDone, s));
-	c->svgfCur = next;
-	c->svgfHave = true;
-	return TYR_OK;
+	launch_svgf(P, L.s);
+	return L.close();
 }

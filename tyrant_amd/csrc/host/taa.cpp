@@ -20,22 +20,6 @@ constexpr float kDefaultGamma = 1.5f;
 
 } // namespace
 
-namespace tyr {
-namespace drv {
-
-void taa_free(tyr_ctx* c) {
-	if (c->taaDone) {
-		(void)hipEventSynchronize(c->taaDone);
-		(void)hipEventDestroy(c->taaDone);
-		c->taaDone = nullptr;
-	}
-	dev_free(c->dTaaHist);
-	c->taaHave = false;
-}
-
-} // namespace drv
-} // namespace tyr
-
 int tyr_taa(tyr_ctx* c, const tyr_taa_in* in, const tyr_taa_params* params, void* device_rgba_out, void* stream) {
 	if (!c || !in || !in->color || !in->depth || !in->motion || !in->prev_depth || !device_rgba_out)
 		return TYR_ERR_INVALID;
@@ -44,21 +28,13 @@ int tyr_taa(tyr_ctx* c, const tyr_taa_in* in, const tyr_taa_params* params, void
 		p = *params;
 	if (!(p.alpha > 0.f && p.alpha <= 1.f) || !(p.gamma >= 0.f && std::isfinite(p.gamma)) || (p.flags & ~(TYR_TAA_RESET | TYR_TAA_BILINEAR)) != 0u)
 		return TYR_ERR_INVALID;
-	DeviceScope scope;
-	if (int rc = scope.enter(c))
+	FilterLaunch L;
+	if (int rc = L.open(c, c->taa, stream))
 		return rc;
 	const size_t n = static_cast<size_t>(c->cfg.width) * c->cfg.height;
-	if (!c->dTaaHist) {
-		c->taaHave = false;
-		if (int rc = dev_alloc(c->dTaaHist, 2 * n))
-			return rc;
-	}
-	if (!c->taaDone)
-		HIPCHK(hipEventCreateWithFlags(&c->taaDone, hipEventDisableTiming));
-	const hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-	HIPCHK(hipStreamWaitEvent(s, c->taaDone, 0)); // the previous call's history (a no-op before the first record)
+	if (int rc = L.buffer(c->dTaaHist, 2 * n))
+		return rc;
 
-	const uint32_t prev = c->taaCur, next = prev ^ 1u;
 	// in place: lanes read their neighbours' colours, so the kernel writes the history plane alone and a copy follows it
 	const bool inPlace = device_rgba_out == static_cast<const void*>(in->color);
 	TaaParams P{};
@@ -66,21 +42,19 @@ int tyr_taa(tyr_ctx* c, const tyr_taa_in* in, const tyr_taa_params* params, void
 	P.depth = in->depth;
 	P.motion = reinterpret_cast<const float2*>(in->motion);
 	P.prevDepth = in->prev_depth;
-	P.histIn = c->dTaaHist + prev * n;
-	P.histOut = c->dTaaHist + next * n;
+	P.haveHistory = L.history((p.flags & TYR_TAA_RESET) != 0u);
+	P.histIn = c->dTaaHist + L.prev * n;
+	P.histOut = c->dTaaHist + L.next * n;
 	P.out = inPlace ? nullptr : static_cast<float4*>(device_rgba_out);
 	P.W = c->cfg.width;
 	P.H = c->cfg.height;
 	P.alpha = p.alpha;
 	P.gamma = p.gamma;
-	P.haveHistory = c->taaHave && (p.flags & TYR_TAA_RESET) == 0u;
 	P.bilinear = (p.flags & TYR_TAA_BILINEAR) != 0u;
-	launch_taa(P, s);
-	HIPCHK(hipGetLastError());
-	if (inPlace)
-		HIPCHK(hipMemcpyAsync(device_rgba_out, P.histOut, n * sizeof(float4), hipMemcpyDeviceToDevice, s));
-	HIPCHK(hipEventRecord(c->taaDone, s));
-	c->taaCur = next;
-	c->taaHave = true;
-	return TYR_OK;
+	launch_taa(P, L.s);
+	if (inPlace) {
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(device_rgba_out, P.histOut, n * sizeof(float4), hipMemcpyDeviceToDevice, L.s));
+	}
+	return L.close();
 }

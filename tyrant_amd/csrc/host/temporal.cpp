@@ -22,7 +22,6 @@ namespace {
 constexpr uint32_t kDefaultMaxHistory = 16;
 constexpr float kDefaultDepthTolerance = 0.05f;
 constexpr float kDefaultNormalCos = 0.9f;
-constexpr uint32_t kMaxHistory = 1024;
 
 // position, direction, basis and the basis' squared lengths of a camera, as the projection reads them
 void camera_fields(const tyr_ctx* c, const tyr_camera& cam, float pos[3], float dir[3], float right[3], float up[3], float& FF, float& RR, float& UU) {
@@ -33,26 +32,6 @@ void camera_fields(const tyr_ctx* c, const tyr_camera& cam, float pos[3], float 
 	RR = dot(ld3(right), ld3(right));
 	UU = dot(ld3(up), ld3(up));
 }
-
-} // namespace
-
-namespace tyr {
-namespace drv {
-
-void temporal_free(tyr_ctx* c) {
-	if (c->temporalDone) {
-		(void)hipEventSynchronize(c->temporalDone);
-		(void)hipEventDestroy(c->temporalDone);
-		c->temporalDone = nullptr;
-	}
-	dev_free(c->dTemporal);
-	c->temporalHave = false;
-}
-
-} // namespace drv
-} // namespace tyr
-
-namespace {
 
 // both motion passes; via: tyr_render_motion_chain's chain inputs, or null
 int render_motion(tyr_ctx* c, const tyr_motion_in* in, const tyr_motion_chain_in* via, const tyr_motion_out* out, void* stream) {
@@ -108,28 +87,21 @@ int tyr_temporal(tyr_ctx* c, const tyr_temporal_in* in, const tyr_temporal_param
 	tyr_temporal_params p{ kDefaultMaxHistory, kDefaultDepthTolerance, kDefaultNormalCos, 0u };
 	if (params)
 		p = *params;
-	if (p.max_history < 1 || p.max_history > kMaxHistory || !(p.depth_tolerance > 0.f) || !std::isfinite(p.depth_tolerance) || !(p.normal_cos >= -1.f && p.normal_cos <= 1.f) ||
-	    (p.flags & ~TYR_TEMPORAL_RESET) != 0u)
+	if (!reprojection_ok(p.max_history, p.depth_tolerance, p.normal_cos) || (p.flags & ~TYR_TEMPORAL_RESET) != 0u)
 		return TYR_ERR_INVALID;
 	const float4* accum = in->accum ? reinterpret_cast<const float4*>(in->accum) : c->blit;
 	if (!accum)
 		return TYR_ERR_NO_BUFFER;
-	DeviceScope scope;
-	if (int rc = scope.enter(c))
+	FilterLaunch L;
+	if (int rc = L.open(c, c->temporal, stream))
 		return rc;
 	const size_t n = static_cast<size_t>(c->cfg.width) * c->cfg.height;
-	if (!c->dTemporal) {
-		if (int rc = dev_alloc(c->dTemporal, 4 * n))
-			return rc;
-		c->temporalHave = false;
-	}
-	if (!c->temporalDone)
-		HIPCHK(hipEventCreateWithFlags(&c->temporalDone, hipEventDisableTiming));
-	const hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-	HIPCHK(hipStreamWaitEvent(s, c->temporalDone, 0)); // the previous call's history (a no-op before the first record)
+	if (int rc = L.buffer(c->dTemporal, 4 * n))
+		return rc;
 
-	const uint32_t prev = c->temporalCur, next = prev ^ 1u;
 	TemporalParams P{};
+	P.haveHistory = L.history((p.flags & TYR_TEMPORAL_RESET) != 0u);
+	const uint32_t prev = L.prev, next = L.next;
 	P.accum = accum;
 	P.albedo = in->albedo;
 	P.normal = in->normal;
@@ -147,11 +119,6 @@ int tyr_temporal(tyr_ctx* c, const tyr_temporal_in* in, const tyr_temporal_param
 	P.maxHistory = static_cast<float>(p.max_history);
 	P.depthTolerance = p.depth_tolerance;
 	P.normalCos = p.normal_cos;
-	P.haveHistory = c->temporalHave && (p.flags & TYR_TEMPORAL_RESET) == 0u;
-	launch_temporal(P, s);
-	HIPCHK(hipGetLastError());
-	HIPCHK(hipEventRecord(c->temporalDone, s));
-	c->temporalCur = next;
-	c->temporalHave = true;
-	return TYR_OK;
+	launch_temporal(P, L.s);
+	return L.close();
 }
