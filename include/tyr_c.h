@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_query_winding, tyr_scene_moments, TYR_FLAG_WINDING and tyr_vecmath_probe ops 50-52; tyr_query_sweep and tyr_sweep_out; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_query_winding, tyr_scene_moments, TYR_FLAG_WINDING and tyr_vecmath_probe ops 50-52; tyr_query_sweep and tyr_sweep_out; tyr_query_box, tyr_box_out, TYR_QUERY_BOX_ANY and TYR_QUERY_BOX_MAX; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -808,7 +808,8 @@ int tyr_query_occlusion(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 *
  * sees the refitted scene and its rebuilt moments.
  * TYR_ERR_INVALID: ctx, points or w_out NULL, n >= 2^31, an accuracy that is NaN or negative; TYR_ERR_UNSUPPORTED: a ctx
  * without TYR_FLAG_WINDING; TYR_ERR_NO_SCENE: nothing uploaded.
- * Not part of it: higher-order expansions, the spheres, a signed-distance call, a voxel-grid helper, point clouds. */
+ * Not part of it: higher-order expansions, the spheres, a signed-distance call, a voxel-grid helper (tyr_query_box answers the surface
+ * voxels, this call the solid ones at their centres), point clouds. */
 int tyr_query_winding(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3, device */, float accuracy, float* w_out /* n */,
                       uint32_t* terms_out /* n x 2, NULL ok */, void* stream);
 /* Test hook in the spirit of tyr_scene_hash: nodes first .. first + count - 1 of the moment tree the ctx holds, read back into
@@ -872,7 +873,7 @@ int tyr_scene_moments(tyr_ctx* ctx, int32_t first, int32_t count, double* host_o
  * out->normal n x 3 (each may be NULL).
  * TYR_ERR_INVALID: ctx, origins, directions, radius, out, out->t or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE:
  * nothing uploaded.
- * Not part of it: the sphere table (flags must be 0), capsules and boxes, all contacts rather than the first, rotating or
+ * Not part of it: the sphere table (flags must be 0), capsules and moving boxes (a box at rest: tyr_query_box), all contacts rather than the first, rotating or
  * deforming bodies, triangles that move during the sweep, penetration depth beyond what `normal` carries. */
 typedef struct tyr_sweep_out {
 	float*   t;       /* n, required */
@@ -885,6 +886,70 @@ typedef struct tyr_sweep_out {
 int tyr_query_sweep(tyr_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* radius /* n */,
                     const float* tmax /* n, or NULL: 1 = the whole displacement d */, uint32_t flags /* must be 0 */,
                     const tyr_sweep_out* out, void* stream);
+
+/* ---- box-overlap queries (extension) --------------------------------------------------------------------------------------
+ * "Which triangles are in this box, and is there anything in it at all?" for a caller's batch of axis-aligned boxes [lo, hi],
+ * against the scene the ctx holds: the surface voxels of a voxelisation (the solid fill is tyr_query_winding at the voxel
+ * centres), the broadphase of box-shaped bodies, the eight children of an octree or sparse-grid node, "give me the triangles
+ * in this region".  The contract is a set over all triangles of the uploaded array with no traversal order in it.
+ *
+ * All arithmetic is binary64, one IEEE operation per operation written, nothing contracted; inputs (triangle records, lo, hi)
+ * are binary32 widened exactly.  dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z; cross is the "Winding numbers" block's; vector -
+ * is componentwise; min(a, b) = b < a ? b : a; max(a, b) = b > a ? b : a.  For finite corners and a valid box no operand
+ * overflows or becomes NaN: differences are below 2^129, an axis below 2^259, every product and sum below 2^400.
+ *
+ * Triangle corners: the "Swept-sphere queries" block's -- A = vert, B = the BINARY32 sum vert + e1, C = the binary32 sum
+ * vert + e2, all widened: exactly the corners tyr_triangle_bboxes bounds.  e1' = B - A, e2' = C - A (binary64).
+ *
+ * A box is valid when every component of lo and hi is finite and lo_k <= hi_k on every axis; a box of zero extent on any axes
+ * (a point, a segment, a rectangle) is valid.
+ *
+ * Member test of a (box, triangle) pair.  Both sets are closed, so touching counts.  The pair is a member when none of these
+ * 13 axes separates, tested in this order:
+ *  1. The box axes k = x, y, z: separated when min(A_k, min(B_k, C_k)) > hi_k or max(A_k, max(B_k, C_k)) < lo_k -- exact
+ *     comparisons of the inputs.
+ *  Relative to A for the others: l = lo - A, h = hi - A.  For an axis a and the triangle's projections ps:
+ *       bmin(a) = (min(a.x*l.x, a.x*h.x) + min(a.y*l.y, a.y*h.y)) + min(a.z*l.z, a.z*h.z),  bmax(a) likewise with max
+ *       separated when max(ps) < bmin(a) or min(ps) > bmax(a)
+ *  2. The plane: a = cross(e1', e2'), ps = {0}.
+ *  3. Nine edge axes: for i = x, y, z (outer) and f = e1', e2' - e1', e2' (inner), a = cross(unit_i, f) with the zeros and ones
+ *     multiplied out as written, ps = {0, dot(a, e1'), dot(a, e2')}.
+ * A degenerate triangle needs no special case: for a segment or a point the plane axis is 0 and separates nothing, and the other
+ * axes are the segment-box or point-box test.  Against the same 13 axes in exact rational arithmetic on the same inputs the
+ * binary64 test gives the same answer on every pair of the test families (DESIGN.md "Box-overlap queries").
+ *
+ * Answer per box, W = { i : (box, triangle i) is a member } over all triangles of the uploaded array (after a refit: the new
+ * records).  Without TYR_QUERY_BOX_ANY: count = |W|, NOT capped by max_prims; the min(max_prims, |W|) lowest build-order indices
+ * of W go into the box's row, ascending, unused entries -1; max_prims == 0 is allowed and out->prim is then ignored: a count
+ * alone.  With TYR_QUERY_BOX_ANY: max_prims must be 0, count = W is empty ? 0 : 1, and the walk may stop at the first member.
+ * An invalid box: count = 0 and a row of -1; a scene without triangles answers every box that way.  Hence the row for k is the
+ * first k entries of the row for any larger k, ANY equals count > 0, and a box answers the same whatever else is in the batch.
+ * count > max_prims: split the box and ask again.
+ *
+ * Pruning is exact and needs no slack.  A node's stored binary32 box contains the corners A, B, C of every triangle below it,
+ * so a node whose box fails the closed interval test against [lo, hi] on some axis has every corner below it beyond that face:
+ * rule 1 separates each of its triangles, and it holds no member.  Scope of this guarantee: tyr_query_nearest's -- trees from
+ * tyr_bvh_build, tyr_bvh_build_device, tyr_scene_build_upload, and tyr_scene_refit with bboxes = NULL or containing boxes.
+ *
+ * Arrays, streams and state follow tyr_query_hits: every array pointer is a DEVICE pointer, contiguous, float32 / int32 /
+ * uint32, indexed with 64-bit offsets -- lo, hi n x 3.  While the call runs, a box's row of out->prim is its working buffer.
+ * n up to 2^31 - 1, independent of queue_size; n == 0: TYR_OK and nothing launched.  The work is enqueued on `stream` (NULL: the
+ * ctx's stream); the call uses the ctx's device, restores the caller's and touches no render state.  A later tyr_scene_refit
+ * waits for it, a query issued after a refit sees the refitted scene, and a traversal stack overflow sets bit 1 of
+ * tyr_query_error.
+ * TYR_ERR_INVALID: ctx, lo, hi, out or out->count NULL, out->prim NULL with max_prims > 0, n >= 2^31, max_prims above
+ * TYR_QUERY_BOX_MAX, a flag other than TYR_QUERY_BOX_ANY, or TYR_QUERY_BOX_ANY with max_prims != 0; TYR_ERR_NO_SCENE: nothing
+ * uploaded.
+ * Not part of it: the sphere table, oriented boxes, more than TYR_QUERY_BOX_MAX indices per box, a voxel-grid call, clipping
+ * the triangles to the box. */
+#define TYR_QUERY_BOX_ANY 4u      /* tyr_query_box only */
+#define TYR_QUERY_BOX_MAX 32
+typedef struct tyr_box_out {
+	uint32_t* count;   /* n, required */
+	int32_t*  prim;    /* n x max_prims, required when max_prims > 0; build-order index, -1 = unused entry */
+} tyr_box_out;
+int tyr_query_box(tyr_ctx* ctx, uint32_t n, const float* lo /* n x 3 */, const float* hi /* n x 3 */,
+                  uint32_t max_prims, uint32_t flags, const tyr_box_out* out, void* stream);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

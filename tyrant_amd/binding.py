@@ -32,6 +32,8 @@ TYR_ERR_UNSUPPORTED = -7
 TYR_QUERY_SPHERES = 1
 TYR_QUERY_TWO_SIDED = 2  # tyr_query_hits only
 TYR_QUERY_HITS_MAX = 32
+TYR_QUERY_BOX_ANY = 4  # tyr_query_box only
+TYR_QUERY_BOX_MAX = 32
 TYR_QUERY_NEAREST_K_MAX = 32
 TYR_QUERY_OCCLUSION_MAX_SAMPLES = 1024
 AOV_CHAIN_MAX = 8  # TYR_AOV_CHAIN_MAX
@@ -143,6 +145,12 @@ class SweepOut(C.Structure):
     """tyr_sweep_out: device pointers of tyr_query_sweep's outputs; region, point, center, normal may be NULL"""
 
     _fields_ = [("t", P), ("prim", P), ("region", P), ("point", P), ("center", P), ("normal", P)]
+
+
+class BoxOut(C.Structure):
+    """tyr_box_out: device pointers of tyr_query_box's outputs; prim may be NULL when max_prims is 0"""
+
+    _fields_ = [("count", P), ("prim", P)]
 
 
 class HitsOut(C.Structure):
@@ -305,6 +313,7 @@ SYMBOLS = {
     "tyr_query_nearest": (C.c_int, [P, c_u32, P, P, c_u32, P, P]),
     "tyr_query_nearest_k": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_sweep": (C.c_int, [P, c_u32, P, P, P, P, c_u32, P, P]),
+    "tyr_query_box": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
     "tyr_query_winding": (C.c_int, [P, c_u32, P, C.c_float, P, P, P]),
@@ -777,6 +786,31 @@ class Renderer:
         out = SweepOut(*_dptrs(*outs))
         self._query_call("tyr_query_sweep", stream, staged, n, *_dptrs(o, d, r, tm), 0, C.byref(out))
         return tuple(outs) if normal else tuple(outs[:5])
+
+    def query_box(self, lo, hi, max_prims=0, any=False, stream=None):
+        """tyr_query_box: for every axis-aligned box [lo, hi] the triangles of the uploaded scene it touches (include/tyr_c.h
+        "Box-overlap queries"; touching counts).  lo, hi: (N, 3) float32 -- torch tensors on this ctx's device, taken as they are,
+        or numpy arrays.  Returns count, (N,) int32 (the library's uint32): every triangle the box touches, not capped by
+        max_prims; with max_prims > 0 (count, prim), prim (N, max_prims) int32 the lowest build-order indices of them, ascending,
+        unused entries -1; with any=True (max_prims must be 0) a bool tensor, count > 0, from a walk that stops at the first
+        triangle.  An invalid box (a NaN or infinite component, lo > hi on an axis) touches nothing."""
+        import contextlib
+
+        import torch
+
+        k = int(max_prims)
+        if not 0 <= k <= TYR_QUERY_BOX_MAX:
+            raise ValueError(f"max_prims: 0 .. {TYR_QUERY_BOX_MAX}")
+        if any and k:
+            raise ValueError("any=True answers without indices: max_prims must be 0")
+        n, ins, staged = self._query_inputs(("lo", lo, (3,)), ("hi", hi, (3,)))
+        cnt, prim = self._query_outputs(n, ((), torch.int32), ((k,), torch.int32) if k else None)
+        out = BoxOut(*_dptrs(cnt, prim))
+        self._query_call("tyr_query_box", stream, staged, n, *_dptrs(*ins), k, TYR_QUERY_BOX_ANY if any else 0, C.byref(out))
+        if any:
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                return cnt != 0
+        return (cnt, prim) if k else cnt
 
     def query_nearest_k(self, points, k, max_dist=None, count=False, stream=None):
         """tyr_query_nearest_k: for every point the k nearest triangles of the uploaded scene inside max_dist (include/tyr_c.h
