@@ -10,19 +10,18 @@ import ctypes as C
 import functools
 import hashlib
 import os
-import re
 
 import numpy as np
 import pytest
 
 import box_ref as ref
-from conftest import GOLDEN, ROOT, built_scene
-from kernel_resources import kernel_resources
-from test_point_query import OFFSET, box_points, build, duplicated, lattice, offset_soup, stack40, surface_points
+from conftest import GOLDEN, built_scene
+from query_support import (OFFSET, assert_kernel_budget, assert_query_abi, assert_render_undisturbed, box_points, build, deformed, duplicated, lattice, launch_bounds_blocks,
+                           no_triangles, offset_soup, on_side_stream, renderer, stack40, surface_points, tri)
+from query_support import same as same_outputs
 
 F = np.float32
 D = np.float64
-LDS_PER_CU, LDS_GRANULE = 163840, 1280
 C3_ANSWERS = os.path.join(GOLDEN, "box_c3.npz")
 INF = F(np.inf)
 KMAX = 32
@@ -36,15 +35,6 @@ def down(x):
     return np.nextafter(F(x), -INF)
 
 
-def tri(vert, e1, e2):
-    """one triangle record from vert, e1, e2 as given"""
-    from tyrant_amd import scenes
-
-    t = np.zeros(1, dtype=scenes.TRIANGLE_DTYPE)
-    t["vert"], t["e1"], t["e2"] = np.array(vert, F), np.array(e1, F), np.array(e2, F)
-    return t
-
-
 # ---- fixtures (numpy only) --------------------------------------------------------------------------------------------
 def cubes(rng, centres, lo_exp=-1.0, hi_exp=1.2):
     """boxes round `centres` with seeded half extents of 10^lo_exp .. 10^hi_exp per axis"""
@@ -55,7 +45,7 @@ def cubes(rng, centres, lo_exp=-1.0, hi_exp=1.2):
 @functools.lru_cache(maxsize=None)
 def lattice_case():
     """heightfield(32), grid step 3.125 (exact in binary32): (nodes, prims, (lo, hi), the parts' slices, (count, prim) for 32)"""
-    nodes, prims, grid, _ = lattice(32)
+    nodes, prims, grid, _ = lattice(32, 21)
     rng = np.random.default_rng(61)
     xs = np.linspace(-50.0, 50.0, 33).astype(F)
     step = F(3.125)
@@ -250,7 +240,7 @@ def test_pruning_argument_holds_on_the_fixtures_trees():
     leaves' primitive ranges follow each other in node order, so members arrive ascending."""
     from tyrant_amd import scenes
 
-    trees = [lattice(32)[:2], duplicated()[:2], build(stack40()), offset_soup(False), offset_soup(True), build(scenes.heightfield(16)), build(scenes.cornell_box().triangles)]
+    trees = [lattice(32, 21)[:2], duplicated(22, 2048)[:2], build(stack40()), offset_soup(False), offset_soup(True), build(scenes.heightfield(16)), build(scenes.cornell_box().triangles)]
     for nodes, prims in trees:
         nested, holds, offsets, counts = tree_facts(nodes, prims)
         assert nested and holds
@@ -269,7 +259,7 @@ def test_fixtures_reach_what_they_are_for():
     assert hist[0] >= 200 and (hist[1:] >= 10).all(), hist.tolist()
     nodes, prims, (lo, hi), parts, (cnt, prim) = lattice_case()
     assert (cnt == 0).sum() >= 20 and ((cnt > 0) & (cnt <= 5)).sum() >= 20 and (cnt > 5).sum() >= 20 and (cnt > KMAX).sum() >= 20
-    grid = lattice(32)[2][:, :2]
+    grid = lattice(32, 21)[2][:, :2]
     v = (lo[parts["vertex"]] + F(0.5))[:, :2]
     inner = (np.abs(v) < 49).all(axis=1)
     assert inner.sum() >= 64 and (cnt[parts["vertex"]][inner] == 6).all() and len(grid) == 33 * 33
@@ -285,41 +275,15 @@ def test_box_kernels_keep_registers_and_lds_in_budget():
     """exactly two k_query_box kernels (with and without ANY); no vector spills; scratch no larger than the LdsStack's private
     spill array (52 entries of 4 bytes, plus the frame's alignment); LDS (12,288 + 7,168 bytes) that admits the blocks per CU the
     launch bounds plan for.  The occupancy reached is printed (DESIGN.md "Box-overlap queries" records it), not prescribed."""
-    res = kernel_resources("box")
-    names = [n for n in res if "k_query_box" in n]
-    assert len(names) == 2, list(res)
-    src = open(os.path.join(ROOT, "tyrant_amd", "csrc", "hip", "box.hip")).read()
-    planned = int(re.search(r"__launch_bounds__\(kBlock, (\d+)\) k_query_box", src).group(1))
-    for name in names:
-        k = res[name]
-        print(name, k)
-        assert k["VGPRs Spill"] == 0, k
-        assert k["ScratchSize [bytes/lane]"] <= (64 - 12) * 4 + 16, k
-        assert k["LDS Size [bytes/block]"] <= 12288 + 7168, k
-        per_block = -(-k["LDS Size [bytes/block]"] // LDS_GRANULE) * LDS_GRANULE
-        assert LDS_PER_CU // per_block >= planned and k["Occupancy [waves/SIMD]"] >= planned, k
+    assert_kernel_budget("box", "k_query_box", 2, (64 - 12) * 4 + 16, 12288 + 7168, planned=launch_bounds_blocks("box", "k_query_box"))
 
 
 def test_abi_declares_and_exports_the_query(hip):
-    hdr = open(os.path.join(ROOT, "include", "tyr_c.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+tyr_query_box\s*\(", code) and re.search(r"\}\s*tyr_box_out\s*;", code)
-    assert re.search(r"#define\s+TYR_QUERY_BOX_ANY\s+4u\b", code) and re.search(r"#define\s+TYR_QUERY_BOX_MAX\s+32\b", code)
-    assert re.search(r"#define\s+TYR_ABI_VERSION\s+5\b", code)
-    L = hip.lib()
-    assert hasattr(L, "tyr_query_box") and "tyr_query_box" in hip.SYMBOLS
-    assert L.tyr_abi_version() == 5
-    assert C.sizeof(hip.BoxOut) == 2 * C.sizeof(C.c_void_p)
+    assert_query_abi(hip, "tyr_query_box", "tyr_box_out", hip.BoxOut, 2, (r"TYR_QUERY_BOX_ANY\s+4u\b", r"TYR_QUERY_BOX_MAX\s+32\b"))
     assert (hip.TYR_QUERY_BOX_ANY, hip.TYR_QUERY_BOX_MAX) == (4, KMAX)
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
-def renderer(hip, nodes, prims, flags=0):
-    g = hip.Renderer(64, 64, 4096, flags=flags)
-    g.upload(nodes, prims)
-    return g
-
-
 def ask(g, lo, hi, k=0, **kw):
     """(count, prim) as numpy arrays; prim of shape (n, 0) for a count alone"""
     res = g.query_box(np.array(lo), np.array(hi), max_prims=k, **kw)
@@ -328,9 +292,7 @@ def ask(g, lo, hi, k=0, **kw):
     return cnt, (prim.cpu().numpy() if k else np.zeros((len(cnt), 0), np.int32))
 
 
-def same(got, want, what=""):
-    for name, a, b in zip(("count", "prim"), got, want):
-        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs at {np.argwhere(a != b)[:5].tolist()} ({np.count_nonzero(a != b)} values)"
+same = functools.partial(same_outputs, ("count", "prim"))
 
 
 def check(g, prims, lo, hi, k, what=""):
@@ -370,16 +332,11 @@ def test_duplicated_triangles_and_the_over_long_leaf(hip):
     (an over-long leaf behind synthetic records), alone and next to the Cornell box, with rows of 1, 5 and 32"""
     from tyrant_amd import scenes
 
-    nodes, prims, pts = duplicated()
+    nodes, prims, pts, twin = duplicated(22, 2048)
     rng = np.random.default_rng(63)
     lo, hi = cubes(rng, np.concatenate([pts[:289] - np.array([0, 0, 40], F), surface_points(rng, prims, 351, 1.0)]), -1.0, 0.8)
     g = renderer(hip, nodes, prims)
     cnt, prim = check(g, prims, lo, hi, KMAX, "duplicated")
-    raw = np.ascontiguousarray(prims).view(np.uint8).reshape(len(prims), -1)
-    twins = np.lexsort(raw.T[::-1]).reshape(-1, 2)  # equal records are neighbours in the sorted order: pairs
-    assert np.array_equal(raw[twins[:, 0]], raw[twins[:, 1]])
-    twin = np.empty(len(prims), np.int64)
-    twin[twins[:, 0]], twin[twins[:, 1]] = twins[:, 1], twins[:, 0]
     whole = (cnt > 0) & (cnt <= KMAX)
     assert whole.sum() >= 100 and (cnt[whole] % 2 == 0).all()
     for row, c in zip(prim[whole], cnt[whole]):
@@ -422,7 +379,6 @@ def test_shapes_flags_hostile_input_and_batch_sizes(hip):
     """the lattice: rows of 0, 1, 5 and 32 are prefixes of each other; ANY equals count > 0; n = 1 .. 4097; the same boxes
     shuffled answer the same; NaN, infinite and inverted boxes among good ones touch nothing and disturb nothing; a scene
     without triangles"""
-    from tyrant_amd import scenes
 
     nodes, prims, (lo, hi), parts, want32 = lattice_case()
     rng = np.random.default_rng(65)
@@ -454,7 +410,7 @@ def test_shapes_flags_hostile_input_and_batch_sizes(hip):
         g.query_box(lo, hi, max_prims=KMAX + 1)
     with pytest.raises(ValueError):
         g.query_box(lo, hi, max_prims=1, any=True)
-    g.upload(np.zeros(0, dtype=scenes.NODE_DTYPE), np.zeros(0, dtype=scenes.TRIANGLE_DTYPE))
+    g.upload(*no_triangles())
     same(ask(g, lo, hi, 5), ref.box(lo, hi, prims[:0], 5), "empty scene")
     assert not g.query_box(lo, hi, any=True).any().item()
     assert g.query_error() == 0
@@ -465,7 +421,6 @@ def test_shapes_flags_hostile_input_and_batch_sizes(hip):
 def test_box_queries_leave_the_render_alone(hip):
     """a Cornell-box render (64 x 64, 2 spp) with box queries between its tyr_render calls: the same accumulation buffer and
     counters as without them"""
-    from conftest import bits
     from tyrant_amd import binding, scenes
 
     sc = scenes.cornell_box()
@@ -474,27 +429,11 @@ def test_box_queries_leave_the_render_alone(hip):
     lo, hi = cubes(rng, box_points(rng, prims, 20000), -1.0, 1.3)
     want = ref.box(lo, hi, prims, 4)
 
-    def run(with_queries):
-        g = binding.Renderer(64, 64, 4096)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            same(ask(g, lo, hi, 4), want, "between two renders")
-            g.query_box(lo, hi, any=True)
-        g.render(1)
-        out = (g.blit_buffer(), g.counters())
-        g.close()
-        return out
+    def between(g):
+        same(ask(g, lo, hi, 4), want, "between two renders")
+        g.query_box(lo, hi, any=True)
 
-    b0, k0 = run(False)
-    b1, k1 = run(False)
-    bq, kq = run(True)
-    assert kq == k0, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)):  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0))
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
+    assert_render_undisturbed(between)
 
 
 @pytest.mark.gpu
@@ -511,21 +450,14 @@ def test_refit_side_stream_and_invalid_arguments(hip):
     n = 1000
     lo, hi = cubes(rng, surface_points(rng, prims, n, 2.0), -0.5, 0.8)
     check(g, prims, lo, hi, 8, "before the refit")
-    moved = prims.copy()
-    moved["vert"][:, 2] += (4.0 * np.sin(moved["vert"][:, 0] * 0.2)).astype(F)
-    moved["e1"][:, 2] *= F(1.5)
+    moved = deformed(prims, 4.0)
     g.refit(moved)
     check(g, moved, lo, hi, 8, "after the refit")
     want = ref.box(lo, hi, moved, 8)
     assert not np.array_equal(want[0], ref.box(lo, hi, prims, 8)[0])
     # a side stream, device tensors taken in place; then the ctx's own stream (NULL) through the C call
     tl, th = torch.from_numpy(lo).cuda(), torch.from_numpy(hi).cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        cnt, prim = g.query_box(tl, th, max_prims=8, stream=side)
-        hit = g.query_box(tl, th, any=True, stream=side)
-    side.synchronize()
+    (cnt, prim), hit = on_side_stream(lambda side: (g.query_box(tl, th, max_prims=8, stream=side), g.query_box(tl, th, any=True, stream=side)))
     same((cnt.cpu().numpy(), prim.cpu().numpy()), want, "side stream")
     assert np.array_equal(hit.cpu().numpy(), want[0] > 0)
 

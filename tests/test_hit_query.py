@@ -10,47 +10,26 @@ import ctypes as C
 import functools
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
 
 import hits_ref as ref
-from conftest import GOLDEN, ROOT, bits
-from kernel_resources import kernel_resources
+from conftest import GOLDEN, bits
+from query_support import (assert_kernel_budget, assert_query_abi, assert_render_undisturbed, build, deformed, no_triangles, on_side_stream, query_exists, renderer, stack40,
+                           take, unit)
+from query_support import same as same_outputs
 
 F = np.float32
-LDS_PER_CU, LDS_GRANULE = 163840, 1280
 VERY_FAR = F(1e20)
 NAMES = ("count", "t", "prim", "uv", "side", "back_count")
 SOUP_EDGE = 16.0
 
 
-@pytest.fixture(autouse=True)
-def _the_query_exists(hip):
-    """nothing here means anything without the entry point: every test of this module needs it"""
-    assert "tyr_query_hits" in hip.SYMBOLS and hasattr(hip.lib(), "tyr_query_hits")
+_the_query_exists = query_exists("tyr_query_hits")  # nothing here means anything without the entry point
 
 
 # ---- fixtures (numpy only; made once, never changed) ------------------------------------------------------------------
-def build(tris):
-    from tyrant_amd import binding
-
-    return binding.bvh_build(tris)
-
-
-def unit(d):
-    d = np.asarray(d, np.float64)
-    return (d / np.linalg.norm(d, axis=-1, keepdims=True)).astype(F)
-
-
-def stack40():
-    """40 identical triangles in the plane y = 0, facing -y: one over-long leaf behind synthetic records"""
-    from tyrant_amd import scenes
-
-    return scenes.make_triangles(np.tile([-30, 0, 10], (40, 1)), np.tile([30, 0, 10], (40, 1)), np.tile([0, 0, 70], (40, 1)))
-
-
 def quads48():
     """48 squares [-20, 20] x [10, 50] in the planes y = 0, 0.5, .. 23.5, two triangles each, facing -y"""
     from tyrant_amd import scenes
@@ -268,54 +247,22 @@ def test_fixtures_reach_what_they_are_for():
 def test_hits_kernels_keep_registers_and_lds_in_budget():
     """both instantiations: no vector spills; scratch no larger than the LdsStack's private spill arrays plus alignment -- so
     the k-buffer is not in scratch; occupancy and LDS that admit the five blocks per CU the launch bounds name"""
-    res = kernel_resources("hits")
-    for two in (0, 1):
-        names = [n for n in res if f"k_query_hitsILb{two}E" in n]
-        assert len(names) == 1, list(res)
-        k = res[names[0]]
-        print(names[0], k)
-        assert k["VGPRs Spill"] == 0, k
-        assert k["ScratchSize [bytes/lane]"] <= (64 - 12) * 8 + 16, k
-        assert k["Occupancy [waves/SIMD]"] >= 5, k
-        per_block = -(-k["LDS Size [bytes/block]"] // LDS_GRANULE) * LDS_GRANULE
-        assert LDS_PER_CU // per_block >= 5, k
+    assert_kernel_budget("hits", r"k_query_hitsILb[01]E", 2, (64 - 12) * 8 + 16)
 
 
 def test_abi_declares_and_exports_the_query(hip):
-    hdr = open(os.path.join(ROOT, "include", "tyr_c.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+tyr_query_hits\s*\(", code) and re.search(r"\}\s*tyr_hits_out\s*;", code)
-    assert re.search(r"#define\s+TYR_QUERY_TWO_SIDED\s+2u", code) and re.search(r"#define\s+TYR_QUERY_HITS_MAX\s+32\b", code)
-    assert re.search(r"#define\s+TYR_ABI_VERSION\s+5\b", code)
-    L = hip.lib()
-    assert hasattr(L, "tyr_query_hits") and "tyr_query_hits" in hip.SYMBOLS
-    assert L.tyr_abi_version() == 5
-    assert C.sizeof(hip.HitsOut) == 6 * C.sizeof(C.c_void_p)
+    assert_query_abi(hip, "tyr_query_hits", "tyr_hits_out", hip.HitsOut, 6, (r"TYR_QUERY_TWO_SIDED\s+2u", r"TYR_QUERY_HITS_MAX\s+32\b"))
     assert hip.TYR_QUERY_TWO_SIDED == 2 and hip.TYR_QUERY_HITS_MAX == 32
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
-def renderer(hip, nodes, prims, flags=0):
-    g = hip.Renderer(64, 64, 4096, flags=flags)
-    g.upload(nodes, prims)
-    return g
-
-
 def ask(g, o, d, tmax=None, max_hits=4, two_sided=False, **kw):
     o, d, tmax = np.array(o), np.array(d), None if tmax is None else np.array(tmax)  # (the fixtures' arrays are read-only: torch wants its own)
     res = tuple(x.cpu().numpy() for x in g.query_hits(o, d, tmax, max_hits=max_hits, two_sided=two_sided, **kw))
     return (res[0].view(np.uint32),) + res[1:5] + (res[5].view(np.uint32),)
 
 
-def same(got, want, what=""):
-    for name, a, b in zip(NAMES, got, want):
-        if a.dtype == np.float32:
-            a, b = bits(a), bits(b)
-        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs at {np.argwhere(a != b)[:5].tolist()} ({np.count_nonzero(a != b)} values)"
-
-
-def take(ans, idx):
-    return tuple(a[idx] for a in ans)
+same = functools.partial(same_outputs, NAMES)
 
 
 # ---- GPU tests --------------------------------------------------------------------------------------------------------
@@ -396,8 +343,6 @@ def test_hostile_input_and_optional_outputs(hip):
     optional outputs NULL in every combination (what is not passed stays untouched)"""
     import torch
 
-    from tyrant_amd import scenes
-
     nodes, prims, o, d, tmax = fixture("quads48")
     rng = np.random.default_rng(58)
     n = o.shape[0]
@@ -437,11 +382,11 @@ def test_hostile_input_and_optional_outputs(hip):
         used = (True, True, True) + use
         for name, r, w, u in zip(NAMES, res, want, used):
             if u:
-                same((r,), (w,), f"outputs {use}: {name}")
+                same_outputs((name,), (r,), (w,), f"outputs {use}")
             else:
                 assert (r == 7).all(), (use, name)
     # a scene without triangles: every ray a row of unused entries
-    g.upload(np.zeros(0, dtype=scenes.NODE_DTYPE), np.zeros(0, dtype=scenes.TRIANGLE_DTYPE))
+    g.upload(*no_triangles())
     got = ask(g, o, d, tmax, 3, True)
     assert not got[0].any() and not got[5].any() and (got[2] == -1).all() and not got[3].any() and not got[4].any()
     assert np.array_equal(bits(got[1]), bits(np.repeat(tmax[:, None], 3, axis=1)))
@@ -464,27 +409,11 @@ def test_hit_queries_leave_the_render_alone(hip):
     want = ref.Hits(o, d, nodes, prims, None, True)
     assert want.count.max() >= 3
 
-    def run(with_queries):
-        g = binding.Renderer(64, 64, 4096)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            same(ask(g, o, d, None, 4, True), want.answer(4), "between two renders")
-            ask(g, o, d, np.full(n, 90.0, F), 32, False)
-        g.render(1)
-        out = (g.blit_buffer(), g.counters(), g.ray_queue(0, 4096).tobytes(), g.shadow_queue(4096).tobytes())
-        g.close()
-        return out
+    def between(g):
+        same(ask(g, o, d, None, 4, True), want.answer(4), "between two renders")
+        ask(g, o, d, np.full(n, 90.0, F), 32, False)
 
-    b0, k0, q0, s0 = run(False)
-    b1, k1, q1, s1 = run(False)
-    bq, kq, qq, sq = run(True)
-    assert kq == k0, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)) and q0 == q1 and s0 == s1:  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0)) and qq == q0 and sq == s0
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
+    assert_render_undisturbed(between)
 
 
 @pytest.mark.gpu
@@ -498,20 +427,14 @@ def test_refit_side_stream_and_invalid_arguments(hip):
     nodes, prims, o, d, tmax = fixture("heightfield32")
     g = renderer(hip, nodes, prims, flags=64)  # TYR_FLAG_REFIT
     same(ask(g, o, d, tmax, 8, True), reference("heightfield32", True).answer(8), "before the refit")
-    moved = prims.copy()
-    moved["vert"][:, 2] += (2.0 * np.sin(moved["vert"][:, 0] * 0.2)).astype(F)
-    moved["e1"][:, 2] *= F(1.5)
+    moved = deformed(prims, 2.0)
     new_nodes = g.refit(moved, want_nodes=True)
     want = ref.Hits(o, d, new_nodes, moved, tmax, True)
     assert not np.array_equal(want.count, reference("heightfield32", True).count)
     same(ask(g, o, d, tmax, 8, True), want.answer(8), "after the refit")
     # a side stream, device tensors taken in place
     to, td, tt = torch.from_numpy(np.array(o)).cuda(), torch.from_numpy(np.array(d)).cuda(), torch.from_numpy(np.array(tmax)).cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        res = g.query_hits(to, td, tt, max_hits=8, two_sided=True, stream=side)
-    side.synchronize()
+    res = on_side_stream(lambda side: g.query_hits(to, td, tt, max_hits=8, two_sided=True, stream=side))
     res = tuple(x.cpu().numpy() for x in res)
     same((res[0].view(np.uint32),) + res[1:5] + (res[5].view(np.uint32),), want.answer(8), "side stream")
 

@@ -9,19 +9,18 @@ answer on the device for the rays the query reports, independence of batch and o
 the render, streams, refit and argument checks."""
 import ctypes as C
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
 
 import occlusion_ref as ref
-from conftest import ROOT, bits
+from conftest import bits
 from kernel_resources import kernel_resources
+from query_support import assert_query_abi, assert_render_undisturbed, build, check_kernel_budget, deformed, no_triangles, on_side_stream, query_exists, renderer, take
+from query_support import same as same_outputs
 
 F = np.float32
 U = np.uint32
-LDS_PER_CU, LDS_GRANULE = 163840, 1280
 VERY_FAR = F(1e20)
 NAMES = ("visible", "mask", "bent", "origin", "direction")
 SAMPLE_COUNTS = (1, 7, 32, 33, 64, 100)
@@ -35,19 +34,10 @@ def combos_for(S, n=512):
     return COMBOS[:max(1, min(len(COMBOS), 65536 // (n * S)))]
 
 
-@pytest.fixture(autouse=True)
-def _the_query_exists(hip):
-    """nothing here means anything without the entry point: every test of this module needs it"""
-    assert "tyr_query_occlusion" in hip.SYMBOLS and hasattr(hip.lib(), "tyr_query_occlusion")
+_the_query_exists = query_exists("tyr_query_occlusion")  # nothing here means anything without the entry point
 
 
 # ---- fixtures (numpy only; made once, never changed) ------------------------------------------------------------------
-def build(tris):
-    from tyrant_amd import binding
-
-    return binding.bvh_build(tris)
-
-
 def big_triangle():
     """one triangle in the plane z = 0 facing +z, 2e4 across"""
     from tyrant_amd import scenes
@@ -163,15 +153,7 @@ def test_occlusion_kernels_keep_registers_and_lds_in_budget():
     without scratch"""
     res = kernel_resources("occlusion")
     for sph in (0, 1):
-        names = [n for n in res if f"k_occlusionILb{sph}E" in n]
-        assert len(names) == 1, list(res)
-        k = res[names[0]]
-        print(names[0], k)
-        assert k["VGPRs Spill"] == 0, k
-        assert k["ScratchSize [bytes/lane]"] <= (64 - 12) * 4 + 16, k
-        assert k["Occupancy [waves/SIMD]"] >= 5, k
-        per_block = -(-k["LDS Size [bytes/block]"] // LDS_GRANULE) * LDS_GRANULE
-        assert LDS_PER_CU // per_block >= 5, k
+        check_kernel_budget(res, f"k_occlusionILb{sph}E", 1, (64 - 12) * 4 + 16)
     names = [n for n in res if "k_occlusion_bent" in n]
     assert len(names) == 1, list(res)
     print(names[0], res[names[0]])
@@ -179,27 +161,11 @@ def test_occlusion_kernels_keep_registers_and_lds_in_budget():
 
 
 def test_abi_declares_and_exports_the_query(hip):
-    hdr = open(os.path.join(ROOT, "include", "tyr_c.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+tyr_query_occlusion\s*\(", code) and re.search(r"\}\s*tyr_occlusion_out\s*;", code)
-    assert re.search(r"#define\s+TYR_QUERY_OCCLUSION_MAX_SAMPLES\s+1024\b", code)
-    assert re.search(r"#define\s+TYR_ABI_VERSION\s+5\b", code)
-    L = hip.lib()
-    assert hasattr(L, "tyr_query_occlusion") and "tyr_query_occlusion" in hip.SYMBOLS
-    assert L.tyr_abi_version() == 5
-    assert C.sizeof(hip.OcclusionOut) == 5 * C.sizeof(C.c_void_p)
+    assert_query_abi(hip, "tyr_query_occlusion", "tyr_occlusion_out", hip.OcclusionOut, 5, (r"TYR_QUERY_OCCLUSION_MAX_SAMPLES\s+1024\b",))
     assert hip.TYR_QUERY_OCCLUSION_MAX_SAMPLES == 1024
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
-def renderer(hip, nodes, prims, spheres=None, flags=0):
-    g = hip.Renderer(64, 64, 4096, flags=flags)
-    g.upload(nodes, prims)
-    if spheres is not None:
-        g.set_spheres(spheres)
-    return g
-
-
 def ask(g, p, nr, S, md=None, bias=1e-3, seed=0, spheres=False, mask=True, bent=True, rays=True, **kw):
     """query_occlusion's tuple as numpy arrays, the integer ones as the library's uint32 (the fixtures' arrays are read-only:
     torch wants its own)"""
@@ -209,17 +175,7 @@ def ask(g, p, nr, S, md=None, bias=1e-3, seed=0, spheres=False, mask=True, bent=
     return tuple(None if x is None else (x.view(U) if x.dtype == np.int32 else x) for x in res)
 
 
-def same(got, want, what=""):
-    for name, a, b in zip(NAMES, got, want):
-        if a is None:
-            continue
-        if a.dtype == np.float32:
-            a, b = bits(a), bits(b)
-        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs at {np.argwhere(a != b)[:5].tolist()} ({np.count_nonzero(a != b)} values)"
-
-
-def take(ans, idx):
-    return tuple(a[idx] for a in ans)
+same = functools.partial(same_outputs, NAMES)  # (an output that was not asked for is None, and is not compared)
 
 
 def pack(vis):
@@ -241,7 +197,7 @@ def test_bit_for_bit_against_the_restatement(hip, name, S):
     and without a per-point max_dist of 10, +inf and VERY_FAR, bias 0, 1e-3 and 1e-2, two seeds (combos_for: every value at the
     small sample counts, the first of COMBOS at the large ones); the cornell box with its sphere table and TYR_QUERY_SPHERES"""
     nodes, prims, sph, p, nr, mixed = fixture(name)
-    g = renderer(hip, nodes, prims, sph)
+    g = renderer(hip, nodes, prims, spheres=sph)
     n = 512
     for md, bias, seed in combos_for(S):
         want = reference(name, n, S, md, bias, seed, sph is not None)
@@ -272,7 +228,7 @@ def test_the_siblings_answer_on_the_device(hip, name, n, S):
     import torch
 
     nodes, prims, sph, p, nr, mixed = fixture(name)
-    g = renderer(hip, nodes, prims, sph)
+    g = renderer(hip, nodes, prims, spheres=sph)
     spheres = sph is not None
     for md in (None, mixed[:n]):
         visible, mask, bent, origin, direction = g.query_occlusion(np.array(p[:n]), np.array(nr[:n]), samples=S, max_dist=None if md is None else np.array(md), seed=5,
@@ -365,7 +321,7 @@ def test_hostile_input(hip):
     same(ask(g, q, qn, 64, None, 0.0, 17), want, "one triangle")
     # no triangles: the spheres alone, or everything visible
     sc = scenes.cornell_box()
-    none_n, none_p = np.zeros(0, dtype=scenes.NODE_DTYPE), np.zeros(0, dtype=scenes.TRIANGLE_DTYPE)
+    none_n, none_p = no_triangles()
     g.upload(none_n, none_p)
     g.set_spheres(sc.spheres)
     _, _, _, cp, cn, cmd = fixture("cornell")
@@ -382,33 +338,14 @@ def test_hostile_input(hip):
 def test_occlusion_queries_leave_the_render_alone(hip):
     """a Cornell-box render (64 x 64, 2 spp) with occlusion queries between its tyr_render calls: the same accumulation buffer,
     counters and queues as without them"""
-    from tyrant_amd import binding, scenes
-
-    sc = scenes.cornell_box()
-    nodes, prims, sph, p, nr, mixed = fixture("cornell")
+    nodes, prims, sph, p, nr, mixed = fixture("cornell")  # (the Cornell box's own tree and sphere table: what the render loads)
     want = reference("cornell", 512, 32, "mixed", 1e-3, 0x9E3779B9, True)
 
-    def run(with_queries):
-        g = binding.Renderer(64, 64, 4096)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            same(ask(g, p[:512], nr[:512], 32, mixed[:512], 1e-3, 0x9E3779B9, spheres=True), want, "between two renders")
-            ask(g, p, nr, 64, None, 1e-2, 1, spheres=False)
-        g.render(1)
-        out = (g.blit_buffer(), g.counters(), g.ray_queue(0, 4096).tobytes(), g.shadow_queue(4096).tobytes())
-        g.close()
-        return out
+    def between(g):
+        same(ask(g, p[:512], nr[:512], 32, mixed[:512], 1e-3, 0x9E3779B9, spheres=True), want, "between two renders")
+        ask(g, p, nr, 64, None, 1e-2, 1, spheres=False)
 
-    b0, k0, q0, s0 = run(False)
-    b1, k1, q1, s1 = run(False)
-    bq, kq, qq, sq = run(True)
-    assert kq == k0, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)) and q0 == q1 and s0 == s1:  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0)) and qq == q0 and sq == s0
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
+    assert_render_undisturbed(between)
 
 
 @pytest.mark.gpu
@@ -423,20 +360,14 @@ def test_refit_side_stream_and_invalid_arguments(hip):
     g = renderer(hip, nodes, prims, flags=64)  # TYR_FLAG_REFIT
     before = reference("heightfield32", 256, 32, "mixed", 1e-3, 7)
     same(ask(g, p, nr, S, md, 1e-3, 7), before, "before the refit")
-    moved = prims.copy()
-    moved["vert"][:, 2] += (2.0 * np.sin(moved["vert"][:, 0] * 0.2)).astype(F)
-    moved["e1"][:, 2] *= F(1.5)
+    moved = deformed(prims, 2.0)
     new_nodes = g.refit(moved, want_nodes=True)
     want = ref.occlusion(new_nodes, moved, p, nr, S, md, 1e-3, 7)
     assert not np.array_equal(want[0], before[0])
     same(ask(g, p, nr, S, md, 1e-3, 7), want, "after the refit")
     # a side stream, device tensors taken in place
     tp, tn, tm = torch.from_numpy(np.array(p)).cuda(), torch.from_numpy(np.array(nr)).cuda(), torch.from_numpy(np.array(md)).cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        res = g.query_occlusion(tp, tn, samples=S, max_dist=tm, bias=1e-3, seed=7, mask=True, bent=True, rays=True, stream=side)
-    side.synchronize()
+    res = on_side_stream(lambda side: g.query_occlusion(tp, tn, samples=S, max_dist=tm, bias=1e-3, seed=7, mask=True, bent=True, rays=True, stream=side))
     res = [x.cpu().numpy() for x in res]
     same((res[0].view(U), res[1].view(U)) + tuple(res[2:]), want, "side stream")
 

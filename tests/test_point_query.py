@@ -7,6 +7,7 @@ kernel, the ABI.  GPU: lattices with shared edges and vertices, exact ties by in
 bounds and hostile input, batch sizes, optional outputs, isolation from the render, refit, streams, argument checks, and one
 pass on C3's 1 M-triangle tree."""
 import ctypes as C
+import functools
 import itertools
 import os
 import re
@@ -16,86 +17,15 @@ import pytest
 
 import nearest_ref as ref
 from conftest import GOLDEN, ROOT, bits, built_scene
-from kernel_resources import kernel_resources
+from query_support import (OFFSET, assert_kernel_budget, assert_query_abi, assert_render_undisturbed, box_points, build, deformed, duplicated, lattice, no_triangles,
+                           offset_soup, on_side_stream, renderer, stack40, surface_points)
+from query_support import same as same_outputs
 
 F = np.float32
-LDS_PER_CU, LDS_GRANULE = 163840, 1280
-OFFSET = np.array([4096.0, -4096.0, 8192.0], F)
 C3_ANSWERS = os.path.join(GOLDEN, "nearest_c3.npz")
 
 
 # ---- fixtures (numpy only) --------------------------------------------------------------------------------------------
-def build(tris):
-    from tyrant_amd import binding
-
-    return binding.bvh_build(tris)
-
-
-def root_box(prims, inflate=0.1):
-    vert, e1, e2 = ref.records(prims)
-    allv = np.concatenate([vert, vert + e1, vert + e2])
-    lo, hi = allv.min(axis=0), allv.max(axis=0)
-    pad = (hi - lo) * F(inflate)
-    return (lo - pad).astype(F), (hi + pad).astype(F)
-
-
-def box_points(rng, prims, n):
-    lo, hi = root_box(prims)
-    return (lo + (hi - lo) * rng.random((n, 3))).astype(F)
-
-
-def lattice(cells):
-    """(nodes, prims, grid points above every vertex at z = 40, seeded points in the inflated root box)"""
-    from tyrant_amd import scenes
-
-    nodes, prims = build(scenes.heightfield(cells))
-    xs = np.linspace(-50.0, 50.0, cells + 1)
-    X, Y = np.meshgrid(xs, xs, indexing="xy")
-    grid = np.stack([X.reshape(-1), Y.reshape(-1), np.full(X.size, 40.0)], axis=1).astype(F)
-    return nodes, prims, grid, box_points(np.random.default_rng(21), prims, 4096)
-
-
-def duplicated():
-    from tyrant_amd import scenes
-
-    h = scenes.heightfield(16)
-    nodes, prims = build(np.concatenate([h, h]))
-    xs = np.linspace(-50.0, 50.0, 17)
-    X, Y = np.meshgrid(xs, xs, indexing="xy")
-    grid = np.stack([X.reshape(-1), Y.reshape(-1), np.full(X.size, 40.0)], axis=1).astype(F)
-    return nodes, prims, np.concatenate([grid, box_points(np.random.default_rng(22), prims, 2048)])
-
-
-def stack40():
-    from tyrant_amd import scenes
-
-    return scenes.make_triangles(np.tile([-30, 0, 10], (40, 1)), np.tile([30, 0, 10], (40, 1)), np.tile([0, 0, 70], (40, 1)))
-
-
-def offset_soup(slivers):
-    """random_soup(2000) moved by OFFSET; slivers: every tenth triangle's e2 = 0.75 e1 + a perpendicular of 1e-5 |e1|"""
-    from tyrant_amd import scenes
-
-    t = scenes.random_soup(2000)
-    if slivers:
-        e1 = t["e1"][::10].astype(np.float64)
-        perp = np.cross(e1, [0.3, -0.5, 0.8])
-        perp *= 1e-5 * np.linalg.norm(e1, axis=1, keepdims=True) / np.linalg.norm(perp, axis=1, keepdims=True)
-        t["e2"][::10] = (0.75 * e1 + perp).astype(F)
-    t["vert"] = (t["vert"] + OFFSET).astype(F)
-    return build(t)
-
-
-def surface_points(rng, prims, n, noise):
-    """a point of a seeded triangle plus noise"""
-    vert, e1, e2 = ref.records(prims)
-    i = rng.integers(0, len(prims), n)
-    u = rng.random(n)
-    v = rng.random(n) * (1 - u)
-    p = vert[i].astype(np.float64) + u[:, None] * e1[i] + v[:, None] * e2[i]
-    return (p + rng.normal(size=(n, 3)) * noise).astype(F)
-
-
 def tie_fraction(points, prims):
     _, _, ties = ref.brute_values(points, prims)
     return float((ties >= 2).mean())
@@ -212,12 +142,12 @@ def test_fixtures_reach_what_they_are_for():
     the lattice's tree needs more stack than the 12 LDS entries"""
     from tyrant_amd import binding
 
-    nodes, prims, grid, _ = lattice(32)
+    nodes, prims, grid, _ = lattice(32, 21)
     frac = tie_fraction(grid, prims)
     print("lattice(32): fraction of the grid points with a tie", frac)
     assert frac >= 0.5
     assert binding.layout_probe(nodes, prims, want_pairs=False)["quad_max_stack"] > 12
-    nodes, prims, pts = duplicated()
+    nodes, prims, pts, _ = duplicated(22, 2048)
     _, _, ties = ref.brute_values(pts, prims)
     assert (ties >= 2).all()
     nodes, prims = build(stack40())
@@ -227,48 +157,22 @@ def test_fixtures_reach_what_they_are_for():
 def test_nearest_kernel_keeps_registers_and_lds_in_budget():
     """no vector spills; scratch no larger than the LdsStack's private spill arrays (52 entries of 8 bytes, plus the frame's
     alignment); occupancy and LDS (24,576 + 7,168 bytes) that admit the five blocks per CU the launch bounds plan for"""
-    res = kernel_resources("nearest")
-    names = [n for n in res if "k_query_nearest" in n]
-    assert len(names) == 1, list(res)
-    k = res[names[0]]
-    assert k["VGPRs Spill"] == 0, k
-    assert k["ScratchSize [bytes/lane]"] <= (64 - 12) * 8 + 16, k
-    assert k["Occupancy [waves/SIMD]"] >= 5, k
-    assert k["LDS Size [bytes/block]"] <= 24576 + 7168, k
-    per_block = -(-k["LDS Size [bytes/block]"] // LDS_GRANULE) * LDS_GRANULE
-    assert LDS_PER_CU // per_block >= 5, k
+    assert_kernel_budget("nearest", "k_query_nearest", 1, (64 - 12) * 8 + 16, 24576 + 7168)
 
 
 def test_abi_declares_and_exports_the_query(hip):
-    hdr = open(os.path.join(ROOT, "include", "tyr_c.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+tyr_query_nearest\s*\(", code) and re.search(r"\}\s*tyr_nearest_out\s*;", code)
-    assert re.search(r"#define\s+TYR_ABI_VERSION\s+5\b", code)
-    L = hip.lib()
-    assert hasattr(L, "tyr_query_nearest") and "tyr_query_nearest" in hip.SYMBOLS
-    assert L.tyr_abi_version() == 5
-    assert C.sizeof(hip.NearestOut) == 5 * C.sizeof(C.c_void_p)
+    assert_query_abi(hip, "tyr_query_nearest", "tyr_nearest_out", hip.NearestOut, 5)
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
 NAMES = ("dist2", "prim", "uv", "region", "point")
 
 
-def renderer(hip, nodes, prims, flags=0):
-    g = hip.Renderer(64, 64, 4096, flags=flags)
-    g.upload(nodes, prims)
-    return g
-
-
 def ask(g, points, max_dist=None, **kw):
     return tuple(x.cpu().numpy() for x in g.query_nearest(points, max_dist, **kw))
 
 
-def same(got, want, what=""):
-    for name, a, b in zip(NAMES, got, want):
-        if a.dtype == np.float32:
-            a, b = bits(a), bits(b)
-        assert a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs at {np.argwhere(a != b)[:5].tolist()} ({np.count_nonzero(a != b)} values)"
+same = functools.partial(same_outputs, NAMES)
 
 
 def check(g, prims, points, max_dist=None, what=""):
@@ -282,7 +186,7 @@ def check(g, prims, points, max_dist=None, what=""):
 @pytest.mark.gpu
 def test_lattice_and_ties(hip):
     """heightfield(32): points above every grid vertex (most of them equally near to several triangles) and seeded points"""
-    nodes, prims, grid, rand = lattice(32)
+    nodes, prims, grid, rand = lattice(32, 21)
     g = renderer(hip, nodes, prims)
     (d2, prim, uv, region, _), _ = check(g, prims, np.concatenate([grid, rand]), what="lattice")
     assert (prim >= 0).all() and len(np.unique(region)) >= 4
@@ -296,15 +200,9 @@ def test_exact_ties_resolve_to_the_lower_index(hip):
     triangles (an over-long leaf behind synthetic records), alone and next to the Cornell box"""
     from tyrant_amd import scenes
 
-    nodes, prims, pts = duplicated()
+    nodes, prims, pts, twin = duplicated(22, 2048)
     g = renderer(hip, nodes, prims)
     (_, prim, _, _, _), _ = check(g, prims, pts, what="duplicated")
-    raw = np.ascontiguousarray(prims).view(np.uint8).reshape(len(prims), -1)
-    order = np.lexsort(raw.T[::-1])
-    twins = order.reshape(-1, 2)  # equal records are neighbours in the sorted order: pairs
-    assert np.array_equal(raw[twins[:, 0]], raw[twins[:, 1]])
-    twin = np.empty(len(prims), np.int64)
-    twin[twins[:, 0]], twin[twins[:, 1]] = twins[:, 1], twins[:, 0]
     assert (prim < twin[prim]).all()
     for tris in (stack40(), np.concatenate([scenes.cornell_box().triangles, stack40()])):
         nodes, prims = build(tris)
@@ -337,8 +235,6 @@ def test_bounds_hostile_input_and_batch_sizes(hip):
     """max_dist of 0, exactly the distance (strict <: a miss), +inf, NaN, negative; NaN / infinite points; n = 0 .. 4097 and
     400,003; a scene without triangles; every combination of the optional outputs"""
     import torch
-
-    from tyrant_amd import scenes
 
     sc, nodes, prims = built_scene("cornell36")
     g = renderer(hip, nodes, prims)
@@ -389,10 +285,10 @@ def test_bounds_hostile_input_and_batch_sizes(hip):
         assert g.query_error() == 0
         res = [o.cpu().numpy() for o in outs]
         used = (True, True) + use
-        same([r for r, u in zip(res, used) if u], [w[:m] for w, u in zip(want, used) if u], f"outputs {use}")
+        same_outputs([nm for nm, u in zip(NAMES, used) if u], [r for r, u in zip(res, used) if u], [w[:m] for w, u in zip(want, used) if u], f"outputs {use}")
         assert all((r == 7).all() for r, u in zip(res, used) if not u), use
     # a scene without triangles: every point a miss
-    g.upload(np.zeros(0, dtype=scenes.NODE_DTYPE), np.zeros(0, dtype=scenes.TRIANGLE_DTYPE))
+    g.upload(*no_triangles())
     same(ask(g, pts[:5000], md[:5000]), ref.nearest(pts[:5000], prims[:0], md[:5000]), "empty scene")
     assert g.query_error() == 0
     g.close()
@@ -410,27 +306,11 @@ def test_nearest_queries_leave_the_render_alone(hip):
     pts = np.stack([rng.uniform(-40, 40, 20000), rng.uniform(-40, 40, 20000), rng.uniform(5, 80, 20000)], axis=1).astype(F)
     want = ref.nearest(pts, prims)
 
-    def run(with_queries):
-        g = binding.Renderer(64, 64, 4096)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            same(ask(g, pts), want, "between two renders")
-            ask(g, pts, np.full(20000, 5.0, F))
-        g.render(1)
-        out = (g.blit_buffer(), g.counters())
-        g.close()
-        return out
+    def between(g):
+        same(ask(g, pts), want, "between two renders")
+        ask(g, pts, np.full(20000, 5.0, F))
 
-    b0, k0 = run(False)
-    b1, k1 = run(False)
-    bq, kq = run(True)
-    assert kq == k0, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)):  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0))
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
+    assert_render_undisturbed(between)
 
 
 @pytest.mark.gpu
@@ -446,19 +326,13 @@ def test_refit_side_stream_and_invalid_arguments(hip):
     rng = np.random.default_rng(26)
     pts = box_points(rng, prims, 3000)
     check(g, prims, pts, what="before the refit")
-    moved = prims.copy()
-    moved["vert"][:, 2] += (4.0 * np.sin(moved["vert"][:, 0] * 0.2)).astype(F)
-    moved["e1"][:, 2] *= F(1.5)
+    moved = deformed(prims, 4.0)
     g.refit(moved)
     got, want = check(g, moved, pts, what="after the refit")
     assert not np.array_equal(want[1], ref.nearest(pts, prims)[1])
     # a side stream, device tensors taken in place
     tp, tm = torch.from_numpy(pts).cuda(), torch.full((3000,), 6.0).cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        res = g.query_nearest(tp, tm, stream=side)
-    side.synchronize()
+    res = on_side_stream(lambda side: g.query_nearest(tp, tm, stream=side))
     same(tuple(x.cpu().numpy() for x in res), ref.nearest(pts, moved, np.full(3000, 6.0, F)), "side stream")
 
     L, h, P = hip.lib(), g.h, C.c_void_p

@@ -11,80 +11,23 @@ import ctypes as C
 import functools
 import itertools
 import os
-import re
 
 import numpy as np
 import pytest
 
 import nearest_k_ref as kref
 import nearest_ref as ref
-from conftest import GOLDEN, ROOT, bits, built_scene
-from kernel_resources import kernel_resources
+from conftest import GOLDEN, bits, built_scene
+from query_support import (assert_kernel_budget, assert_query_abi, assert_render_undisturbed, box_points, build, deformed, duplicated, lattice, no_triangles, offset_soup,
+                           on_side_stream, renderer, root_box, stack40, surface_points)
+from query_support import same as same_outputs
 
 F = np.float32
-LDS_PER_CU, LDS_GRANULE = 163840, 1280
-OFFSET = np.array([4096.0, -4096.0, 8192.0], F)
 NAMES = ("dist2", "prim", "uv", "region", "point", "count")
 K_MAX = 32
 
 
 # ---- fixtures (numpy only; made once, never changed) ------------------------------------------------------------------
-def build(tris):
-    from tyrant_amd import binding
-
-    return binding.bvh_build(tris)
-
-
-def root_box(prims, inflate=0.1):
-    vert, e1, e2 = ref.records(prims)
-    allv = np.concatenate([vert, vert + e1, vert + e2])
-    lo, hi = allv.min(axis=0), allv.max(axis=0)
-    pad = (hi - lo) * F(inflate)
-    return (lo - pad).astype(F), (hi + pad).astype(F)
-
-
-def box_points(rng, prims, n):
-    lo, hi = root_box(prims)
-    return (lo + (hi - lo) * rng.random((n, 3))).astype(F)
-
-
-def grid_points(cells):
-    xs = np.linspace(-50.0, 50.0, cells + 1)
-    X, Y = np.meshgrid(xs, xs, indexing="xy")
-    return np.stack([X.reshape(-1), Y.reshape(-1), np.full(X.size, 40.0)], axis=1).astype(F)
-
-
-@functools.lru_cache(maxsize=None)
-def lattice(cells):
-    """(nodes, prims, grid points above every vertex at z = 40, seeded points in the inflated root box)"""
-    from tyrant_amd import scenes
-
-    nodes, prims = build(scenes.heightfield(cells))
-    return nodes, prims, grid_points(cells), box_points(np.random.default_rng(31), prims, 4096)
-
-
-@functools.lru_cache(maxsize=None)
-def duplicated():
-    """heightfield(16) concatenated with itself: (nodes, prims, points, twin) with twin[i] the index of i's equal record"""
-    from tyrant_amd import scenes
-
-    h = scenes.heightfield(16)
-    nodes, prims = build(np.concatenate([h, h]))
-    pts = np.concatenate([grid_points(16), box_points(np.random.default_rng(32), prims, 1024)])
-    raw = np.ascontiguousarray(prims).view(np.uint8).reshape(len(prims), -1)
-    twins = np.lexsort(raw.T[::-1]).reshape(-1, 2)  # equal records are neighbours in the sorted order: pairs
-    assert np.array_equal(raw[twins[:, 0]], raw[twins[:, 1]])
-    twin = np.empty(len(prims), np.int64)
-    twin[twins[:, 0]], twin[twins[:, 1]] = twins[:, 1], twins[:, 0]
-    return nodes, prims, pts, twin
-
-
-def stack40():
-    from tyrant_amd import scenes
-
-    return scenes.make_triangles(np.tile([-30, 0, 10], (40, 1)), np.tile([30, 0, 10], (40, 1)), np.tile([0, 0, 70], (40, 1)))
-
-
 @functools.lru_cache(maxsize=None)
 def soup():
     """random_soup(2000) and 2048 seeded points in its root box (the box itself: with the 10 % pad of box_points three points
@@ -94,30 +37,6 @@ def soup():
     nodes, prims = build(scenes.random_soup(2000))
     lo, hi = root_box(prims, inflate=0.0)
     return nodes, prims, (lo + (hi - lo) * np.random.default_rng(33).random((2048, 3))).astype(F)
-
-
-def offset_soup(slivers):
-    """random_soup(2000) moved by OFFSET; slivers: every tenth triangle's e2 = 0.75 e1 + a perpendicular of 1e-5 |e1|"""
-    from tyrant_amd import scenes
-
-    t = scenes.random_soup(2000)
-    if slivers:
-        e1 = t["e1"][::10].astype(np.float64)
-        perp = np.cross(e1, [0.3, -0.5, 0.8])
-        perp *= 1e-5 * np.linalg.norm(e1, axis=1, keepdims=True) / np.linalg.norm(perp, axis=1, keepdims=True)
-        t["e2"][::10] = (0.75 * e1 + perp).astype(F)
-    t["vert"] = (t["vert"] + OFFSET).astype(F)
-    return build(t)
-
-
-def surface_points(rng, prims, n, noise):
-    """a point of a seeded triangle plus noise"""
-    vert, e1, e2 = ref.records(prims)
-    i = rng.integers(0, len(prims), n)
-    u = rng.random(n)
-    v = rng.random(n) * (1 - u)
-    p = vert[i].astype(np.float64) + u[:, None] * e1[i] + v[:, None] * e2[i]
-    return (p + rng.normal(size=(n, 3)) * noise).astype(F)
 
 
 def prefix(want, k):
@@ -164,7 +83,7 @@ def test_fixtures_reach_what_they_are_for():
     largest k, and a tree that needs more stack than the 12 LDS entries"""
     from tyrant_amd import binding
 
-    nodes, prims, grid, _ = lattice(16)
+    nodes, prims, grid, _ = lattice(16, 31)
     d2, prim, _, _, _, cnt = kref.nearest_k(grid, prims, 9)
     assert (prim >= 0).all()
     eq = d2[:, :-1] == d2[:, 1:]
@@ -179,7 +98,7 @@ def test_fixtures_reach_what_they_are_for():
     cnt8 = kref.nearest_k(pts, prims, 1, np.full(len(pts), 8.0, F))[5]
     print("soup at max_dist 8: count above 4 on", float((cnt8 > 4).mean()), "above 8 on", float((cnt8 > 8).mean()), "none on", float((cnt8 == 0).mean()))
     assert (cnt8 > 4).mean() >= 0.4 and (cnt8 == 0).any() and ((cnt8 > 0) & (cnt8 < 8)).any() and (cnt8 > 8).any()
-    nodes, prims, _, _ = lattice(32)
+    nodes, prims, _, _ = lattice(32, 31)
     assert binding.layout_probe(nodes, prims, want_pairs=False)["quad_max_stack"] > 12
     nodes, prims = build(stack40())
     assert nodes["primitiveCount"].max() == 40  # an over-long leaf: synthetic records
@@ -189,38 +108,15 @@ def test_nearest_k_kernels_keep_registers_and_lds_in_budget():
     """both forms of the kernel within k_query_nearest's budget: no vector spills; scratch no larger than the LdsStack's
     private spill arrays (52 entries of 8 bytes, plus the frame's alignment); occupancy and LDS (24,576 + 7,168 bytes) that admit
     the five blocks per CU the launch bounds plan for"""
-    res = kernel_resources("nearest_k")
-    names = [n for n in res if "k_query_nearest_k" in n]
-    assert len(names) == 2, list(res)
-    for name in names:
-        k = res[name]
-        assert k["VGPRs Spill"] == 0, k
-        assert k["ScratchSize [bytes/lane]"] <= (64 - 12) * 8 + 16, k
-        assert k["Occupancy [waves/SIMD]"] >= 5, k
-        assert k["LDS Size [bytes/block]"] <= 24576 + 7168, k
-        per_block = -(-k["LDS Size [bytes/block]"] // LDS_GRANULE) * LDS_GRANULE
-        assert LDS_PER_CU // per_block >= 5, k
+    assert_kernel_budget("nearest_k", "k_query_nearest_k", 2, (64 - 12) * 8 + 16, 24576 + 7168)
 
 
 def test_abi_declares_and_exports_the_query(hip):
-    hdr = open(os.path.join(ROOT, "include", "tyr_c.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+tyr_query_nearest_k\s*\(", code) and re.search(r"\}\s*tyr_nearest_k_out\s*;", code)
-    assert re.search(r"#define\s+TYR_QUERY_NEAREST_K_MAX\s+32\b", code)
-    assert re.search(r"#define\s+TYR_ABI_VERSION\s+5\b", code)
-    L = hip.lib()
-    assert hasattr(L, "tyr_query_nearest_k") and "tyr_query_nearest_k" in hip.SYMBOLS
-    assert L.tyr_abi_version() == 5
-    assert C.sizeof(hip.NearestKOut) == 6 * C.sizeof(C.c_void_p) and hip.TYR_QUERY_NEAREST_K_MAX == K_MAX
+    assert_query_abi(hip, "tyr_query_nearest_k", "tyr_nearest_k_out", hip.NearestKOut, 6, (r"TYR_QUERY_NEAREST_K_MAX\s+32\b",))
+    assert hip.TYR_QUERY_NEAREST_K_MAX == K_MAX
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
-def renderer(hip, nodes, prims, flags=0):
-    g = hip.Renderer(64, 64, 4096, flags=flags)
-    g.upload(nodes, prims)
-    return g
-
-
 def ask(g, points, k, max_dist=None, count=True, **kw):
     """the five or six outputs as numpy arrays (count as int64)"""
     out = tuple(x.cpu().numpy() for x in g.query_nearest_k(points, k, max_dist, count=count, **kw))
@@ -230,10 +126,7 @@ def ask(g, points, k, max_dist=None, count=True, **kw):
 def same(got, want, what=""):
     """every output of `got` (five, or six with the count) against `want`, bit for bit"""
     assert len(got) in (5, 6)
-    for name, a, b in zip(NAMES, got, want):
-        if a.dtype == np.float32:
-            a, b = bits(a), bits(b)
-        assert a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs at {np.argwhere(a != b)[:5].tolist()} ({np.count_nonzero(a != b)} values)"
+    same_outputs(NAMES, got, want, what)
 
 
 def rows_hold_the_definition(got, points, prims, max_dist, what=""):
@@ -267,7 +160,7 @@ def rows_hold_the_definition(got, points, prims, max_dist, what=""):
 def test_lattice_every_k_with_and_without_count_and_radius(hip):
     """heightfield(32): points above every grid vertex (equally near to several triangles, inside the row and across its cut)
     and seeded points; k = 1, 4, 8, 32, count off and on, unbounded and within 25"""
-    nodes, prims, grid, rand = lattice(32)
+    nodes, prims, grid, rand = lattice(32, 31)
     pts = np.concatenate([grid, rand])
     g = renderer(hip, nodes, prims)
     for md in (None, np.full(len(pts), 25.0, F)):
@@ -292,7 +185,7 @@ def test_exact_ties_resolve_by_index(hip):
     """a scene concatenated with itself: every value occurs twice, so entries come in pairs of equal dist2, the lower copy's
     index first, and at an odd cut the index alone decides; and 40 identical triangles (an over-long leaf behind synthetic
     records): the row is the first 32 of them in order, the count all 40"""
-    nodes, prims, pts, twin = duplicated()
+    nodes, prims, pts, twin = duplicated(32, 1024)
     g = renderer(hip, nodes, prims)
     want = kref.nearest_k(pts, prims, 9)
     for k in (2, 8):
@@ -339,8 +232,6 @@ def test_bounds_hostile_input_and_batch_sizes(hip):
     """max_dist of 0, exactly an entry's distance (strict <: that entry and what follows it are out), +inf, NaN, negative; NaN,
     infinite and 1e30 points; n = 0 .. 4097 and 400,003; every combination of the optional outputs; a scene without triangles"""
     import torch
-
-    from tyrant_amd import scenes
 
     sc, nodes, prims = built_scene("cornell36")
     g = renderer(hip, nodes, prims)
@@ -403,7 +294,7 @@ def test_bounds_hostile_input_and_batch_sizes(hip):
             else:
                 assert (r == 7).all(), (use, name)
     # a scene without triangles: unused entries and no member
-    g.upload(np.zeros(0, dtype=scenes.NODE_DTYPE), np.zeros(0, dtype=scenes.TRIANGLE_DTYPE))
+    g.upload(*no_triangles())
     same(ask(g, pts[:5000], k, md[:5000]), kref.nearest_k(pts[:5000], prims[:0], k, md[:5000]), "empty scene")
     assert g.query_error() == 0
     g.close()
@@ -422,27 +313,11 @@ def test_nearest_k_queries_leave_the_render_alone(hip):
     md = np.full(20000, 30.0, F)
     want = kref.nearest_k(pts, prims, 8, md)
 
-    def run(with_queries):
-        g = binding.Renderer(64, 64, 4096)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            same(ask(g, pts, 8, md), want, "between two renders")
-            ask(g, pts, K_MAX, count=False)
-        g.render(1)
-        out = (g.blit_buffer(), g.counters())
-        g.close()
-        return out
+    def between(g):
+        same(ask(g, pts, 8, md), want, "between two renders")
+        ask(g, pts, K_MAX, count=False)
 
-    b0, k0 = run(False)
-    b1, k1 = run(False)
-    bq, kq = run(True)
-    assert kq == k0, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)):  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0))
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
+    assert_render_undisturbed(between)
 
 
 @pytest.mark.gpu
@@ -459,20 +334,14 @@ def test_refit_side_stream_and_invalid_arguments(hip):
     md = np.full(3000, 12.0, F)
     before = kref.nearest_k(pts, prims, 8, md)
     same(ask(g, pts, 8, md), before, "before the refit")
-    moved = prims.copy()
-    moved["vert"][:, 2] += (4.0 * np.sin(moved["vert"][:, 0] * 0.2)).astype(F)
-    moved["e1"][:, 2] *= F(1.5)
+    moved = deformed(prims, 4.0)
     g.refit(moved)
     after = kref.nearest_k(pts, moved, 8, md)
     same(ask(g, pts, 8, md), after, "after the refit")
     assert not np.array_equal(after[1], before[1]) and not np.array_equal(after[5], before[5])
     # a side stream, device tensors taken in place
     tp, tm = torch.from_numpy(pts).cuda(), torch.from_numpy(md).cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        res = g.query_nearest_k(tp, 8, tm, count=True, stream=side)
-    side.synchronize()
+    res = on_side_stream(lambda side: g.query_nearest_k(tp, 8, tm, count=True, stream=side))
     same(tuple(x.cpu().numpy() for x in res[:5]) + (res[5].cpu().numpy().astype(np.int64),), after, "side stream")
 
     L, h, P = hip.lib(), g.h, C.c_void_p

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from test_winding_query import box
+from query_support import box
 
 F = np.float32
 N = 4

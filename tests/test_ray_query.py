@@ -13,8 +13,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT, bits, built_scene
 from kernel_resources import kernel_resources
-
-LDS_PER_CU, LDS_GRANULE = 163840, 1280
+from query_support import assert_render_undisturbed, check_kernel_budget, on_side_stream, renderer
 
 
 # ---- CPU: resources of the query kernels ------------------------------------------------------------------------------
@@ -25,14 +24,7 @@ def test_query_kernels_keep_registers_and_lds_in_budget():
     spill_entries = 64 - 12
     for kind, with_t, blocks in (("k_query_closest", True, 5), ("k_query_any", False, 7)):
         for sph in (0, 1):
-            names = [n for n in res if f"{kind}ILb{sph}E" in n]
-            assert len(names) == 1, (kind, sph, list(res))
-            k = res[names[0]]
-            assert k["VGPRs Spill"] == 0, k
-            assert k["ScratchSize [bytes/lane]"] <= spill_entries * (8 if with_t else 4) + 16, k
-            assert k["Occupancy [waves/SIMD]"] >= blocks, k
-            per_block = -(-k["LDS Size [bytes/block]"] // LDS_GRANULE) * LDS_GRANULE
-            assert LDS_PER_CU // per_block >= blocks, k
+            check_kernel_budget(res, f"{kind}ILb{sph}E", 1, spill_entries * (8 if with_t else 4) + 16, planned=blocks)
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
@@ -117,17 +109,14 @@ def oracle_spheres_any(orc, spheres, nodes, prims, o, d, tmax):
     return occ
 
 
-def renderer(hip, nodes, prims, spheres=None, n=4096):
+def parked_spheres():
+    """every sphere where no ray can reach it: only the BVH answers"""
     from tyrant_amd import scenes
 
-    g = hip.Renderer(64, 64, n)
-    g.upload(nodes, prims)
-    if spheres is None:  # park every sphere where no ray can reach it: only the BVH answers
-        spheres = scenes.cornell_spheres()
-        spheres["position"] = np.array([0.0, 1e6, -1e6], dtype=np.float32)
-        spheres["radius"] = 1.0
-    g.set_spheres(spheres)
-    return g
+    spheres = scenes.cornell_spheres()
+    spheres["position"] = np.array([0.0, 1e6, -1e6], dtype=np.float32)
+    spheres["radius"] = 1.0
+    return spheres
 
 
 def np_results(res):
@@ -149,7 +138,7 @@ def test_reference_fixtures_closest_and_any(hip):
         z = np.load(os.path.join(GOLDEN, f"ref_traverse_{name}.npz"))
         nodes = np.ascontiguousarray(z["nodes"]).view(scenes.NODE_DTYPE).reshape(-1)
         prims = np.ascontiguousarray(z["prims"]).view(scenes.TRIANGLE_DTYPE).reshape(-1)
-        g = renderer(hip, nodes, prims)
+        g = renderer(hip, nodes, prims, spheres=parked_spheres())
         t, prim, geom, uv = np_results(g.query_closest(z["origin"], z["direction"], z["distance_in"]))
         hit = z["hit"].astype(bool)
         assert np.array_equal(bits(t), bits(z["distance"])), name
@@ -191,7 +180,7 @@ def test_c3_tree_live_against_the_reference(orc, hip):
     rng = np.random.default_rng(7)
     box = (nodes[0]["bounds"][0].astype(np.float32), nodes[0]["bounds"][1].astype(np.float32))
     o, d, tmax = c3_rays(rng, box, sc.camera)
-    g = renderer(hip, nodes, prims)
+    g = renderer(hip, nodes, prims, spheres=parked_spheres())
     t, prim, geom, uv = np_results(g.query_closest(o, d, tmax))
     want_t, want_p = oracle_closest(orc, nodes, prims, o, d, tmax)
     assert (want_p >= 0).sum() > o.shape[0] // 4
@@ -218,7 +207,7 @@ def test_spheres_equal_the_extend_stage_and_intersect_scene(orc, hip):
     n = 4096
     o = np.stack([rng.uniform(-40, 40, n), rng.uniform(-40, 40, n), rng.uniform(5, 80, n)], axis=1).astype(np.float32)
     d = random_dirs(rng, n)
-    g = renderer(hip, nodes, prims, spheres, n)
+    g = renderer(hip, nodes, prims, spheres=spheres, n=n)
     t, prim, geom, uv = np_results(g.query_closest(o, d, spheres=True))
     # the extend stage
     rays = _rays(o, d, np.full(n, 1e20, np.float32))
@@ -279,7 +268,7 @@ def test_hostile_rays_and_batch_sizes(orc, hip):
     where = rng.integers(0, 6, n)
     for i in np.nonzero(bad)[0]:
         (o if where[i] < 3 else d)[i, where[i] % 3] = badval[rng.integers(0, 3)]
-    g = renderer(hip, nodes, prims, n=qsize)
+    g = renderer(hip, nodes, prims, spheres=parked_spheres(), n=qsize)
     t, prim, geom, uv = np_results(g.query_closest(o, d, tmax))
     occ = g.query_any(o, d, tmax).cpu().numpy()
     ok = ~bad
@@ -332,7 +321,7 @@ def test_barycentrics(orc, hip):
     n = 65536
     o = np.stack([rng.uniform(-40, 40, n), rng.uniform(-40, 40, n), rng.uniform(5, 80, n)], axis=1).astype(np.float32)
     d = random_dirs(rng, n)
-    g = renderer(hip, nodes, prims, n=4096)
+    g = renderer(hip, nodes, prims, spheres=parked_spheres())
     t, prim, geom, uv = np_results(g.query_closest(o, d))
     hit = prim >= 0
     assert hit.sum() > n // 2
@@ -347,35 +336,15 @@ def test_barycentrics(orc, hip):
 def test_queries_leave_the_render_alone(hip):
     """a Cornell-box render (64 x 64, 2 spp) with queries between its tyr_render calls: the same accumulation buffer and
     counters as without them"""
-    from tyrant_amd import binding, scenes
-
-    sc = scenes.cornell_box()
-    nodes, prims = binding.bvh_build(sc.triangles)
     rng = np.random.default_rng(1)
     o = np.stack([rng.uniform(-40, 40, 20000), rng.uniform(-40, 40, 20000), rng.uniform(5, 80, 20000)], axis=1).astype(np.float32)
     d = random_dirs(rng, 20000)
 
-    def run(with_queries):
-        g = binding.Renderer(64, 64, 4096)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            g.query_closest(o, d, spheres=True)
-            g.query_any(o, d, np.full(20000, 50.0, np.float32), spheres=True)
-        g.render(1)
-        out = (g.blit_buffer(), g.counters(), g.timings())
-        g.close()
-        return out
+    def between(g):
+        g.query_closest(o, d, spheres=True)
+        g.query_any(o, d, np.full(20000, 50.0, np.float32), spheres=True)
 
-    b0, k0, _ = run(False)
-    b1, k1, _ = run(False)
-    bq, kq, _ = run(True)
-    assert kq == k0, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)):  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0))
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
+    assert_render_undisturbed(between)
 
 
 @pytest.mark.gpu
@@ -391,14 +360,9 @@ def test_side_stream_and_invalid_arguments(orc, hip):
     o = np.stack([rng.uniform(-40, 40, n), rng.uniform(-40, 40, n), rng.uniform(5, 80, n)], axis=1).astype(np.float32)
     d = random_dirs(rng, n)
     tmax = (rng.random(n) * 100).astype(np.float32)
-    g = renderer(hip, nodes, prims)
+    g = renderer(hip, nodes, prims, spheres=parked_spheres())
     to, td, tt = (torch.from_numpy(a).cuda() for a in (o, d, tmax))
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        t, prim, geom, uv = g.query_closest(to, td, tt, stream=side)
-        occ = g.query_any(to, td, tt, stream=side)
-    side.synchronize()
+    (t, prim, geom, uv), occ = on_side_stream(lambda side: (g.query_closest(to, td, tt, stream=side), g.query_any(to, td, tt, stream=side)))
     wt, wp = oracle_closest(orc, nodes, prims, o, d, tmax)
     assert np.array_equal(bits(t.cpu().numpy()), bits(wt)) and np.array_equal(prim.cpu().numpy(), wp)
     assert np.array_equal(occ.cpu().numpy(), oracle_any(orc, nodes, prims, o, d, tmax))

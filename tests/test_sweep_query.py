@@ -18,12 +18,12 @@ import pytest
 
 import sweep_ref as ref
 from conftest import GOLDEN, ROOT, bits, built_scene
-from kernel_resources import kernel_resources
-from test_point_query import OFFSET, box_points, build, duplicated, lattice, offset_soup, stack40, surface_points
+from query_support import (OFFSET, assert_kernel_budget, assert_query_abi, assert_render_undisturbed, box_points, build, deformed, duplicated, lattice, launch_bounds_blocks,
+                           no_triangles, offset_soup, on_side_stream, renderer, stack40, surface_points, tri)
+from query_support import same as same_outputs
 
 F = np.float32
 D = np.float64
-LDS_PER_CU, LDS_GRANULE = 163840, 1280
 C3_ANSWERS = os.path.join(GOLDEN, "sweep_c3.npz")
 NAMES = ("t", "prim", "region", "point", "center", "normal")
 # |t - truth| of the restatement on the committed seeds (test_restatement_against_truth prints it; DESIGN.md "Swept-sphere
@@ -44,7 +44,7 @@ def aimed(rng, prims, n, radii=(0.0, 0.05, 0.5, 4.0)):
 @functools.lru_cache(maxsize=None)
 def lattice_case():
     """heightfield(32): a sphere dropped onto every grid vertex, and seeded sweeps -- (nodes, prims, sweeps, answers)"""
-    nodes, prims, grid, _ = lattice(32)
+    nodes, prims, grid, _ = lattice(32, 21)
     rng = np.random.default_rng(41)
     drop = np.tile(np.array([0, 0, -60], F), (len(grid), 1))
     so, sd, sr = aimed(rng, prims, 448)
@@ -57,7 +57,7 @@ def lattice_case():
 
 @functools.lru_cache(maxsize=None)
 def duplicated_case():
-    nodes, prims, pts = duplicated()
+    nodes, prims, pts, _ = duplicated(22, 2048)
     rng = np.random.default_rng(42)
     n = 640
     o = pts[:n].copy()
@@ -65,15 +65,6 @@ def duplicated_case():
     d = ((target - o) * rng.uniform(0.5, 1.5, (n, 1))).astype(F)
     r = rng.choice(np.array([0.0, 0.3, 3.0], F), n).astype(F)
     return nodes, prims, (o, d, r), ref.sweep(o, d, r, prims)
-
-
-def tri(vert, e1, e2):
-    """one triangle record from vert, e1, e2 as given"""
-    from tyrant_amd import scenes
-
-    t = np.zeros(1, dtype=scenes.TRIANGLE_DTYPE)
-    t["vert"], t["e1"], t["e2"] = np.array(vert, F), np.array(e1, F), np.array(e2, F)
-    return t
 
 
 # ---- CPU: the restatement ---------------------------------------------------------------------------------------------
@@ -313,48 +304,20 @@ def test_sweep_kernel_keeps_registers_and_lds_in_budget():
     """exactly one k_query_sweep; no vector spills; scratch no larger than the LdsStack's private spill arrays (52 entries of 8
     bytes, plus the frame's alignment); LDS (24,576 + 7,168 bytes) that admits the three blocks per CU the launch bounds plan
     for.  The occupancy reached is printed (DESIGN.md "Swept-sphere queries" records it), not prescribed."""
-    res = kernel_resources("sweep")
-    names = [n for n in res if "k_query_sweep" in n]
-    assert len(names) == 1, list(res)
-    k = res[names[0]]
-    print("k_query_sweep:", k)
-    assert k["VGPRs Spill"] == 0, k
-    assert k["ScratchSize [bytes/lane]"] <= (64 - 12) * 8 + 16, k
-    assert k["LDS Size [bytes/block]"] <= 24576 + 7168, k
-    per_block = -(-k["LDS Size [bytes/block]"] // LDS_GRANULE) * LDS_GRANULE
-    src = open(os.path.join(ROOT, "tyrant_amd", "csrc", "hip", "sweep.hip")).read()
-    planned = int(re.search(r"__launch_bounds__\(kBlock, (\d+)\) k_query_sweep", src).group(1))
-    assert LDS_PER_CU // per_block >= planned and k["Occupancy [waves/SIMD]"] >= planned, k
+    assert_kernel_budget("sweep", "k_query_sweep", 1, (64 - 12) * 8 + 16, 24576 + 7168, planned=launch_bounds_blocks("sweep", "k_query_sweep"))
 
 
 def test_abi_declares_and_exports_the_query(hip):
-    hdr = open(os.path.join(ROOT, "include", "tyr_c.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    assert re.search(r"\bint\s+tyr_query_sweep\s*\(", code) and re.search(r"\}\s*tyr_sweep_out\s*;", code)
-    assert re.search(r"#define\s+TYR_ABI_VERSION\s+5\b", code)
-    L = hip.lib()
-    assert hasattr(L, "tyr_query_sweep") and "tyr_query_sweep" in hip.SYMBOLS
-    assert L.tyr_abi_version() == 5
-    assert C.sizeof(hip.SweepOut) == 6 * C.sizeof(C.c_void_p)
+    assert_query_abi(hip, "tyr_query_sweep", "tyr_sweep_out", hip.SweepOut, 6)
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
-def renderer(hip, nodes, prims, flags=0):
-    g = hip.Renderer(64, 64, 4096, flags=flags)
-    g.upload(nodes, prims)
-    return g
-
-
 def ask(g, o, d, r, tmax=None, **kw):
     r = r if np.isscalar(r) else np.array(r)
     return tuple(x.cpu().numpy() for x in g.query_sweep(np.array(o), np.array(d), r, None if tmax is None else np.array(tmax), normal=True, **kw))
 
 
-def same(got, want, what="", names=NAMES):
-    for name, a, b in zip(names, got, want):
-        if a.dtype == np.float32:
-            a, b = bits(a), bits(b)
-        assert a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs at {np.argwhere(a != b)[:5].tolist()} ({np.count_nonzero(a != b)} values)"
+same = functools.partial(same_outputs, NAMES)
 
 
 def check(g, prims, o, d, r, tmax=None, what=""):
@@ -386,15 +349,11 @@ def test_exact_ties_resolve_to_the_lower_index(hip):
     from tyrant_amd import scenes
 
     nodes, prims, (o, d, r), want = duplicated_case()
+    twin = duplicated(22, 2048)[3]
     g = renderer(hip, nodes, prims)
     got = ask(g, o, d, r)
     same(got, want, "duplicated")
     prim = got[1][got[1] >= 0]
-    raw = np.ascontiguousarray(prims).view(np.uint8).reshape(len(prims), -1)
-    twins = np.lexsort(raw.T[::-1]).reshape(-1, 2)  # equal records are neighbours in the sorted order: pairs
-    assert np.array_equal(raw[twins[:, 0]], raw[twins[:, 1]])
-    twin = np.empty(len(prims), np.int64)
-    twin[twins[:, 0]], twin[twins[:, 1]] = twins[:, 1], twins[:, 0]
     assert prim.size >= 200 and (prim < twin[prim]).all()
     for tris in (stack40(), np.concatenate([scenes.cornell_box().triangles, stack40()])):
         nodes, prims = build(tris)
@@ -466,8 +425,6 @@ def test_radii_tmax_hostile_input_and_batch_sizes(hip):
     negative input; n = 0 .. 4097; a scene without triangles; every combination of the optional outputs"""
     import torch
 
-    from tyrant_amd import scenes
-
     sc, nodes, prims = built_scene("cornell36")
     g = renderer(hip, nodes, prims)
     rng = np.random.default_rng(45)
@@ -516,10 +473,10 @@ def test_radii_tmax_hostile_input_and_batch_sizes(hip):
         assert g.query_error() == 0
         res = [x.cpu().numpy() for x in outs]
         used = (True, True) + use
-        same([x for x, u in zip(res, used) if u], [w[:m] for w, u in zip(want, used) if u], f"outputs {use}", [nm for nm, u in zip(NAMES, used) if u])
+        same_outputs([nm for nm, u in zip(NAMES, used) if u], [x for x, u in zip(res, used) if u], [w[:m] for w, u in zip(want, used) if u], f"outputs {use}")
         assert all((x == 7).all() for x, u in zip(res, used) if not u), use
     # a scene without triangles: every valid sweep a miss
-    g.upload(np.zeros(0, dtype=scenes.NODE_DTYPE), np.zeros(0, dtype=scenes.TRIANGLE_DTYPE))
+    g.upload(*no_triangles())
     same(ask(g, o, d, r, tmax), ref.sweep(o, d, r, prims[:0], tmax), "empty scene")
     assert g.query_error() == 0
     g.close()
@@ -540,27 +497,11 @@ def test_sweep_queries_leave_the_render_alone(hip):
     r = rng.uniform(0, 3, n).astype(F)
     want = ref.sweep(o, d, r, prims)
 
-    def run(with_queries):
-        g = binding.Renderer(64, 64, 4096)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            same(ask(g, o, d, r), want, "between two renders")
-            ask(g, o, d, 0.0, np.full(n, 0.5, F))
-        g.render(1)
-        out = (g.blit_buffer(), g.counters())
-        g.close()
-        return out
+    def between(g):
+        same(ask(g, o, d, r), want, "between two renders")
+        ask(g, o, d, 0.0, np.full(n, 0.5, F))
 
-    b0, k0 = run(False)
-    b1, k1 = run(False)
-    bq, kq = run(True)
-    assert kq == k0, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)):  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0))
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
+    assert_render_undisturbed(between)
 
 
 @pytest.mark.gpu
@@ -577,20 +518,14 @@ def test_refit_side_stream_and_invalid_arguments(hip):
     n = 1000
     o, d, r = aimed(rng, prims, n)
     check(g, prims, o, d, r, what="before the refit")
-    moved = prims.copy()
-    moved["vert"][:, 2] += (4.0 * np.sin(moved["vert"][:, 0] * 0.2)).astype(F)
-    moved["e1"][:, 2] *= F(1.5)
+    moved = deformed(prims, 4.0)
     g.refit(moved)
     got, want = check(g, moved, o, d, r, what="after the refit")
     assert not np.array_equal(want[1], ref.sweep(o, d, r, prims)[1])
     # a side stream, device tensors taken in place; then the ctx's own stream (NULL) through the C call
     to, td, tr = (torch.from_numpy(a).cuda() for a in (o, d, r))
     tt = torch.full((n,), 0.5).cuda()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        res = g.query_sweep(to, td, tr, tt, normal=True, stream=side)
-    side.synchronize()
+    res, side = on_side_stream(lambda side: (g.query_sweep(to, td, tr, tt, normal=True, stream=side), side))
     half = ref.sweep(o, d, r, moved, np.full(n, 0.5, F))
     same(tuple(x.cpu().numpy() for x in res), half, "side stream")
     # a number as the radius, device tensors, and a side stream named from outside its context: the radius tensor is filled on

@@ -9,15 +9,15 @@ two streams, hostile input."""
 import ctypes as C
 import functools
 import math
-import os
 import re
 
 import numpy as np
 import pytest
 
 import winding_ref as ref
-from conftest import ROOT, bits
 from kernel_resources import kernel_resources
+from query_support import assert_render_undisturbed, box, build, header_code, query_exists, renderer
+from query_support import same as same_outputs
 
 F = np.float32
 D = np.float64
@@ -31,20 +31,10 @@ ACCURACIES = (0.0, 1.0, 2.0, 3.5, INF)
 SIZES = (1, 63, 64, 65, 257, 2048)
 
 
-@pytest.fixture(autouse=True)
-def _the_query_exists(hip):
-    """nothing here means anything without the entry points: every test of this module needs them"""
-    assert "tyr_query_winding" in hip.SYMBOLS and hasattr(hip.lib(), "tyr_query_winding")
-    assert "tyr_scene_moments" in hip.SYMBOLS and hasattr(hip.lib(), "tyr_scene_moments")
+_the_query_exists = query_exists("tyr_query_winding", "tyr_scene_moments")  # nothing here means anything without the entry points
 
 
 # ---- fixtures (numpy only; made once, never changed) ------------------------------------------------------------------
-def build(tris):
-    from tyrant_amd import binding
-
-    return binding.bvh_build(tris)
-
-
 @functools.lru_cache(maxsize=None)
 def icosphere(level):
     """unit vertices (float64) and outward-wound faces of an icosahedron subdivided `level` times: 20 * 4^level triangles"""
@@ -90,18 +80,6 @@ def torus(nu=48, nv=24, R=20.0, r=7.0, centre=(0.0, 0.0, 30.0)):
     P = np.stack([(R + r * np.cos(v)) * np.cos(u), (R + r * np.cos(v)) * np.sin(u), r * np.sin(v)], axis=-1) + np.asarray(centre, D)
     p00, p10, p11, p01 = (x.reshape(-1, 3) for x in (P[:-1, :-1], P[1:, :-1], P[1:, 1:], P[:-1, 1:]))
     return scenes.make_triangles(np.concatenate([p00, p00]), np.concatenate([p10, p11]), np.concatenate([p11, p01]))  # e1 x e2 along du x dv: outward
-
-
-def box(lo=(-10.0, -10.0, 5.0), hi=(10.0, 10.0, 25.0)):
-    from tyrant_amd import scenes
-
-    c = np.array([[(lo, hi)[(i >> k) & 1][k] for k in range(3)] for i in range(8)], F)
-    v0, v1, v2 = [], [], []
-    for a, b, cc, d in ((0, 2, 3, 1), (4, 5, 7, 6), (0, 1, 5, 4), (2, 6, 7, 3), (0, 4, 6, 2), (1, 3, 7, 5)):  # outward
-        v0 += [c[a], c[a]]
-        v1 += [c[b], c[cc]]
-        v2 += [c[cc], c[d]]
-    return scenes.make_triangles(np.array(v0), np.array(v1), np.array(v2))
 
 
 def one_triangle():
@@ -316,8 +294,7 @@ def test_winding_kernels_need_no_scratch():
 
 
 def test_abi_declares_exports_and_refuses(hip):
-    hdr = open(os.path.join(ROOT, "include", "tyr_c.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    code = header_code()
     assert re.search(r"\bint\s+tyr_query_winding\s*\(", code) and re.search(r"\bint\s+tyr_scene_moments\s*\(", code)
     assert re.search(r"#define\s+TYR_FLAG_WINDING\s+128u", code) and re.search(r"#define\s+TYR_ABI_VERSION\s+5\b", code)
     L = hip.lib()
@@ -330,14 +307,6 @@ def test_abi_declares_exports_and_refuses(hip):
 
 
 # ---- GPU helpers ------------------------------------------------------------------------------------------------------
-def renderer(hip, nodes, prims, flags=WINDING, **tuning):
-    g = hip.Renderer(64, 64, 4096, flags=flags)
-    if tuning:
-        g.set_tuning(**tuning)
-    g.upload(nodes, prims)
-    return g
-
-
 def ask(g, pts, accuracy, terms=True, **kw):
     """query_winding's answer as numpy arrays, terms as the library's uint32 (the fixtures' arrays are read-only: torch wants its own)"""
     res = g.query_winding(np.array(pts), accuracy=accuracy, terms=terms, **kw)
@@ -346,12 +315,7 @@ def ask(g, pts, accuracy, terms=True, **kw):
     return res[0].cpu().numpy(), res[1].cpu().numpy().view(U)
 
 
-def same(got, want, what=""):
-    for name, a, b in zip(("w", "terms"), got, want):
-        if a is None:
-            continue
-        a, b = (bits(a), bits(b)) if a.dtype == np.float32 else (a, b)
-        assert a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b), f"{what}: {name} differs at {np.argwhere(a != b)[:5].tolist()} ({np.count_nonzero(a != b)} values)"
+same = functools.partial(same_outputs, ("w", "terms"))  # (terms not asked for: None, and not compared)
 
 
 def same_moments(got, tree, what=""):
@@ -369,7 +333,7 @@ def test_moments_bit_for_bit_through_every_upload_path(hip, name):
     host and on the device, and tyr_scene_build_upload, whose tree is the device builder's"""
     nodes, prims, tree, _ = fixture(name)
     for lod in (0, 1):
-        g = renderer(hip, nodes, prims, layout_on_device=lod)
+        g = renderer(hip, nodes, prims, flags=WINDING, layout_on_device=lod)
         same_moments(g.scene_moments(), tree, f"{name}, layout_on_device {lod}")
         last = nodes.shape[0] - 1
         assert np.array_equal(g.scene_moments(last, 1).view(np.uint64), tree.moments()[last:].view(np.uint64))  # a range of its own
@@ -386,7 +350,7 @@ def test_bit_for_bit_against_the_restatement(hip, name):
     """w and terms by bits at accuracy 0, 1, 2, 3.5 and inf, on batches of 1, 63, 64, 65, 257, 2048 points and on the whole set
     with its hand-placed points (a vertex, an edge, a face's plane, two nodes' centres)"""
     nodes, prims, tree, pts = fixture(name)
-    g = renderer(hip, nodes, prims)
+    g = renderer(hip, nodes, prims, flags=WINDING)
     for acc, limit in cases(name):
         want = reference(name, acc, limit)
         total = want[0].shape[0]
@@ -419,7 +383,7 @@ def test_independence(hip):
     """the first m points of a batch give what a batch of m gives; terms_out NULL changes nothing; a permuted batch gives the
     permuted answers; two runs are identical"""
     nodes, prims, tree, pts = fixture("torus")
-    g = renderer(hip, nodes, prims)
+    g = renderer(hip, nodes, prims, flags=WINDING)
     big = ask(g, pts, 2.0)
     same(big, reference("torus", 2.0), "the whole batch")
     for m in (1, 100, 1000):
@@ -464,37 +428,21 @@ def test_refit_rebuilds_the_moments(hip):
 def test_winding_queries_leave_the_render_alone(hip):
     """a Cornell-box render (64 x 64) with winding queries between its two halves: the same accumulation buffer, counters, queues
     and scene hash as the uninterrupted render's, and as a ctx without the flag"""
-    from tyrant_amd import binding, scenes
+    from tyrant_amd import scenes
 
-    sc = scenes.cornell_box()
-    nodes, prims = build(sc.triangles)
-    tree = ref.Tree(nodes, prims)
+    tree = ref.Tree(*build(scenes.cornell_box().triangles))
     pts = fixture("box")[3]
     want = ref.winding(tree, pts[:512], 2.0)
 
-    def run(flags, with_queries):
-        g = binding.Renderer(64, 64, 4096, flags=flags)
-        g.load_scene(sc, nodes, prims)
-        g.render(1)
-        if with_queries:
-            same(ask(g, pts[:512], 2.0), want, "between two renders")
-            ask(g, pts, INF, terms=False)
-        g.render(1)
-        out = (g.blit_buffer(), g.counters(), g.ray_queue(0, 4096).tobytes(), g.shadow_queue(4096).tobytes(), g.scene_hash())
-        g.close()
-        return out
+    def between(g):
+        same(ask(g, pts[:512], 2.0), want, "between two renders")
+        ask(g, pts, INF, terms=False)
 
-    b0, k0, q0, s0, h0 = run(0, False)
-    b1, k1, q1, s1, h1 = run(WINDING, False)
-    bq, kq, qq, sq, hq = run(WINDING, True)
-    assert kq == k0 == k1, {k: (k0[k], kq[k]) for k in k0 if k0[k] != kq[k]}
+    # the first run on a ctx without the flag, the other two with it
+    (_, k0, _, _, h0), (_, k1, _, _, h1), (_, kq, _, _, hq) = assert_render_undisturbed(between, flags=(0, WINDING, WINDING), also=lambda g: g.scene_hash())
+    assert kq == k0 == k1, {k: (k0[k], k1[k]) for k in k0 if k0[k] != k1[k]}
     drop = lambda h: {k: v for k, v in h.items() if k != "seconds"}  # noqa: E731
     assert drop(hq) == drop(h0) == drop(h1)
-    assert np.array_equal(bq[:, 3], b0[:, 3])
-    if np.array_equal(bits(b0), bits(b1)) and q0 == q1 and s0 == s1:  # the render is bit-reproducible: so must it be with queries in between
-        assert np.array_equal(bits(bq), bits(b0)) and qq == q0 and sq == s0
-    else:
-        assert np.allclose(bq, b0, rtol=1e-5, atol=1e-6)
 
 
 @pytest.mark.gpu
@@ -532,7 +480,7 @@ def test_two_streams_and_invalid_arguments(hip):
     import torch
 
     nodes, prims, tree, pts = fixture("nested")
-    g = renderer(hip, nodes, prims)
+    g = renderer(hip, nodes, prims, flags=WINDING)
     tp = torch.from_numpy(np.array(pts)).cuda()
     s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
     for s in (s1, s2):
@@ -578,7 +526,7 @@ def test_two_streams_and_invalid_arguments(hip):
 def test_hostile_input(hip):
     """NaN and infinite points, a point 1e30 away, accuracy 1e-30 and 1e30, and the scene without triangles -- against the restatement"""
     nodes, prims, tree, pts = fixture("soup")
-    g = renderer(hip, nodes, prims)
+    g = renderer(hip, nodes, prims, flags=WINDING)
     p = np.array(pts[:512])
     rng = np.random.default_rng(9)
     kind = rng.integers(0, 6, p.shape[0])
