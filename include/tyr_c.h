@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_query_winding, tyr_scene_moments, TYR_FLAG_WINDING and tyr_vecmath_probe ops 50-52; tyr_query_sweep and tyr_sweep_out; tyr_query_box, tyr_box_out, TYR_QUERY_BOX_ANY and TYR_QUERY_BOX_MAX; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
+#define TYR_ABI_VERSION 5 /* 2: tyr_counters grows (rays_in_tree_*, debug[16]), tyr_dist_*, per-triangle colours; 3: retired tuning keys removed, tyr_sunsky_probe / tyr_sun_setup; 4: tyr_set_frame, tyr_layout_probe, tyr_bvh_build_device, tyr_scene_build_upload, tyr_scene_hash, tyr_scene_info grows (upload_*_s, layout_on_device); 5: the streamed tail's tuning keys (16, 17, 18) retired with its kernels; additive within 5: tyr_query_closest, tyr_query_any, tyr_query_error and TYR_QUERY_SPHERES; tyr_scene_refit, TYR_FLAG_REFIT and TYR_REFIT_DEVICE; tyr_render_aov and tyr_aov_out; tyr_denoise, tyr_denoise_in, tyr_denoise_params and TYR_DENOISE_RESOLVE; tyr_render_motion, tyr_motion_in, tyr_motion_out, tyr_temporal, tyr_temporal_in, tyr_temporal_params and TYR_TEMPORAL_RESET; tyr_svgf, tyr_svgf_in, tyr_svgf_params, TYR_SVGF_RESET and TYR_SVGF_RESOLVE; tyr_set_sample_map, tyr_render_adaptive, tyr_allocate_samples and tyr_allocate_params; tyr_taa, tyr_taa_in, tyr_taa_params, TYR_TAA_RESET and TYR_TAA_BILINEAR; tyr_render_aov_chain, tyr_aov_chain_out, TYR_AOV_CHAIN_MAX, tyr_render_motion_chain and tyr_motion_chain_in; tyr_query_nearest and tyr_nearest_out; tyr_query_hits, tyr_hits_out, TYR_QUERY_TWO_SIDED and TYR_QUERY_HITS_MAX; tyr_query_nearest_k, tyr_nearest_k_out and TYR_QUERY_NEAREST_K_MAX; tyr_query_occlusion, tyr_occlusion_out and TYR_QUERY_OCCLUSION_MAX_SAMPLES; tyr_query_winding, tyr_scene_moments, TYR_FLAG_WINDING and tyr_vecmath_probe ops 50-52; tyr_query_sweep and tyr_sweep_out; tyr_query_box, tyr_box_out, TYR_QUERY_BOX_ANY and TYR_QUERY_BOX_MAX; tyr_query_tri, tyr_tri_out, TYR_QUERY_TRI_ANY, TYR_QUERY_TRI_SKIP_SHARED and TYR_QUERY_TRI_MAX; tyr_primary_window, tyr_primary_window_probe, tyr_primary_window_info and the tuning keys 28-31 */
 
 /* ---- record layouts (identical to the reference structs) ------------------ */
 
@@ -950,6 +950,80 @@ typedef struct tyr_box_out {
 } tyr_box_out;
 int tyr_query_box(tyr_ctx* ctx, uint32_t n, const float* lo /* n x 3 */, const float* hi /* n x 3 */,
                   uint32_t max_prims, uint32_t flags, const tyr_box_out* out, void* stream);
+
+/* ---- triangle-overlap queries (extension) ---------------------------------------------------------------------------------
+ * "Which triangles of the uploaded mesh does this triangle touch?" for a caller's batch of triangles (corners a, b, c), against
+ * the scene the ctx holds: the narrowphase of mesh against mesh, cloth or tet-surface triangles against an obstacle,
+ * self-intersection checks (TYR_QUERY_TRI_SKIP_SHARED), the cut set before a boolean or a remesh.  The contract is a set over
+ * all triangles of the uploaded array with no traversal order in it.
+ *
+ * Arithmetic, dot, cross, vector -, min and max are the "Box-overlap queries" block's: binary64, one IEEE operation per operation
+ * written, nothing contracted; inputs are binary32 widened exactly.  For finite corners no operand overflows or becomes NaN
+ * (the largest intermediate is below 1e156).
+ *
+ * Corners.  P0, P1, P2 are the query's binary32 corners a, b, c.  Q0 = vert, Q1 = the BINARY32 sum vert + e1, Q2 = the binary32
+ * sum vert + e2: exactly the corners tyr_triangle_bboxes bounds, as in the two blocks above.  A query is valid when all nine
+ * components are finite; a triangle of zero area (a segment, a point) is valid.
+ *
+ * Member test of a (query, scene triangle) pair.  Both sets are closed, so touching counts.  In this order:
+ *  0. With TYR_QUERY_TRI_SKIP_SHARED only: if some Pi equals some Qj as binary32 values on all three components (==, so -0
+ *     equals +0), the pair is NOT a member.
+ *  1. The coordinate axes k = x, y, z, in binary32: separated when min(P0_k, P1_k, P2_k) > max(Q0_k, Q1_k, Q2_k) or
+ *     max(P0_k, P1_k, P2_k) < min(Q0_k, Q1_k, Q2_k) -- exact comparisons of the inputs.
+ *  2. Seventeen axes in binary64.  All six corners widened, relative to Q0: p_i = P_i - Q0, q_j = Q_j - Q0.  Edges, cyclic:
+ *     e0 = p1 - p0, e1 = p2 - p1, e2 = p0 - p2; f0 = q1 - q0, f1 = q2 - q1, f2 = q0 - q2.  Normals: n = cross(e0, p2 - p0),
+ *     m = cross(f0, q2 - q0).  The axes, in order: m; n; cross(e_i, f_j) for i = 0, 1, 2 (outer) and j = 0, 1, 2 (inner);
+ *     cross(n, e_i) for i = 0, 1, 2; cross(m, f_j) for j = 0, 1, 2.  On each axis a ALL SIX points are projected by the same
+ *     expression dot(a, x) -- nothing is assumed to be zero -- and the pair is separated when
+ *         max(dot(a, p0), dot(a, p1), dot(a, p2)) < min(dot(a, q0), dot(a, q1), dot(a, q2))   or
+ *         max(dot(a, q0), dot(a, q1), dot(a, q2)) < min(dot(a, p0), dot(a, p1), dot(a, p2)),   strictly.
+ *  The pair is a member when no rule applies.  An implementation may test the axes in any order and leave out a term where the
+ *  comparisons provably come out the same (dot(a, q0) is a zero); only membership is observable.
+ *
+ * Why seventeen.  The two normals and the nine edge crosses decide triangles in general position; for COPLANAR triangles every
+ * edge cross is parallel to the common normal and separates nothing, so disjoint coplanar pairs would all be members.  The six
+ * in-plane axes cross(n, e_i), cross(m, f_j) are the edge normals of the 2D test and separate them.
+ * Shared corners.  Because both triangles go through one expression, a corner the two share bit for bit projects to the same
+ * number on every axis, and no strict inequality can hold: pairs that share a corner or an edge are ALWAYS members without
+ * TYR_QUERY_TRI_SKIP_SHARED, independent of rounding, and never with it.  Meshes that share vertices rely on this.
+ * Zero area.  The test is conservative for a triangle of zero area (either one): its normal is 0, the axes made from it separate
+ * nothing, and a few coplanar disjoint pairs are reported as members; a contact is never missed.  A segment's exact answer is
+ * tyr_query_hits.
+ * Against the same rules in exact integer arithmetic on the same binary32 inputs the binary64 test gives the same answer on every
+ * pair of the test families (DESIGN.md "Triangle-overlap queries").
+ *
+ * Answer per query, W = { i : (query, triangle i) is a member } over all triangles of the uploaded array (after a refit: the new
+ * records).  Without TYR_QUERY_TRI_ANY: count = |W|, NOT capped by max_prims; the min(max_prims, |W|) lowest build-order indices
+ * of W go into the query's row, ascending, unused entries -1; max_prims == 0 is allowed and out->prim is then ignored: a count
+ * alone.  With TYR_QUERY_TRI_ANY: max_prims must be 0, count = W is empty ? 0 : 1, and the walk may stop at the first member.
+ * An invalid query (a NaN or infinite component): count = 0 and a row of -1; a scene without triangles answers every query that
+ * way.  Hence the row for k is the first k entries of the row for any larger k, ANY equals count > 0, and a query answers the
+ * same whatever else is in the batch.
+ *
+ * Pruning is exact and needs no slack.  A node's stored binary32 box contains the corners Q0, Q1, Q2 of every triangle below it,
+ * so a node whose box fails the closed interval test against the query's binary32 bounding box on some axis holds only triangles
+ * that rule 1 separates on that axis, and it holds no member.  Scope of this guarantee: tyr_query_box's.
+ *
+ * Arrays, streams and state follow tyr_query_box: every array pointer is a DEVICE pointer, contiguous, float32 / int32 /
+ * uint32, indexed with 64-bit offsets -- a, b, c n x 3.  While the call runs, a query's row of out->prim is its working buffer.
+ * n up to 2^31 - 1, independent of queue_size; n == 0: TYR_OK and nothing launched.  The work is enqueued on `stream` (NULL: the
+ * ctx's stream); the call uses the ctx's device, restores the caller's and touches no render state.  A later tyr_scene_refit
+ * waits for it, a query issued after a refit sees the refitted scene, and a traversal stack overflow sets bit 1 of
+ * tyr_query_error.
+ * TYR_ERR_INVALID: ctx, a, b, c, out or out->count NULL, out->prim NULL with max_prims > 0, n >= 2^31, max_prims above
+ * TYR_QUERY_TRI_MAX, a flag other than TYR_QUERY_TRI_ANY and TYR_QUERY_TRI_SKIP_SHARED, or TYR_QUERY_TRI_ANY with
+ * max_prims != 0; TYR_ERR_NO_SCENE: nothing uploaded.
+ * Not part of it: the sphere table, the intersection segment of a pair, moving triangles (a moving sphere: tyr_query_sweep),
+ * more than TYR_QUERY_TRI_MAX indices per query, an exact answer for triangles of zero area. */
+#define TYR_QUERY_TRI_ANY 4u          /* tyr_query_tri only: count is 0 or 1, max_prims must be 0, the walk may stop at the first member */
+#define TYR_QUERY_TRI_SKIP_SHARED 8u  /* tyr_query_tri only: a scene triangle with a corner equal to a corner of the query is no member */
+#define TYR_QUERY_TRI_MAX 32
+typedef struct tyr_tri_out {
+	uint32_t* count;   /* n, required */
+	int32_t*  prim;    /* n x max_prims, required when max_prims > 0; build-order index, -1 = unused entry */
+} tyr_tri_out;
+int tyr_query_tri(tyr_ctx* ctx, uint32_t n, const float* a /* n x 3 */, const float* b /* n x 3 */, const float* c /* n x 3 */,
+                  uint32_t max_prims, uint32_t flags, const tyr_tri_out* out, void* stream);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

@@ -34,6 +34,9 @@ TYR_QUERY_TWO_SIDED = 2  # tyr_query_hits only
 TYR_QUERY_HITS_MAX = 32
 TYR_QUERY_BOX_ANY = 4  # tyr_query_box only
 TYR_QUERY_BOX_MAX = 32
+TYR_QUERY_TRI_ANY = 4  # tyr_query_tri only
+TYR_QUERY_TRI_SKIP_SHARED = 8  # tyr_query_tri only
+TYR_QUERY_TRI_MAX = 32
 TYR_QUERY_NEAREST_K_MAX = 32
 TYR_QUERY_OCCLUSION_MAX_SAMPLES = 1024
 AOV_CHAIN_MAX = 8  # TYR_AOV_CHAIN_MAX
@@ -149,6 +152,12 @@ class SweepOut(C.Structure):
 
 class BoxOut(C.Structure):
     """tyr_box_out: device pointers of tyr_query_box's outputs; prim may be NULL when max_prims is 0"""
+
+    _fields_ = [("count", P), ("prim", P)]
+
+
+class TriOut(C.Structure):
+    """tyr_tri_out: device pointers of tyr_query_tri's outputs; prim may be NULL when max_prims is 0"""
 
     _fields_ = [("count", P), ("prim", P)]
 
@@ -314,6 +323,7 @@ SYMBOLS = {
     "tyr_query_nearest_k": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_sweep": (C.c_int, [P, c_u32, P, P, P, P, c_u32, P, P]),
     "tyr_query_box": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
+    "tyr_query_tri": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
     "tyr_query_winding": (C.c_int, [P, c_u32, P, C.c_float, P, P, P]),
@@ -807,6 +817,33 @@ class Renderer:
         cnt, prim = self._query_outputs(n, ((), torch.int32), ((k,), torch.int32) if k else None)
         out = BoxOut(*_dptrs(cnt, prim))
         self._query_call("tyr_query_box", stream, staged, n, *_dptrs(*ins), k, TYR_QUERY_BOX_ANY if any else 0, C.byref(out))
+        if any:
+            with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+                return cnt != 0
+        return (cnt, prim) if k else cnt
+
+    def query_tri(self, a, b, c, max_prims=0, any=False, skip_shared=False, stream=None):
+        """tyr_query_tri: for every triangle with the corners a, b, c the triangles of the uploaded scene it touches (include/tyr_c.h
+        "Triangle-overlap queries"; touching counts).  a, b, c: (N, 3) float32 -- torch tensors on this ctx's device, taken as they
+        are, or numpy arrays.  Returns what query_box returns: count, (N,) int32 (the library's uint32), not capped by max_prims;
+        with max_prims > 0 (count, prim), prim (N, max_prims) int32 the lowest build-order indices of them, ascending, unused
+        entries -1; with any=True (max_prims must be 0) a bool tensor, count > 0, from a walk that stops at the first triangle.
+        skip_shared=True: a scene triangle with a corner equal to one of the query's is not reported (self-intersection checks
+        with the mesh's own triangles).  A query with a NaN or infinite component touches nothing."""
+        import contextlib
+
+        import torch
+
+        k = int(max_prims)
+        if not 0 <= k <= TYR_QUERY_TRI_MAX:
+            raise ValueError(f"max_prims: 0 .. {TYR_QUERY_TRI_MAX}")
+        if any and k:
+            raise ValueError("any=True answers without indices: max_prims must be 0")
+        n, ins, staged = self._query_inputs(("a", a, (3,)), ("b", b, (3,)), ("c", c, (3,)))
+        cnt, prim = self._query_outputs(n, ((), torch.int32), ((k,), torch.int32) if k else None)
+        out = TriOut(*_dptrs(cnt, prim))
+        flags = (TYR_QUERY_TRI_ANY if any else 0) | (TYR_QUERY_TRI_SKIP_SHARED if skip_shared else 0)
+        self._query_call("tyr_query_tri", stream, staged, n, *_dptrs(*ins), k, flags, C.byref(out))
         if any:
             with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
                 return cnt != 0
