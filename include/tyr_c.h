@@ -873,7 +873,7 @@ int tyr_scene_moments(tyr_ctx* ctx, int32_t first, int32_t count, double* host_o
  * out->normal n x 3 (each may be NULL).
  * TYR_ERR_INVALID: ctx, origins, directions, radius, out, out->t or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE:
  * nothing uploaded.
- * Not part of it: the sphere table (flags must be 0), capsules and moving boxes (a box at rest: tyr_query_box), all contacts rather than the first, rotating or
+ * Not part of it: the sphere table (flags must be 0), moving capsules and moving boxes (a capsule at rest: tyr_query_segment; a box at rest: tyr_query_box), all contacts rather than the first, rotating or
  * deforming bodies, triangles that move during the sweep, penetration depth beyond what `normal` carries. */
 typedef struct tyr_sweep_out {
 	float*   t;       /* n, required */
@@ -1024,6 +1024,80 @@ typedef struct tyr_tri_out {
 } tyr_tri_out;
 int tyr_query_tri(tyr_ctx* ctx, uint32_t n, const float* a /* n x 3 */, const float* b /* n x 3 */, const float* c /* n x 3 */,
                   uint32_t max_prims, uint32_t flags, const tyr_tri_out* out, void* stream);
+
+/* ---- closest-segment queries (extension) -----------------------------------------------------------------------------------
+ * "How near does this segment come to the mesh, where, and to which triangle?" for a caller's batch of segments p -> q, against
+ * the scene the ctx holds: a capsule at rest is everything within r of a segment (max_dist = r: prim >= 0 means contact), and
+ * the clearance of a strut or a path piece is this distance.  Samples along the segment given to tyr_query_nearest miss what
+ * lies between them, tyr_query_closest along it reports only a crossing, tyr_query_sweep answers when a moving sphere touches.
+ * The contract is an argmin over all triangles of the uploaded array with no traversal order in it.
+ *
+ * All arithmetic is binary64, one IEEE operation per operation written, nothing contracted, divisions correctly rounded; dot and
+ * cross are the "Winding numbers" block's; vector - is componentwise.  Inputs (triangle records, p, q) are binary32 widened
+ * exactly.  A comparison with a NaN is false.
+ *
+ * Triangle corners: the "Swept-sphere queries" block's -- A = vert, B = the BINARY32 sum vert + e1, C = the binary32 sum
+ * vert + e2, all widened; e1' = B - A, e2' = C - A.  The stored boxes then contain the defined triangle with no rounding term.
+ * Segment: P0 = p, P1 = q, d = P1 - P0; p == q is allowed.  A point of it is x(s)_k = P0_k + s*d_k for s in [0, 1].
+ *
+ * Value of a (segment, triangle) pair.  Six candidates are offered in the order of their feature codes; a candidate replaces the
+ * one held only when its F is strictly smaller (the first one offered is held), so of equal F the lower feature code stays.  Each
+ * gives F, the squared distance, s, x = x(s) and y, a point of the triangle, and a region numbered as tyr_query_nearest's.
+ *   feature 0, the segment crosses the triangle:
+ *     n = cross(e1', e2'),  nn = dot(n, n),  h0 = dot(n, P0 - A),  h1 = dot(n, P1 - A)
+ *     conditions: nn > 0, h0 != h1, and (h0 <= 0 and h1 >= 0) or (h0 >= 0 and h1 <= 0)
+ *     s = h0 / (h0 - h1),  x = x(s),  w = x - A,  bv = dot(cross(w, e2'), n),  bw = dot(cross(e1', w), n)
+ *     conditions: bv >= 0, bw >= 0, bv + bw <= nn;   F = 0, y = x, region 0
+ *   features 1 and 2, the endpoints P0 (s = 0) and P1 (s = 1):
+ *     the "Closest-point queries" block's rules, clamp, q and c in binary64 with vert, e1, e2 := A, e1', e2' and p := the endpoint,
+ *     as rule 1 of the "Swept-sphere queries" block does it;   F = dot(q, q), x = x(s), y = c, region = that block's region
+ *   features 3, 4 and 5, the edges Q0 -> Q1 = A -> B, A -> C, B -> C (Ericson, Real-Time Collision Detection 5.1.9, with exact
+ *   tests against zero where the book has an epsilon):
+ *     e = Q1 - Q0,  r = P0 - Q0,  a = dot(d, d),  ee = dot(e, e),  f = dot(e, r),  c = dot(d, r),  b = dot(d, e),
+ *     den = a*ee - b*b;   clamp01(v): v1 = v > 0 ? v : 0, then v1 < 1 ? v1 : 1 (a NaN becomes 0)
+ *     a == 0 and ee == 0:  s = t = 0
+ *     a == 0:              s = 0,  t = clamp01(f / ee)
+ *     ee == 0:             t = 0,  s = clamp01(-c / a)
+ *     otherwise:           s = den > 0 ? clamp01((b*f - c*ee) / den) : 0,  tn = b*s + f
+ *                          tn < 0:   t = 0,  s = clamp01(-c / a)
+ *                          tn > ee:  t = 1,  s = clamp01((b - c) / a)
+ *                          else:     t = tn / ee
+ *     x = x(s),  y_k = Q0_k + e_k*t,  F = dot(x - y, x - y);   region 4 / 5 / 6 (the edge) when 0 < t < 1, otherwise the vertex
+ *     code (1, 2, 3 = A, B, C) of that end: Q1's when t >= 1, else Q0's
+ * The least distance between a segment and a triangle that do not cross is attained at an endpoint of the segment or on an edge
+ * of the triangle, so the least of the six is the distance.  A triangle of zero area needs no special case: nn == 0 rules out
+ * feature 0 and the other five measure the segment or the point it is (the zero triangle: its one point, region 1).  p == q is
+ * the point's distance by the BINARY64 rules above, not tyr_query_nearest's binary32 value: the two can differ in the last bits
+ * and, among near-equal triangles, in prim.  On the test families sqrt(F) is within 2e-12 units of a binary64 truth (ternary
+ * search on the point distance along the segment; DESIGN.md "Closest-segment queries" has the table).
+ *
+ * Answer per segment: F32_i = (float)F_i.  bound2 = max_dist * max_dist in binary32 (one multiplication), +inf when max_dist is
+ * NULL -- tyr_query_nearest's rule.  Over all triangles i of the uploaded array the winner is the smallest pair (F32_i, i) in
+ * lexicographic order among those with F32_i < bound2 (strictly): of bit-equal values the lowest build-order index wins.
+ *   a winner:  dist2 = F32, prim = i, s, feature, region, on_segment = x, on_triangle = y, each rounded to binary32 once
+ *   none:      dist2 = bound2, prim = -1, s = 0, feature = region = 0, on_segment = on_triangle = p as given
+ *   invalid:   dist2 = +inf, otherwise as "none".  A segment is invalid when p or q has a NaN or infinite component, or when its
+ *              max_dist is NaN or negative.
+ * A scene without triangles answers every valid segment with "none".
+ *
+ * Scope of the guarantee, arrays (DEVICE pointers, contiguous, float32 / int32 / uint8, indexed with 64-bit offsets), n up to
+ * 2^31 - 1 and n == 0, streams, the device, "touches no render state", tyr_scene_refit and bit 1 of tyr_query_error are
+ * tyr_query_nearest's: p, q n x 3; max_dist n or NULL; out->dist2, out->prim n (required); out->s, out->feature, out->region n,
+ * out->on_segment, out->on_triangle n x 3 (each may be NULL).
+ * TYR_ERR_INVALID: ctx, p, q, out, out->dist2 or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
+ * Not part of it: the sphere table (flags must be 0), an any-only mode, the k nearest, moving capsules (a moving sphere:
+ * tyr_query_sweep), signed distance. */
+typedef struct tyr_segment_out {
+	float*   dist2;       /* n, required */
+	int32_t* prim;        /* n, required: build-order index, -1 = none */
+	float*   s;           /* n or NULL: the parameter on the segment, 0 at p and 1 at q */
+	uint8_t* feature;     /* n or NULL: 0 crossing, 1 2 the endpoints p q, 3 4 5 the edges A -> B, A -> C, B -> C */
+	uint8_t* region;      /* n or NULL: of on_triangle -- 0 face, 1 2 3 vertices, 4 5 6 edges, numbered as tyr_query_nearest's */
+	float*   on_segment;  /* n x 3 or NULL */
+	float*   on_triangle; /* n x 3 or NULL */
+} tyr_segment_out;
+int tyr_query_segment(tyr_ctx* ctx, uint32_t n, const float* p /* n x 3 */, const float* q /* n x 3 */, const float* max_dist /* n or NULL */,
+                      uint32_t flags /* must be 0 */, const tyr_segment_out* out, void* stream);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

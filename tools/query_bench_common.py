@@ -1,7 +1,7 @@
-"""What the query benchmarks (tools/{query,nearest,nearest_k,hits,occlusion,sweep,winding,box,tri}_bench.py) share: the summary
-of a launch's samples, the seeded point batches on C3's scene, a camera-like ray grid, the Morton order of a batch and the loop
-that times the launches in turn.  tools/sweep_c3_golden.py, tools/box_c3_golden.py and tools/tri_c3_golden.py take their starting
-points from here too, so nothing at module level needs a GPU or torch."""
+"""What the query benchmarks (tools/{query,nearest,nearest_k,hits,occlusion,sweep,winding,box,tri,segment}_bench.py) share: the
+summary of a launch's samples, the seeded point batches on C3's scene, a camera-like ray grid, the Morton order of a batch and the
+loop that times the launches in turn.  tools/sweep_c3_golden.py, tools/box_c3_golden.py, tools/tri_c3_golden.py and
+tools/segment_c3_golden.py take their starting points from here too, so nothing at module level needs a GPU or torch."""
 from __future__ import annotations
 
 import numpy as np

@@ -162,6 +162,12 @@ class TriOut(C.Structure):
     _fields_ = [("count", P), ("prim", P)]
 
 
+class SegmentOut(C.Structure):
+    """tyr_segment_out: device pointers of tyr_query_segment's outputs; s, feature, region, on_segment, on_triangle may be NULL"""
+
+    _fields_ = [("dist2", P), ("prim", P), ("s", P), ("feature", P), ("region", P), ("on_segment", P), ("on_triangle", P)]
+
+
 class HitsOut(C.Structure):
     """tyr_hits_out: device pointers of tyr_query_hits's outputs; uv, side, back_count may be NULL"""
 
@@ -324,6 +330,7 @@ SYMBOLS = {
     "tyr_query_sweep": (C.c_int, [P, c_u32, P, P, P, P, c_u32, P, P]),
     "tyr_query_box": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_tri": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
+    "tyr_query_segment": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
     "tyr_query_winding": (C.c_int, [P, c_u32, P, C.c_float, P, P, P]),
@@ -796,6 +803,26 @@ class Renderer:
         out = SweepOut(*_dptrs(*outs))
         self._query_call("tyr_query_sweep", stream, staged, n, *_dptrs(o, d, r, tm), 0, C.byref(out))
         return tuple(outs) if normal else tuple(outs[:5])
+
+    def query_segment(self, p, q, max_dist=None, stream=None):
+        """tyr_query_segment: for every segment p -> q the triangle of the uploaded scene that comes nearest to it (include/tyr_c.h
+        "Closest-segment queries").  p, q: (N, 3) float32, max_dist: a number, (N,) or None -- torch tensors on this ctx's device,
+        taken as they are, or numpy arrays.  Returns torch tensors (dist2, prim, s, feature, region, on_segment, on_triangle):
+        without a triangle nearer than max_dist, dist2 = max_dist^2 (+inf for an invalid segment or max_dist), prim = -1, s = 0,
+        feature = region = 0 and both points = p.  A capsule of radius r at rest touches the scene where prim >= 0 with max_dist = r."""
+        import torch
+
+        if isinstance(max_dist, (int, float, np.floating, np.integer)):
+            n, (a, b), staged = self._query_inputs(("p", p, (3,)), ("q", q, (3,)))
+            md = torch.full((max(n, 0),), float(max_dist), dtype=torch.float32, device=a.device)
+            staged = True  # filled on torch's current stream: `stream` has to wait for it like for a copied numpy input
+        else:
+            n, (a, b, md), staged = self._query_inputs(("p", p, (3,)), ("q", q, (3,)), ("max_dist", max_dist, ()), optional=("max_dist",))
+        vec = ((3,), torch.float32)
+        outs = self._query_outputs(n, ((), torch.float32), ((), torch.int32), ((), torch.float32), ((), torch.uint8), ((), torch.uint8), vec, vec)
+        out = SegmentOut(*_dptrs(*outs))
+        self._query_call("tyr_query_segment", stream, staged, n, *_dptrs(a, b, md), 0, C.byref(out))
+        return tuple(outs)
 
     def query_box(self, lo, hi, max_prims=0, any=False, stream=None):
         """tyr_query_box: for every axis-aligned box [lo, hi] the triangles of the uploaded scene it touches (include/tyr_c.h
