@@ -1,5 +1,5 @@
 """What the test modules of the scene queries share (test_ray_query, test_hit_query, test_point_query, test_point_query_k,
-test_occlusion_query, test_winding_query, test_sweep_query, test_box_query, test_query_streams): the scenes and inputs more than
+test_occlusion_query, test_winding_query, test_sweep_query, test_box_query, test_query_streams, test_query_shapes): the scenes and inputs more than
 one of them is run on, the renderer they ask, the comparison of an answer with its restatement, and the checks every query kind
 repeats -- what the compiler made of its kernels, its part of the ABI, that it leaves a render alone.
 

@@ -19,6 +19,7 @@ import sys
 import numpy as np
 import pytest
 
+import aov_ref
 import specular_ref as sr
 import test_aov
 import test_temporal
@@ -71,14 +72,7 @@ SCENES = ("table", "strip", "hall", "inside_glass")
 
 
 def oracle_queue(orc, sc, nodes, prims, spp, frame=None, rank=0, nranks=1, w=W, h=H):
-    """an oracle ctx after begin / primary / extend with queue_size = spp * P, and its queue: every sample's first segment in
-    ticket order"""
-    n = spp * w * (h // nranks)
-    o = orc.Oracle(w, h, n, rank=rank, nranks=nranks, flags=test_aov.flags_of(sc) & 25)
-    o.load_scene(sc, nodes, prims)
-    if frame is not None:
-        o.set_frame(frame)
-    return o, test_aov.first_wavefront(o, n)
+    return aov_ref.oracle_queue(orc, sc, nodes, prims, spp, w, h, frame=frame, rank=rank, nranks=nranks)
 
 
 def restated(orc, name, spp, max_chain, **kw):
@@ -144,22 +138,11 @@ def test_refr_step_candidates_are_the_oracles_shade(orc):
     assert all(v > 0 for v in seen.values()), seen
 
 
-class OracleMath:
-    """test_aov.expected_aov's vector operations from the oracle's glm restatement (the op codes of tyr_vecmath_probe), so that
-    it runs without a GPU"""
-
-    def __init__(self, lib):
-        self.lib = lib
-
-    def vecmath_probe(self, op, a, b, c):
-        return sr.glm(self.lib, op, a, b, c)
-
-
 @pytest.mark.parametrize("name", ["cornell36", "cornell_colored", "glass_dof48", "mesh128"])
 def test_restatement_without_chains_is_the_first_hit_definition(orc, name):
     """max_chain = 0: the restatement equals test_aov.expected_aov on the oracle's first wavefront; chain 0, the end ids the
     first ids, length0 sample 0's t, depth_first the depth"""
-    hip = OracleMath(orc.lib())
+    hip = aov_ref.OracleMath(orc.lib())
     sc, nodes, prims = built_scene(name)
     spp = 3
     o, q = oracle_queue(orc, sc, nodes, prims, spp)
