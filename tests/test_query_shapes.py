@@ -1,11 +1,12 @@
 """Every query-like entry under every shape of the scene its ctx can hand it, bit for bit against the entry's restatement.
 
 A query takes its scene from launch_scene (host/driver.cpp): nStaged = min(the tree's staged records, TYR_TUNE_STAGED_NODES).
-That count decides, at every step of every descent, which of two hand-written node fetches runs: `idx < nStaged` reads the
-block's vector-major LDS copy through an explicit address-space-3 pointer, everything else reads the quad array in HBM.  The
-fetch is written out once per kernel family -- hip/box.hip, tri.hip, sweep.hip, segment.hip, nearest_common.hpp (nearest,
-nearest_k), hits.hip, and test_quad in traverse.hpp behind q_traverse (closest / any with and without spheres, occlusion, the
-AOV and chain kernels) -- and q_stage_nodes fills the LDS copy from the same count.  The entries' own modules only ever run at
+That count decides, at every step of every descent, which tail of the node fetch runs: `idx < nStaged` reads the block's
+vector-major LDS copy through an explicit address-space-3 pointer, everything else reads the quad array in HBM.  The fetch is
+written out in one place, fetch_quad in hip/traverse.hpp, and every kernel family reaches it through its own descent -- the
+keyed descent (nearest, nearest_k, sweep, segment), the overlap descent (box, tri) and test_quad behind the ray descent (hits;
+closest / any with and without spheres, occlusion, the AOV and chain kernels) -- with its own key, slot test and push order
+behind it; q_stage_nodes fills the LDS copy from the same count.  The entries' own modules only ever run at
 nStaged = min(64, quads in the tree).
 
 Why a wrong fetch cannot pass here.  Which fetch a shape forces:

@@ -8,10 +8,11 @@
 // ticket feed, the first nStaged quad records in LDS, the LdsStack without entry distances, triangle_load, the flat lane states
 // (interior ref | leaf ref | kRefPop | kRefDone).
 //
-// The quad step is this unit's own: the record's seven vectors as n_traverse loads them (hip/nearest_common.hpp), four closed
-// interval tests of a slot's box against [lo, hi] in binary32, descend into the first slot that passes in node order and push
-// the others so that they pop in node order.  There is no key, no sort and no entry distance: the bound is the box and never
-// changes, so a popped entry is always taken.  Pruning is exact and needs no slack: a node's stored box contains the corners
+// The descent is the overlap one (overlap_round, hip/query_common.hpp), shared with tri.hip: the record's seven vectors
+// (fetch_quad, hip/traverse.hpp), four closed interval tests of a slot's box against [lo, hi] in binary32 -- this unit's
+// box_overlaps -- descend into the first slot that passes in node order and push the others so that they pop in node order.
+// There is no key, no sort and no entry distance: the bound is the box and never changes, so a popped entry is always taken.
+// Pruning is exact and needs no slack: a node's stored box contains the corners
 // A, B, C of every triangle below it, and a member's corners do not all lie beyond one face of [lo, hi] (rule 1 of the member
 // test) -- so a slot whose box fails the closed interval test on some axis holds no member.  An unused slot's box lies at
 // +infinity (lo = +inf fails `lo <= hi_k`), a synthetic record's from -inf to +inf (passes).
@@ -27,15 +28,13 @@
 
 #include "device_common.hpp"
 #include "query_common.hpp"
+#include "vecmath64.hpp"
 
 namespace tyr {
 
 namespace {
 
 // ---- the member test of a (box, triangle) pair: include/tyr_c.h "Box-overlap queries", rules 2 and 3 -------------------------
-
-__device__ __forceinline__ double mind(double a, double b) { return b < a ? b : a; }
-__device__ __forceinline__ double maxd(double a, double b) { return b > a ? b : a; }
 
 // An edge axis a = cross(unit_i, f) with the zeros and ones multiplied out: with (u, v) the two other components in cyclic
 // order a_u = -f_v, a_v = f_u and a_i = 0.  The terms of the zero component are +-0 in every sum of the definition and change
@@ -93,88 +92,26 @@ __device__ __forceinline__ bool box_overlaps(const BoxLane& q, float lox, float 
 	return lox <= q.hx && hix >= q.lx && loy <= q.hy && hiy >= q.ly && loz <= q.hz && hiz >= q.lz;
 }
 
-// One round of the wave's traversal: the descent, one pop attempt and one quad step per lane per trip, until no lane descends
-// -- or fewer than kQueryMinTraversing do and a lane is at a leaf or `canRefill()` says enough lanes could start new work; then
-// one leaf per lane that is at one, primitives in array order, each member counted and handed to `offer(prim)`.
+// One round of the wave's traversal: the overlap descent (overlap_round, hip/query_common.hpp) on box_overlaps, then one leaf
+// per lane that is at one, primitives in array order, each member counted and handed to `offer(prim)`.
 template <bool ANY, class CanRefill, class Offer>
 __device__ __forceinline__ void b_traverse(const DevScene& sc, LdsStack<kQueryStackLds, false>& st, const float4* stagedNodes, BoxLane& q, CanRefill canRefill, Offer offer) {
-	const uint32_t nStaged = sc.nStaged;
-	// (the quad array's address as an opaque global-memory pointer: see q_traverse)
-	auto held = (const __attribute__((address_space(1))) float4*)sc.quads;
-	__asm__ volatile("" : "+s"(held));
-	const float4* quads = (const float4*)held;
-	uint32_t ref = q.ref;
-	for (;;) {
-		const uint32_t nTrav = (uint32_t)__popcll(lanes_traversing(ref));
-		if (nTrav == 0)
-			break;
-		if (nTrav < kQueryMinTraversing) {
-			const bool anyLeaf = lanes_at_leaf(ref) != 0ull;
-			if (anyLeaf || canRefill(ref))
-				break;
-		}
-		if (ref == kRefPop) {
-			uint32_t pr;
-			float pt;
-			ref = st.pop(pr, pt) ? pr : kRefDone; // (no entry distance and a constant bound: a popped entry is always taken)
-		}
-		if ((int)ref >= 0) {
-			const uint32_t idx = ref & kQuadIndexMask;
-			float4 x01, x23, y01, y23, z01, z23, rf;
-			if (idx < nStaged) { // (explicit LDS pointers and a tail of its own: see test_quad)
-#if defined(__HIP_DEVICE_COMPILE__)
-				typedef __attribute__((address_space(3))) const float4* lds_f4;
-				const lds_f4 c = (lds_f4)stagedNodes + idx;
-#else
-				const float4* c = stagedNodes + idx; // host pass of the same source: never executed
-#endif
-				x01 = c[0 * kStagedNodes], x23 = c[1 * kStagedNodes], y01 = c[2 * kStagedNodes], y23 = c[3 * kStagedNodes];
-				z01 = c[4 * kStagedNodes], z23 = c[5 * kStagedNodes], rf = c[6 * kStagedNodes];
-				__asm__ volatile("" : "+v"(rf.x));
-			} else {
-				const float4* n = quads + 8 * idx;
-				x01 = n[0], x23 = n[1], y01 = n[2], y23 = n[3], z01 = n[4], z23 = n[5], rf = n[6];
-			}
-			const uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
-			const bool p0 = box_overlaps(q, x01.x, x01.y, y01.x, y01.y, z01.x, z01.y);
-			const bool p1 = box_overlaps(q, x01.z, x01.w, y01.z, y01.w, z01.z, z01.w);
-			const bool p2 = box_overlaps(q, x23.x, x23.y, y23.x, y23.y, z23.x, z23.y);
-			const bool p3 = box_overlaps(q, x23.z, x23.w, y23.z, y23.w, z23.z, z23.w);
-			// every passing slot but the first goes onto the stack, the last in node order first: they pop in node order
-			const lanemask h0 = lanes_where(p0), h1 = lanes_where(p1), h2 = lanes_where(p2), h3 = lanes_where(p3);
-			const lanemask any01 = h0 | h1, any012 = any01 | h2;
-			st.push3(h3 & any012, r3, 0.f, h2 & any01, r2, 0.f, h1 & h0, r1, 0.f);
-			ref = p0 ? r0 : p1 ? r1 : p2 ? r2 : p3 ? r3 : kRefPop;
-		}
-	}
-	if (ref_is_leaf(ref)) {
-		const uint32_t off = ref & (kMaxPrimOffset - 1);
-		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-		bool found = false;
-		TriData tri = triangle_load(sc.tris, off);
-		for (uint32_t i = 0; i < cnt && !(ANY && found); ++i) {
-			const TriData cur = tri; // the next primitive of the leaf is on its way while this one is tested
-			if (i + 1 < cnt)
-				tri = triangle_load(sc.tris, off + i + 1);
-			// the corners tyr_triangle_bboxes bounds: vert and the binary32 sums vert + e1, vert + e2
-			const float ax = cur.a.x, ay = cur.a.y, az = cur.a.z;
-			const float bx = ax + cur.a.w, by = ay + cur.b.x, bz = az + cur.b.y;
-			const float cx = ax + cur.b.z, cy = ay + cur.b.w, cz = az + cur.c.x;
-			// rule 1, the box axes: exact comparisons of the inputs
-			if (!box_overlaps(q, __builtin_fminf(__builtin_fminf(ax, bx), cx), __builtin_fmaxf(__builtin_fmaxf(ax, bx), cx), __builtin_fminf(__builtin_fminf(ay, by), cy),
-			                  __builtin_fmaxf(__builtin_fmaxf(ay, by), cy), __builtin_fminf(__builtin_fminf(az, bz), cz), __builtin_fmaxf(__builtin_fmaxf(az, bz), cz)))
-				continue;
-			if (!box_member(ax, ay, az, bx, by, bz, cx, cy, cz, q.lx, q.ly, q.lz, q.hx, q.hy, q.hz))
-				continue;
-			q.count += 1u;
-			if (ANY)
-				found = true;
-			else if ((int)(off + i) <= q.worst) // (a full row, or one of no entries, turns a larger index away)
-				offer((int)(off + i));
-		}
-		ref = found ? kRefDone : kRefPop;
-	}
-	q.ref = ref;
+	q.ref = overlap_round(
+		sc, st, stagedNodes, q.ref, canRefill, [&](float lox, float hix, float loy, float hiy, float loz, float hiz) { return box_overlaps(q, lox, hix, loy, hiy, loz, hiz); },
+		[&](uint32_t leaf) {
+			return leaf_prims<ANY>(sc.tris, leaf, [&](const TriData& cur, int prim) {
+				const CornerBox t = tri_corner_box(cur);
+				// rule 1, the box axes: exact comparisons of the inputs
+				const bool member = box_overlaps(q, t.lox, t.hix, t.loy, t.hiy, t.loz, t.hiz) &&
+				                    box_member(t.a.x, t.a.y, t.a.z, t.b.x, t.b.y, t.b.z, t.c.x, t.c.y, t.c.z, q.lx, q.ly, q.lz, q.hx, q.hy, q.hz);
+				if (member) {
+					q.count += 1u;
+					if (!ANY && prim <= q.worst) // (a full row, or one of no entries, turns a larger index away)
+						offer(prim);
+				}
+				return member;
+			});
+		});
 }
 
 } // namespace

@@ -4,8 +4,8 @@
 // would test if it never returned early, with no visit order in it).
 //
 // One ray to a lane on the queries' persistent grid, with their pieces (hip/query_common.hpp, hip/traverse.hpp): the chunked
-// ticket feed, the first nStaged quad records in LDS, the LdsStack without entry distances, and the any-hit form of the
-// descent -- test_quad in node order against a bound that never shrinks (the ray's tmax), so that no entry is re-tested when
+// ticket feed, the first nStaged quad records in LDS, the LdsStack without entry distances, and the any-hit form of the ray
+// queries' descent (ray_descent<true>) -- test_quad in node order against a bound that never shrinks (the ray's tmax), so that no entry is re-tested when
 // it is popped and the set of leaves reached does not depend on the order (hip/traverse.hpp "Exactness").  No leaf ends a
 // ray: `count` needs the whole segment.
 //
@@ -63,49 +63,18 @@ struct HitsLane {
 	int worstPrim;                            // ... and its triangle
 };
 
-// One round of the wave's traversal: q_traverse's any-hit descent (hip/query_common.hpp) -- one pop attempt and one quad test
-// per lane per trip, until no lane descends, or fewer than kQueryMinTraversing do and a lane is at a leaf or `canRefill()`
-// says enough lanes could start new work -- then one leaf per lane that is at one: every primitive in array order, each
-// accepted hit (bvh.h:229) counted and handed to `offer(t, prim)`.
+// One round of the wave's traversal: the ray queries' any-hit descent (ray_descent<true>, hip/query_common.hpp), then one leaf
+// per lane that is at one: every primitive in array order, each accepted hit (bvh.h:229) counted and handed to
+// `offer(t, prim)`.
 template <bool TWO_SIDED, class CanRefill, class Offer>
 __device__ __forceinline__ void h_traverse(const DevScene& sc, LdsStack<kQueryStackLds, false>& st, const float4* stagedNodes, HitsLane& q, bool live, CanRefill canRefill, Offer offer) {
 	const uint32_t nStaged = sc.nStaged;
-	// (the quad array's address as an opaque global-memory pointer: see q_traverse)
-	auto held = (const __attribute__((address_space(1))) float4*)sc.quads;
-	__asm__ volatile("" : "+s"(held));
-	const float4* quads = (const float4*)held;
+	const float4* quads = pinned_quads(sc);
 	const bool allRegular = (__ballot(live && !q.regular) == 0ull);
 	const RayConst r = { mk3(q.ox, q.oy, q.oz), mk3(q.dx, q.dy, q.dz), mk3(q.ix, q.iy, q.iz), q.ix < 0, q.iy < 0, q.iz < 0 }; // bvh.h:216-217
-	uint32_t ref = q.ref;
-	for (;;) {
-		const uint32_t nTrav = (uint32_t)__popcll(lanes_traversing(ref));
-		if (nTrav == 0)
-			break;
-		if (nTrav < kQueryMinTraversing) {
-			const bool anyLeaf = lanes_at_leaf(ref) != 0ull;
-			if (anyLeaf || canRefill(ref))
-				break;
-		}
-		if (ref == kRefPop) {
-			uint32_t pr;
-			float pt;
-			ref = st.pop(pr, pt) ? pr : kRefDone; // (no entry distance and a constant bound: a popped entry is always taken)
-		}
-		if ((int)ref >= 0) {
-			const QuadHits h = allRegular ? test_quad<true, false, true>(quads, ref, r, q.tmax, stagedNodes, nStaged) : test_quad<false, false, true>(quads, ref, r, q.tmax, stagedNodes, nStaged);
-			const lanemask any01 = h.hit[0] | h.hit[1], any012 = any01 | h.hit[2];
-			st.push3(h.hit[3] & any012, h.ref[3], h.t[3], h.hit[2] & any01, h.ref[2], h.t[2], h.hit[1] & h.hit[0], h.ref[1], h.t[1]);
-			ref = lane_in(h.hit[0]) ? h.ref[0] : lane_in(h.hit[1]) ? h.ref[1] : lane_in(h.hit[2]) ? h.ref[2] : lane_in(h.hit[3]) ? h.ref[3] : kRefPop;
-		}
-	}
+	uint32_t ref = ray_descent<true>(quads, st, stagedNodes, nStaged, r, allRegular, q.tmax, q.ref, canRefill);
 	if (ref_is_leaf(ref)) {
-		const uint32_t off = ref & (kMaxPrimOffset - 1);
-		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-		TriData tri = triangle_load(sc.tris, off);
-		for (uint32_t i = 0; i < cnt; ++i) {
-			const TriData cur = tri; // the next primitive of the leaf is on its way while this one is tested
-			if (i + 1 < cnt)
-				tri = triangle_load(sc.tris, off + i + 1);
+		leaf_prims<false>(sc.tris, ref, [&](const TriData& cur, int prim) {
 			bool back = false;
 			float u, v;
 			const float t = hit_value<TWO_SIDED>(cur, r.o, r.d, back, u, v);
@@ -113,11 +82,11 @@ __device__ __forceinline__ void h_traverse(const DevScene& sc, LdsStack<kQuerySt
 				q.count += 1u;
 				q.back += back ? 1u : 0u;
 				if (!(t < q.worstT)) // full, and not nearer than the worst kept entry: farther, or a tie that the index decides
-					if (t > q.worstT || (int)(off + i) > q.worstPrim)
-						continue;
-				offer(t, (int)(off + i));
+					if (t > q.worstT || prim > q.worstPrim)
+						return;
+				offer(t, prim);
 			}
-		}
+		});
 		ref = kRefPop;
 	}
 	q.ref = ref;

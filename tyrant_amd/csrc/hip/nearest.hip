@@ -10,7 +10,8 @@
 // entry is tested against it again when it is popped.  The records' visit-order bits are for rays and play no part.
 //
 // Pruning never changes the answer: the key, its slack (kSlackFar2 = 256.f * kUlpHalf of far2, kSlackCoord = 64.f * kUlpHalf
-// of farInf * max |p_k|), the pair's value and the descent are hip/nearest_common.hpp's, shared with hip/nearest_k.hip.
+// of farInf * max |p_k|) and the pair's value are hip/nearest_common.hpp's, shared with hip/nearest_k.hip; the descent is the
+// keyed one of hip/query_common.hpp (keyed_round), which sweep.hip and segment.hip use too.
 #include "nearest.hpp"
 #include "nearest_common.hpp"
 

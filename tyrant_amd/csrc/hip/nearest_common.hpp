@@ -1,6 +1,6 @@
 // nearest_common.hpp -- what the point queries share (hip/nearest.hip: the nearest triangle; hip/nearest_k.hip: the k nearest
 // and those within a radius): the value of a (point, triangle) pair, the pruning key of a box with its slack, and the round
-// of traversal that orders a quad record's four slots by that key and takes a leaf's primitives.  Device code of the two
+// of traversal: the keyed descent of hip/query_common.hpp on that key, and a leaf's primitives.  Device code of the two
 // units only.
 //
 // Pruning never changes the answer (DESIGN.md "Closest-point queries" derives the constants).  A box is skipped only when
@@ -88,94 +88,14 @@ __device__ __forceinline__ float box_key(const Lane& q, float lox, float hix, fl
 	return (lb2 < kInf && key <= q.best) ? key : kInf;
 }
 
-#define TYR_NEAREST_SWAP(a, b)                         \
-	{                                                  \
-		const bool s_ = k##a > k##b;                   \
-		const float tk_ = s_ ? k##b : k##a;            \
-		const uint32_t tr_ = s_ ? r##b : r##a;         \
-		k##b = s_ ? k##a : k##b, r##b = s_ ? r##a : r##b; \
-		k##a = tk_, r##a = tr_;                        \
-	}
-
-// One round of the wave's traversal, the shape of q_traverse (hip/query_common.hpp): the descent, one pop attempt and one quad
-// step per lane per trip, until no lane descends -- or fewer than kQueryMinTraversing do and a lane is at a leaf or
-// `canRefill()` says enough lanes could start new work; then one leaf per lane that is at one, primitives in array order,
-// each one's value handed to `take(q, F, prim)`.  A quad step orders the four slots by their keys, descends into the nearest
-// and pushes the others farthest first; a popped entry's key is tested against the bound again.
+// One round of the wave's traversal: the keyed descent (keyed_round, hip/query_common.hpp) on box_key against the lane's
+// `best`, then one leaf per lane that is at one, each primitive's value handed to `take(q, F, prim)`.
 template <class Lane, class CanRefill, class Take>
 __device__ __forceinline__ void n_traverse(const DevScene& sc, LdsStack<kQueryStackLds, true>& st, const float4* stagedNodes, Lane& q, CanRefill canRefill, Take take) {
-	const uint32_t nStaged = sc.nStaged;
-	// (the quad array's address as an opaque global-memory pointer: see q_traverse)
-	auto held = (const __attribute__((address_space(1))) float4*)sc.quads;
-	__asm__ volatile("" : "+s"(held));
-	const float4* quads = (const float4*)held;
 	const f3 p = mk3(q.px, q.py, q.pz);
-	uint32_t ref = q.ref;
-	for (;;) {
-		const uint32_t nTrav = (uint32_t)__popcll(lanes_traversing(ref));
-		if (nTrav == 0)
-			break;
-		if (nTrav < kQueryMinTraversing) {
-			const bool anyLeaf = lanes_at_leaf(ref) != 0ull;
-			if (anyLeaf || canRefill(ref))
-				break;
-		}
-		if (ref == kRefPop) {
-			uint32_t pr;
-			float pk;
-			if (st.pop(pr, pk)) {
-				if (pk <= q.best) // the entry's key against what has been found since it was pushed
-					ref = pr;
-			} else {
-				ref = kRefDone;
-			}
-		}
-		if ((int)ref >= 0) {
-			const uint32_t idx = ref & kQuadIndexMask;
-			float4 x01, x23, y01, y23, z01, z23, rf;
-			if (idx < nStaged) { // (explicit LDS pointers and a tail of its own: see test_quad)
-#if defined(__HIP_DEVICE_COMPILE__)
-				typedef __attribute__((address_space(3))) const float4* lds_f4;
-				const lds_f4 c = (lds_f4)stagedNodes + idx;
-#else
-				const float4* c = stagedNodes + idx; // host pass of the same source: never executed
-#endif
-				x01 = c[0 * kStagedNodes], x23 = c[1 * kStagedNodes], y01 = c[2 * kStagedNodes], y23 = c[3 * kStagedNodes];
-				z01 = c[4 * kStagedNodes], z23 = c[5 * kStagedNodes], rf = c[6 * kStagedNodes];
-				__asm__ volatile("" : "+v"(rf.x));
-			} else {
-				const float4* n = quads + 8 * idx;
-				x01 = n[0], x23 = n[1], y01 = n[2], y23 = n[3], z01 = n[4], z23 = n[5], rf = n[6];
-			}
-			uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
-			float k0 = box_key(q, x01.x, x01.y, y01.x, y01.y, z01.x, z01.y);
-			float k1 = box_key(q, x01.z, x01.w, y01.z, y01.w, z01.z, z01.w);
-			float k2 = box_key(q, x23.x, x23.y, y23.x, y23.y, z23.x, z23.y);
-			float k3 = box_key(q, x23.z, x23.w, y23.z, y23.w, z23.z, z23.w);
-			// the four by key, nearest first: a sorting network of selects (skipped slots carry +inf and end up last)
-			TYR_NEAREST_SWAP(0, 1)
-			TYR_NEAREST_SWAP(2, 3)
-			TYR_NEAREST_SWAP(0, 2)
-			TYR_NEAREST_SWAP(1, 3)
-			TYR_NEAREST_SWAP(1, 2)
-			st.push3(lanes_where(k3 < kInf), r3, k3, lanes_where(k2 < kInf), r2, k2, lanes_where(k1 < kInf), r1, k1);
-			ref = k0 < kInf ? r0 : kRefPop;
-		}
-	}
-	if (ref_is_leaf(ref)) {
-		const uint32_t off = ref & (kMaxPrimOffset - 1);
-		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-		TriData tri = triangle_load(sc.tris, off);
-		for (uint32_t i = 0; i < cnt; ++i) {
-			const TriData cur = tri; // the next primitive of the leaf is on its way while this one is evaluated
-			if (i + 1 < cnt)
-				tri = triangle_load(sc.tris, off + i + 1);
-			const float F = nearest_value<false>(cur, p).F;
-			take(q, F, (int)(off + i));
-		}
-		ref = kRefPop;
-	}
-	q.ref = ref;
+	q.ref = keyed_round(
+		sc, st, stagedNodes, q.ref, q.best, canRefill, [&](float lox, float hix, float loy, float hiy, float loz, float hiz) { return box_key(q, lox, hix, loy, hiy, loz, hiz); },
+		[&](uint32_t leaf) { leaf_prims<false>(sc.tris, leaf, [&](const TriData& cur, int prim) { take(q, nearest_value<false>(cur, p).F, prim); }); });
 }
 
 } // namespace tyr

@@ -1,8 +1,12 @@
-// query_common.hpp -- the persistent per-lane traversal loop of the ray queries (hip/query.hip) and of the guide passes
-// (hip/aov.hip), once: the staged top nodes, the chunked ticket feed, the descent with its exit test, the leaf loop with the
-// accept rule, the spheres' closest-hit pre-test and the overflow report.  A kernel supplies what a lane's item is (a
-// caller's ray, a pixel's samples), how its ray is made and where its answer goes; the lane states are those of k_trace_flat
-// (hip/traverse.hpp: interior ref | leaf ref | kRefPop | kRefDone).
+// query_common.hpp -- what the batched queries on the uploaded scene and the guide passes (hip/aov.hip) share, once: the staged
+// top nodes, the chunked ticket feed, the overflow report, and a round of the wave's traversal with its pieces -- the pinned
+// quad pointer, the exit test, the leaf iterator, a triangle's corner box -- built into three descents:
+//   keyed_round    a bound that shrinks: slots keyed, sorted, re-tested when popped   (nearest, nearest_k, sweep, segment)
+//   overlap_round  a bound that never changes: slots tested, node order               (box, tri)
+//   ray_descent    test_quad against a ray; q_traverse adds the ray queries' leaf     (query, occlusion, aov; hits)
+// A kernel supplies what a lane's item is (a caller's ray, a pixel's samples, a point, a box), its slot test, what it does
+// with a leaf and where its answer goes; its outer loop (refill, top_up, finish) is its own.  The lane states are those of
+// k_trace_flat (hip/traverse.hpp: interior ref | leaf ref | kRefPop | kRefDone).
 #pragma once
 
 #include "device_common.hpp"
@@ -117,24 +121,173 @@ __device__ __forceinline__ void q_spheres_closest(const tyr_sphere* spheres, con
 	}
 }
 
-// One round of the wave's traversal (`live`: the lane holds an item; a lane without a ray in the tree has q.ref == kRefDone).
-// The descent, one pop attempt and one quad test per lane per trip, until no lane descends -- or fewer than
-// kQueryMinTraversing do and a lane is at a leaf or `canRefill()` says enough lanes could start new work; then one leaf per
-// lane that is at one: bvh.h:129-140 (closest hit) / bvh.h:229-238 (any hit), primitives in array order.  The accept rules
-// of these kernels are the two in the leaf loop below.
-template <bool ANY, class CanRefill>
-__device__ __forceinline__ void q_traverse(const DevScene& sc, LdsStack<kQueryStackLds, !ANY>& st, const float4* stagedNodes, QueryRay& q, bool live, CanRefill canRefill) {
-	const uint32_t nStaged = sc.nStaged;
-	// The quad array's address, read here into a global-memory pointer that is opaque from here on: as a plain read of the
-	// by-value argument it is rematerialised where scalar registers run short -- in the guide kernels an s_load and its wait
-	// in every trip of the descent.  (Address space 1: through a generic pointer the node loads would become flat loads.)
+// ---- the pieces of a round of the wave's traversal, for every descent on the quad tree ----------------------------------------
+// A round is: the descent -- per trip the exit test, one pop attempt, one record fetch (fetch_quad, hip/traverse.hpp), a test
+// of the record's four slots and the pushes -- and then one leaf per lane that is at one.  Lane states are k_trace_flat's
+// (hip/traverse.hpp: interior ref | leaf ref | kRefPop | kRefDone); a lane without an item in the tree holds kRefDone.
+
+// The quad array's address, read here into a global-memory pointer that is opaque from here on: as a plain read of the
+// by-value argument it is rematerialised where scalar registers run short -- in the guide kernels an s_load and its wait
+// in every trip of the descent.  (Address space 1: through a generic pointer the node loads would become flat loads.)
+__device__ __forceinline__ const float4* pinned_quads(const DevScene& sc) {
 	auto held = (const __attribute__((address_space(1))) float4*)sc.quads;
 	__asm__ volatile("" : "+s"(held));
-	const float4* quads = (const float4*)held;
-	const bool allRegular = (__ballot(live && !q.regular) == 0ull);
-	const RayConst r = { mk3(q.ox, q.oy, q.oz), mk3(q.dx, q.dy, q.dz), mk3(q.ix, q.iy, q.iz), q.ix < 0, q.iy < 0, q.iz < 0 }; // bvh.h:120-121
-	uint32_t ref = q.ref;
+	return (const float4*)held;
+}
+
+// The exit test of the descent: no lane descends -- or fewer than kQueryMinTraversing do and a lane is at a leaf or
+// `canRefill(ref)` says enough lanes could start new work.
+template <class CanRefill>
+__device__ __forceinline__ bool descent_ends(uint32_t ref, CanRefill canRefill) {
+	const uint32_t nTrav = (uint32_t)__popcll(lanes_traversing(ref));
+	return nTrav == 0 || (nTrav < kQueryMinTraversing && (lanes_at_leaf(ref) != 0ull || canRefill(ref)));
+}
+
+// A leaf's primitives in array order, each handed to `body(cur, prim)` while the next one's record is on its way.  STOPS: the
+// body returns "found" and a true ends the leaf (the ANY forms); otherwise its result, if any, is not looked at.
+template <bool STOPS, class Body>
+__device__ __forceinline__ bool leaf_prims(const float4* __restrict__ tris, uint32_t leaf, Body body) {
+	const uint32_t off = leaf & (kMaxPrimOffset - 1);
+	const uint32_t cnt = ((leaf >> 26) & 31u) + 1u;
+	bool found = false;
+	TriData tri = triangle_load(tris, off);
+	for (uint32_t i = 0; i < cnt && !(STOPS && found); ++i) {
+		const TriData cur = tri;
+		if (i + 1 < cnt)
+			tri = triangle_load(tris, off + i + 1);
+		if constexpr (STOPS)
+			found = body(cur, (int)(off + i));
+		else
+			body(cur, (int)(off + i));
+	}
+	return found;
+}
+
+// The corners tyr_triangle_bboxes bounds -- vert and the binary32 sums vert + e1, vert + e2 -- and their box: what a leaf of
+// the stored tree bounds, so a slot's test applies to a single triangle as it stands.
+struct CornerBox {
+	f3 a, b, c;
+	float lox, hix, loy, hiy, loz, hiz;
+};
+__device__ __forceinline__ CornerBox tri_corner_box(const TriData& t) {
+	CornerBox o;
+	o.a = mk3(t.a.x, t.a.y, t.a.z);
+	o.b = mk3(t.a.x + t.a.w, t.a.y + t.b.x, t.a.z + t.b.y);
+	o.c = mk3(t.a.x + t.b.z, t.a.y + t.b.w, t.a.z + t.c.x);
+	o.lox = __builtin_fminf(__builtin_fminf(o.a.x, o.b.x), o.c.x), o.hix = __builtin_fmaxf(__builtin_fmaxf(o.a.x, o.b.x), o.c.x);
+	o.loy = __builtin_fminf(__builtin_fminf(o.a.y, o.b.y), o.c.y), o.hiy = __builtin_fmaxf(__builtin_fmaxf(o.a.y, o.b.y), o.c.y);
+	o.loz = __builtin_fminf(__builtin_fminf(o.a.z, o.b.z), o.c.z), o.hiz = __builtin_fmaxf(__builtin_fmaxf(o.a.z, o.b.z), o.c.z);
+	return o;
+}
+
+// ---- the two box descents ------------------------------------------------------------------------------------------------------
+
+// one compare-exchange of the keyed descent's sorting network: afterwards ka <= kb, each key with its reference
+__device__ __forceinline__ void key_swap(float& ka, uint32_t& ra, float& kb, uint32_t& rb) {
+	const bool s = ka > kb;
+	const float tk = s ? kb : ka;
+	const uint32_t tr = s ? rb : ra;
+	kb = s ? ka : kb, rb = s ? ra : rb;
+	ka = tk, ra = tr;
+}
+
+// One round of a query whose bound shrinks as it finds things (nearest, nearest_k, sweep, segment).  `keyOf(lox, hix, loy, hiy,
+// loz, hiz)` is a slot's key, a lower bound of every value below the slot, +inf for a slot that is skipped.  A quad step
+// orders the four slots by key, descends into the nearest and pushes the others farthest first; a popped entry is taken if
+// its key is still `<= bound`, the lane's bound as the round begins (it changes at leaves only).  `leaf(ref)` takes a reached
+// leaf.  Returns the lane's new state.
+// The re-test is written `pk <= bound` for every caller, where hip/segment.hip used to write `!(pk > bound)`: the two differ
+// only for a NaN, and neither side is one.  A key is pushed only when `key < +inf` holds, which a NaN fails.  A bound starts
+// as max_dist * max_dist behind `max_dist >= 0`, as +inf, or as a finite tmax, and later takes only values that passed
+// `value < bound` or `value == bound` (the kernels' take rules), which a NaN fails too.
+template <class CanRefill, class KeyOf, class Leaf>
+__device__ __forceinline__ uint32_t keyed_round(const DevScene& sc, LdsStack<kQueryStackLds, true>& st, const float4* stagedNodes, uint32_t ref, float bound, CanRefill canRefill, KeyOf keyOf,
+                                                Leaf leaf) {
+	constexpr float kSkipped = __builtin_inff();
+	const uint32_t nStaged = sc.nStaged;
+	const float4* quads = pinned_quads(sc);
+	while (!descent_ends(ref, canRefill)) {
+		if (ref == kRefPop) {
+			uint32_t pr;
+			float pk;
+			if (st.pop(pr, pk)) {
+				if (pk <= bound) // the entry's key against what has been found since it was pushed
+					ref = pr;
+			} else {
+				ref = kRefDone;
+			}
+		}
+		if ((int)ref >= 0) {
+			QuadRecord n;
+			fetch_quad<true>(n, quads, ref, stagedNodes, nStaged);
+			uint32_t r0 = __float_as_uint(n.rf.x), r1 = __float_as_uint(n.rf.y), r2 = __float_as_uint(n.rf.z), r3 = __float_as_uint(n.rf.w);
+			float k0 = keyOf(n.x01.x, n.x01.y, n.y01.x, n.y01.y, n.z01.x, n.z01.y);
+			float k1 = keyOf(n.x01.z, n.x01.w, n.y01.z, n.y01.w, n.z01.z, n.z01.w);
+			float k2 = keyOf(n.x23.x, n.x23.y, n.y23.x, n.y23.y, n.z23.x, n.z23.y);
+			float k3 = keyOf(n.x23.z, n.x23.w, n.y23.z, n.y23.w, n.z23.z, n.z23.w);
+			// the four by key, nearest first: a sorting network of selects (skipped slots carry +inf and end up last)
+			key_swap(k0, r0, k1, r1);
+			key_swap(k2, r2, k3, r3);
+			key_swap(k0, r0, k2, r2);
+			key_swap(k1, r1, k3, r3);
+			key_swap(k1, r1, k2, r2);
+			st.push3(lanes_where(k3 < kSkipped), r3, k3, lanes_where(k2 < kSkipped), r2, k2, lanes_where(k1 < kSkipped), r1, k1);
+			ref = k0 < kSkipped ? r0 : kRefPop;
+		}
+	}
+	if (ref_is_leaf(ref)) {
+		leaf(ref);
+		ref = kRefPop;
+	}
+	return ref;
+}
+
+// One round of a query whose bound never changes (box, tri).  `overlaps(lox, hix, loy, hiy, loz, hiz)` says whether a slot can
+// hold a member.  A quad step descends into the first slot that passes in node order and pushes the others, the last first, so
+// that they pop in node order; there is no key, no sort and no entry distance, and a popped entry is always taken.
+// `leaf(ref)` takes a reached leaf and returns whether the lane's item is finished with it (the ANY forms' first member).
+// Returns the lane's new state.
+template <class CanRefill, class Overlaps, class Leaf>
+__device__ __forceinline__ uint32_t overlap_round(const DevScene& sc, LdsStack<kQueryStackLds, false>& st, const float4* stagedNodes, uint32_t ref, CanRefill canRefill, Overlaps overlaps,
+                                                  Leaf leaf) {
+	const uint32_t nStaged = sc.nStaged;
+	const float4* quads = pinned_quads(sc);
+	while (!descent_ends(ref, canRefill)) {
+		if (ref == kRefPop) {
+			uint32_t pr;
+			float pt;
+			ref = st.pop(pr, pt) ? pr : kRefDone;
+		}
+		if ((int)ref >= 0) {
+			QuadRecord n;
+			fetch_quad<true>(n, quads, ref, stagedNodes, nStaged);
+			const uint32_t r0 = __float_as_uint(n.rf.x), r1 = __float_as_uint(n.rf.y), r2 = __float_as_uint(n.rf.z), r3 = __float_as_uint(n.rf.w);
+			const bool p0 = overlaps(n.x01.x, n.x01.y, n.y01.x, n.y01.y, n.z01.x, n.z01.y);
+			const bool p1 = overlaps(n.x01.z, n.x01.w, n.y01.z, n.y01.w, n.z01.z, n.z01.w);
+			const bool p2 = overlaps(n.x23.x, n.x23.y, n.y23.x, n.y23.y, n.z23.x, n.z23.y);
+			const bool p3 = overlaps(n.x23.z, n.x23.w, n.y23.z, n.y23.w, n.z23.z, n.z23.w);
+			const lanemask h0 = lanes_where(p0), h1 = lanes_where(p1), h2 = lanes_where(p2), h3 = lanes_where(p3);
+			const lanemask any01 = h0 | h1, any012 = any01 | h2;
+			st.push3(h3 & any012, r3, 0.f, h2 & any01, r2, 0.f, h1 & h0, r1, 0.f);
+			ref = p0 ? r0 : p1 ? r1 : p2 ? r2 : p3 ? r3 : kRefPop;
+		}
+	}
+	if (ref_is_leaf(ref))
+		ref = leaf(ref) ? kRefDone : kRefPop;
+	return ref;
+}
+
+// ---- the ray queries' round ----------------------------------------------------------------------------------------------------
+
+// The descent of a ray: test_quad against `bound` (closest hit: the nearest accepted distance so far; any hit: tmax, which never
+// shrinks), in the reference's visit order with entry distances (!ANY) or in node order without (ANY: no entry is re-tested when
+// it is popped, and the set of leaves reached does not depend on the order, hip/traverse.hpp "Exactness").
+template <bool ANY, class CanRefill>
+__device__ __forceinline__ uint32_t ray_descent(const float4* quads, LdsStack<kQueryStackLds, !ANY>& st, const float4* stagedNodes, uint32_t nStaged, const RayConst& r, bool allRegular,
+                                                float bound, uint32_t ref, CanRefill canRefill) {
 	for (;;) {
+		// (descent_ends' test, written out: called as a function here it costs every ray kernel two vector registers, and
+		// k_query_hits<false> a wave per SIMD with them -- profiles/query_descent_refactor_isa.txt)
 		const uint32_t nTrav = (uint32_t)__popcll(lanes_traversing(ref));
 		if (nTrav == 0)
 			break;
@@ -147,37 +300,44 @@ __device__ __forceinline__ void q_traverse(const DevScene& sc, LdsStack<kQuerySt
 			uint32_t pr;
 			float pt;
 			if (st.pop(pr, pt)) {
-				if (pt < q.dist) // the pop-time half of Bbox.h:61 (any hit keeps no entry distance: -inf, always taken)
+				if (ANY || pt < bound) // the pop-time half of Bbox.h:61 (any hit keeps no entry distance: always taken)
 					ref = pr;
 			} else {
 				ref = kRefDone;
 			}
 		}
 		if ((int)ref >= 0) {
-			const QuadHits h = allRegular ? test_quad<true, !ANY, true>(quads, ref, r, q.dist, stagedNodes, nStaged) : test_quad<false, !ANY, true>(quads, ref, r, q.dist, stagedNodes, nStaged);
+			const QuadHits h = allRegular ? test_quad<true, !ANY, true>(quads, ref, r, bound, stagedNodes, nStaged) : test_quad<false, !ANY, true>(quads, ref, r, bound, stagedNodes, nStaged);
 			const lanemask any01 = h.hit[0] | h.hit[1], any012 = any01 | h.hit[2];
 			st.push3(h.hit[3] & any012, h.ref[3], h.t[3], h.hit[2] & any01, h.ref[2], h.t[2], h.hit[1] & h.hit[0], h.ref[1], h.t[1]);
 			ref = lane_in(h.hit[0]) ? h.ref[0] : lane_in(h.hit[1]) ? h.ref[1] : lane_in(h.hit[2]) ? h.ref[2] : lane_in(h.hit[3]) ? h.ref[3] : kRefPop;
 		}
 	}
+	return ref;
+}
+
+// One round of the ray queries and guide passes (`live`: the lane holds an item): the descent, then one leaf per lane that is at
+// one: bvh.h:129-140 (closest hit) / bvh.h:229-238 (any hit), primitives in array order.  The accept rules of these kernels are
+// the two in the leaf below.
+template <bool ANY, class CanRefill>
+__device__ __forceinline__ void q_traverse(const DevScene& sc, LdsStack<kQueryStackLds, !ANY>& st, const float4* stagedNodes, QueryRay& q, bool live, CanRefill canRefill) {
+	const uint32_t nStaged = sc.nStaged;
+	const float4* quads = pinned_quads(sc);
+	const bool allRegular = (__ballot(live && !q.regular) == 0ull);
+	const RayConst r = { mk3(q.ox, q.oy, q.oz), mk3(q.dx, q.dy, q.dz), mk3(q.ix, q.iy, q.iz), q.ix < 0, q.iy < 0, q.iz < 0 }; // bvh.h:120-121
+	uint32_t ref = ray_descent<ANY>(quads, st, stagedNodes, nStaged, r, allRegular, q.dist, q.ref, canRefill);
 	if (ref_is_leaf(ref)) {
-		const uint32_t off = ref & (kMaxPrimOffset - 1);
-		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-		bool found = false;
-		TriData tri = triangle_load(sc.tris, off);
-		for (uint32_t i = 0; i < cnt && !found; ++i) {
-			const TriData cur = tri; // the next primitive of the leaf is on its way while this one is tested
-			if (i + 1 < cnt)
-				tri = triangle_load(sc.tris, off + i + 1);
+		const bool found = leaf_prims<true>(sc.tris, ref, [&](const TriData& cur, int prim) {
 			const float t = triangle_test(cur, r);
-			if (ANY) {
-				found = (t > kEpsilon && ((q.dist - t) > kEpsilon)); // bvh.h:232-236
-			} else if (t > kEpsilon && t < q.dist && ((q.dist - t) > kEpsilon)) { // bvh.h:133-137
-				q.prim = (int)(off + i);
+			if (ANY)
+				return t > kEpsilon && ((q.dist - t) > kEpsilon); // bvh.h:232-236
+			if (t > kEpsilon && t < q.dist && ((q.dist - t) > kEpsilon)) { // bvh.h:133-137
+				q.prim = prim;
 				q.dist = t;
 				q.hitTri = true;
 			}
-		}
+			return false;
+		});
 		q.occluded = q.occluded || found;
 		ref = found ? kRefDone : kRefPop;
 	}

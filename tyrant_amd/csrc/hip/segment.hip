@@ -5,9 +5,10 @@
 //
 // One segment to a lane on a persistent grid, with the point queries' pieces (hip/query_common.hpp, hip/traverse.hpp): the
 // chunked ticket feed, the first nStaged quad records in LDS, the LdsStack with its private spill arrays, triangle_load, the
-// flat lane states (interior ref | leaf ref | kRefPop | kRefDone).  The descent is this unit's own, in the shape of n_traverse
-// (hip/nearest_common.hpp) and s_traverse (hip/sweep.hip): a quad step keys each of the four slots, orders them by key, descends
-// into the nearest and pushes the others farthest first; an entry is tested against the bound again when it is popped.
+// flat lane states (interior ref | leaf ref | kRefPop | kRefDone).  The descent is the keyed one of the point queries and the
+// sweeps (keyed_round, hip/query_common.hpp): a quad step keys each of the four slots, orders them by key, descends into the
+// nearest and pushes the others farthest first; an entry is tested against the bound again when it is popped.  This unit
+// supplies the key and what is done with a leaf.
 //
 // A slot's key is a binary32 lower bound of the squared distance between the segment and the slot's box, the larger of
 //   (a) the distance between the box and the segment's own axis-aligned box (the segment lies inside its box), and
@@ -27,6 +28,7 @@
 
 #include "device_common.hpp"
 #include "query_common.hpp"
+#include "vecmath64.hpp"
 
 namespace tyr {
 
@@ -42,18 +44,6 @@ constexpr double kSegInfD = __builtin_inf();
 
 // ---- the value of a (segment, triangle) pair: include/tyr_c.h "Closest-segment queries", operation by operation -------------
 
-struct d3 {
-	double x, y, z;
-};
-__device__ __forceinline__ d3 mk(double x, double y, double z) { return d3{ x, y, z }; }
-__device__ __forceinline__ d3 operator-(d3 a, d3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ double dotd(d3 a, d3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ d3 crossd(d3 a, d3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ double clamp01(double v) {
-	const double v1 = v > 0 ? v : 0.0;
-	return v1 < 1 ? v1 : 1.0;
-}
-
 struct SegValue {
 	double F; // +inf: the pair has no value (no finite input gives that)
 	double s;
@@ -64,14 +54,14 @@ struct SegValue {
 template <bool FULL>
 __device__ __forceinline__ SegValue segment_value(const TriData& td, d3 P0, d3 P1) {
 	// the corners tyr_triangle_bboxes bounds: vert and the binary32 sums vert + e1, vert + e2
-	const d3 A = mk((double)td.a.x, (double)td.a.y, (double)td.a.z);
-	const d3 B = mk((double)(td.a.x + td.a.w), (double)(td.a.y + td.b.x), (double)(td.a.z + td.b.y));
-	const d3 C = mk((double)(td.a.x + td.b.z), (double)(td.a.y + td.b.w), (double)(td.a.z + td.c.x));
+	const d3 A = mk3d((double)td.a.x, (double)td.a.y, (double)td.a.z);
+	const d3 B = mk3d((double)(td.a.x + td.a.w), (double)(td.a.y + td.b.x), (double)(td.a.z + td.b.y));
+	const d3 C = mk3d((double)(td.a.x + td.b.z), (double)(td.a.y + td.b.w), (double)(td.a.z + td.c.x));
 	const d3 e1 = B - A, e2 = C - A;
 	const d3 d = P1 - P0;
 	SegValue o_;
-	o_.F = kSegInfD, o_.s = 0.0, o_.feature = 0u, o_.region = 0u, o_.x = o_.y = mk(0.0, 0.0, 0.0);
-	auto at = [&](double s) { return mk(P0.x + s * d.x, P0.y + s * d.y, P0.z + s * d.z); };
+	o_.F = kSegInfD, o_.s = 0.0, o_.feature = 0u, o_.region = 0u, o_.x = o_.y = mk3d(0.0, 0.0, 0.0);
+	auto at = [&](double s) { return mk3d(P0.x + s * d.x, P0.y + s * d.y, P0.z + s * d.z); };
 	auto offer = [&](bool ok, double F, double s, uint32_t feature, uint32_t region, d3 x, d3 y) {
 		if (ok && F < o_.F) { // strict: of equal F the lower feature code stays
 			o_.F = F;
@@ -116,14 +106,14 @@ __device__ __forceinline__ SegValue segment_value(const TriData& td, d3 P0, d3 P
 		const double u1 = u > 0 ? u : 0.0, u2 = u1 < 1 ? u1 : 1.0;
 		const double rem = 1.0 - u2;
 		const double v1 = v > 0 ? v : 0.0, v2 = v1 < rem ? v1 : rem;
-		const d3 q = mk((ap.x - e1.x * u2) - e2.x * v2, (ap.y - e1.y * u2) - e2.y * v2, (ap.z - e1.z * u2) - e2.z * v2);
+		const d3 q = mk3d((ap.x - e1.x * u2) - e2.x * v2, (ap.y - e1.y * u2) - e2.y * v2, (ap.z - e1.z * u2) - e2.z * v2);
 		const double F = dotd(q, q);
-		d3 px = mk(0.0, 0.0, 0.0), py = px;
+		d3 px = mk3d(0.0, 0.0, 0.0), py = px;
 		uint32_t region = 0u;
 		if (FULL) {
 			region = rule == 3u ? 4u : rule == 4u ? 3u : rule == 7u ? 0u : rule; // vertices 1 2 3, edges 4 5 6, the face 0
 			px = at(s);
-			py = mk((A.x + e1.x * u2) + e2.x * v2, (A.y + e1.y * u2) + e2.y * v2, (A.z + e1.z * u2) + e2.z * v2);
+			py = mk3d((A.x + e1.x * u2) + e2.x * v2, (A.y + e1.y * u2) + e2.y * v2, (A.z + e1.z * u2) + e2.z * v2);
 		}
 		offer(true, F, s, feature, region, px, py);
 	};
@@ -152,7 +142,7 @@ __device__ __forceinline__ SegValue segment_value(const TriData& td, d3 P0, d3 P
 				t = tn / ee;
 		}
 		const d3 x = at(s);
-		const d3 y = mk(Q0.x + e.x * t, Q0.y + e.y * t, Q0.z + e.z * t);
+		const d3 y = mk3d(Q0.x + e.x * t, Q0.y + e.y * t, Q0.z + e.z * t);
 		const d3 xy = x - y;
 		offer(true, dotd(xy, xy), s, feature, (t > 0.0 && t < 1.0) ? code : (t >= 1.0 ? code1 : code0), x, y);
 	};
@@ -207,15 +197,6 @@ __device__ __forceinline__ float segment_key(const SegLane& q, float lox, float 
 	return (lox < kSegInf && !(key > q.best)) ? key : kSegInf;
 }
 
-#define TYR_SEG_SWAP(a, b)                             \
-	{                                                  \
-		const bool s_ = k##a > k##b;                   \
-		const float tk_ = s_ ? k##b : k##a;            \
-		const uint32_t tr_ = s_ ? r##b : r##a;         \
-		k##b = s_ ? k##a : k##b, r##b = s_ ? r##a : r##b; \
-		k##a = tk_, r##a = tr_;                        \
-	}
-
 // a triangle of a reached leaf: the smallest pair (F32, index) so far stays; F32 at the bound is no winner
 __device__ __forceinline__ void segment_take(SegLane& q, double F, int prim) {
 	const float F32 = (float)F;
@@ -225,89 +206,21 @@ __device__ __forceinline__ void segment_take(SegLane& q, double F, int prim) {
 	}
 }
 
-// One round of the wave's traversal, the shape of n_traverse (hip/nearest_common.hpp): the descent, one pop attempt and one quad
-// step per lane per trip, until no lane descends -- or fewer than kQueryMinTraversing do and a lane is at a leaf or
-// `canRefill()` says enough lanes could start new work; then one leaf per lane that is at one, primitives in array order.
+// One round of the wave's traversal: the keyed descent (keyed_round, hip/query_common.hpp) on segment_key against the lane's
+// `best`, then one leaf per lane that is at one, primitives in array order.
 template <class CanRefill>
 __device__ __forceinline__ void g_traverse(const DevScene& sc, LdsStack<kQueryStackLds, true>& st, const float4* stagedNodes, SegLane& q, CanRefill canRefill) {
-	const uint32_t nStaged = sc.nStaged;
-	// (the quad array's address as an opaque global-memory pointer: see q_traverse)
-	auto held = (const __attribute__((address_space(1))) float4*)sc.quads;
-	__asm__ volatile("" : "+s"(held));
-	const float4* quads = (const float4*)held;
-	uint32_t ref = q.ref;
-	for (;;) {
-		const uint32_t nTrav = (uint32_t)__popcll(lanes_traversing(ref));
-		if (nTrav == 0)
-			break;
-		if (nTrav < kQueryMinTraversing) {
-			const bool anyLeaf = lanes_at_leaf(ref) != 0ull;
-			if (anyLeaf || canRefill(ref))
-				break;
-		}
-		if (ref == kRefPop) {
-			uint32_t pr;
-			float pk;
-			if (st.pop(pr, pk)) {
-				if (!(pk > q.best)) // the entry's key against what has been found since it was pushed
-					ref = pr;
-			} else {
-				ref = kRefDone;
-			}
-		}
-		if ((int)ref >= 0) {
-			const uint32_t idx = ref & kQuadIndexMask;
-			float4 x01, x23, y01, y23, z01, z23, rf;
-			if (idx < nStaged) { // (explicit LDS pointers and a tail of its own: see test_quad)
-#if defined(__HIP_DEVICE_COMPILE__)
-				typedef __attribute__((address_space(3))) const float4* lds_f4;
-				const lds_f4 c = (lds_f4)stagedNodes + idx;
-#else
-				const float4* c = stagedNodes + idx; // host pass of the same source: never executed
-#endif
-				x01 = c[0 * kStagedNodes], x23 = c[1 * kStagedNodes], y01 = c[2 * kStagedNodes], y23 = c[3 * kStagedNodes];
-				z01 = c[4 * kStagedNodes], z23 = c[5 * kStagedNodes], rf = c[6 * kStagedNodes];
-				__asm__ volatile("" : "+v"(rf.x));
-			} else {
-				const float4* n = quads + 8 * idx;
-				x01 = n[0], x23 = n[1], y01 = n[2], y23 = n[3], z01 = n[4], z23 = n[5], rf = n[6];
-			}
-			uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
-			float k0 = segment_key(q, x01.x, x01.y, y01.x, y01.y, z01.x, z01.y);
-			float k1 = segment_key(q, x01.z, x01.w, y01.z, y01.w, z01.z, z01.w);
-			float k2 = segment_key(q, x23.x, x23.y, y23.x, y23.y, z23.x, z23.y);
-			float k3 = segment_key(q, x23.z, x23.w, y23.z, y23.w, z23.z, z23.w);
-			// the four by key, nearest first: a sorting network of selects (skipped slots carry +inf and end up last)
-			TYR_SEG_SWAP(0, 1)
-			TYR_SEG_SWAP(2, 3)
-			TYR_SEG_SWAP(0, 2)
-			TYR_SEG_SWAP(1, 3)
-			TYR_SEG_SWAP(1, 2)
-			st.push3(lanes_where(k3 < kSegInf), r3, k3, lanes_where(k2 < kSegInf), r2, k2, lanes_where(k1 < kSegInf), r1, k1);
-			ref = k0 < kSegInf ? r0 : kRefPop;
-		}
-	}
-	if (ref_is_leaf(ref)) {
-		const uint32_t off = ref & (kMaxPrimOffset - 1);
-		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-		const d3 P0 = mk((double)q.px, (double)q.py, (double)q.pz), P1 = mk((double)q.qx, (double)q.qy, (double)q.qz);
-		TriData tri = triangle_load(sc.tris, off);
-		for (uint32_t i = 0; i < cnt; ++i) {
-			const TriData cur = tri; // the next primitive of the leaf is on its way while this one is evaluated
-			if (i + 1 < cnt)
-				tri = triangle_load(sc.tris, off + i + 1);
-			// the triangle's own three-corner box against the bound, as a slot's: the binary64 evaluation only behind it
-			const float bx = cur.a.x + cur.a.w, by = cur.a.y + cur.b.x, bz = cur.a.z + cur.b.y;
-			const float cx = cur.a.x + cur.b.z, cy = cur.a.y + cur.b.w, cz = cur.a.z + cur.c.x;
-			const float key = segment_key(q, __builtin_fminf(__builtin_fminf(cur.a.x, bx), cx), __builtin_fmaxf(__builtin_fmaxf(cur.a.x, bx), cx),
-			                              __builtin_fminf(__builtin_fminf(cur.a.y, by), cy), __builtin_fmaxf(__builtin_fmaxf(cur.a.y, by), cy),
-			                              __builtin_fminf(__builtin_fminf(cur.a.z, bz), cz), __builtin_fmaxf(__builtin_fmaxf(cur.a.z, bz), cz));
-			if (key < kSegInf)
-				segment_take(q, segment_value<false>(cur, P0, P1).F, (int)(off + i));
-		}
-		ref = kRefPop;
-	}
-	q.ref = ref;
+	q.ref = keyed_round(
+		sc, st, stagedNodes, q.ref, q.best, canRefill, [&](float lox, float hix, float loy, float hiy, float loz, float hiz) { return segment_key(q, lox, hix, loy, hiy, loz, hiz); },
+		[&](uint32_t leaf) {
+			const d3 P0 = mk3d((double)q.px, (double)q.py, (double)q.pz), P1 = mk3d((double)q.qx, (double)q.qy, (double)q.qz);
+			leaf_prims<false>(sc.tris, leaf, [&](const TriData& cur, int prim) {
+				// the triangle's own three-corner box against the bound, as a slot's: the binary64 evaluation only behind it
+				const CornerBox b = tri_corner_box(cur);
+				if (segment_key(q, b.lox, b.hix, b.loy, b.hiy, b.loz, b.hiz) < kSegInf)
+					segment_take(q, segment_value<false>(cur, P0, P1).F, prim);
+			});
+		});
 }
 
 } // namespace
@@ -335,7 +248,7 @@ __global__ void __launch_bounds__(kBlock, 3) k_query_segment(const SegmentParams
 		uint32_t feature = 0u, region = 0u;
 		float xx = q.px, xy = q.py, xz = q.pz, yx = q.px, yy = q.py, yz = q.pz;
 		if (q.prim >= 0) {
-			const d3 A0 = mk((double)q.px, (double)q.py, (double)q.pz), A1 = mk((double)q.qx, (double)q.qy, (double)q.qz);
+			const d3 A0 = mk3d((double)q.px, (double)q.py, (double)q.pz), A1 = mk3d((double)q.qx, (double)q.qy, (double)q.qz);
 			const SegValue w = segment_value<true>(triangle_load(sc.tris, (uint32_t)q.prim), A0, A1); // the winner's operations once more: the same value
 			dist2 = (float)w.F, s = (float)w.s;
 			feature = w.feature, region = w.region;

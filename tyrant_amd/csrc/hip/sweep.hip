@@ -5,9 +5,10 @@
 //
 // One sweep to a lane on a persistent grid, with the point queries' pieces (hip/query_common.hpp, hip/traverse.hpp): the chunked
 // ticket feed, the first nStaged quad records in LDS, the LdsStack with its private spill arrays, triangle_load, the flat lane
-// states (interior ref | leaf ref | kRefPop | kRefDone).  The descent is this unit's own, in the shape of n_traverse
-// (hip/nearest_common.hpp): a quad step keys each of the four slots, orders them by key, descends into the nearest and pushes
-// the others farthest first; an entry is tested against the bound again when it is popped.
+// states (interior ref | leaf ref | kRefPop | kRefDone).  The descent is the keyed one the point queries use (keyed_round,
+// hip/query_common.hpp): a quad step keys each of the four slots, orders them by key, descends into the nearest and pushes
+// the others farthest first; an entry is tested against the bound again when it is popped.  This unit supplies the key and
+// what is done with a leaf.
 //
 // A slot's key is the parameter at which the segment enters the slot's box inflated by r on every axis, from a binary32 slab
 // test.  At a contact the centre is within r of a point of the box, so it is inside the inflated box: the entry parameter is
@@ -22,6 +23,7 @@
 
 #include "device_common.hpp"
 #include "query_common.hpp"
+#include "vecmath64.hpp"
 
 namespace tyr {
 
@@ -34,14 +36,6 @@ constexpr double kSweepInfD = __builtin_inf();
 
 // ---- the value of a (sweep, triangle) pair: include/tyr_c.h "Swept-sphere queries", operation by operation -------------------
 
-struct d3 {
-	double x, y, z;
-};
-__device__ __forceinline__ d3 mk(double x, double y, double z) { return d3{ x, y, z }; }
-__device__ __forceinline__ d3 operator-(d3 a, d3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ double dotd(d3 a, d3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ d3 crossd(d3 a, d3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-
 struct SweepValue {
 	double t; // +inf: the pair has no value
 	uint32_t region;
@@ -51,15 +45,15 @@ struct SweepValue {
 template <bool FULL>
 __device__ __forceinline__ SweepValue sweep_value(const TriData& td, d3 o, d3 d, double r, double tmax) {
 	// the corners tyr_triangle_bboxes bounds: vert and the binary32 sums vert + e1, vert + e2
-	const d3 A = mk((double)td.a.x, (double)td.a.y, (double)td.a.z);
-	const d3 B = mk((double)(td.a.x + td.a.w), (double)(td.a.y + td.b.x), (double)(td.a.z + td.b.y));
-	const d3 C = mk((double)(td.a.x + td.b.z), (double)(td.a.y + td.b.w), (double)(td.a.z + td.c.x));
+	const d3 A = mk3d((double)td.a.x, (double)td.a.y, (double)td.a.z);
+	const d3 B = mk3d((double)(td.a.x + td.a.w), (double)(td.a.y + td.b.x), (double)(td.a.z + td.b.y));
+	const d3 C = mk3d((double)(td.a.x + td.b.z), (double)(td.a.y + td.b.w), (double)(td.a.z + td.c.x));
 	const d3 e1 = B - A, e2 = C - A;
 	const d3 ap = o - A;
 	const double rr = r * r;
 	const double dd = dotd(d, d);
 	SweepValue o_;
-	o_.t = kSweepInfD, o_.region = 0u, o_.c = mk(0.0, 0.0, 0.0);
+	o_.t = kSweepInfD, o_.region = 0u, o_.c = mk3d(0.0, 0.0, 0.0);
 	auto offer = [&](bool ok, double t, uint32_t code, d3 pt) {
 		if (ok && t >= 0.0 && t <= tmax && t < o_.t) { // strict: of equal t the lower region code stays
 			o_.t = t;
@@ -79,7 +73,7 @@ __device__ __forceinline__ SweepValue sweep_value(const TriData& td, d3 o, d3 d,
 		const double rl = r * ln;
 		const double t = (ah - rl) / (-sdn);
 		const double k = (s * r) / ln;
-		const d3 q = mk((o.x + t * d.x) - n.x * k, (o.y + t * d.y) - n.y * k, (o.z + t * d.z) - n.z * k);
+		const d3 q = mk3d((o.x + t * d.x) - n.x * k, (o.y + t * d.y) - n.y * k, (o.z + t * d.z) - n.z * k);
 		const d3 w = q - A;
 		const double bv = dotd(crossd(w, e2), n), bw = dotd(crossd(e1, w), n);
 		offer(nn > 0.0 && sdn < 0.0 && ah > rl && bv >= 0.0 && bw >= 0.0 && (bv + bw) <= nn, t, 0u, q);
@@ -106,7 +100,7 @@ __device__ __forceinline__ SweepValue sweep_value(const TriData& td, d3 o, d3 d,
 		const double disc = b * b - a * c;
 		const double t = (-b - __builtin_sqrt(disc)) / a;
 		const double sg = (me + t * de) / ee;
-		offer(ee > 0.0 && a > 0.0 && b < 0.0 && c > 0.0 && disc >= 0.0 && sg >= 0.0 && sg <= 1.0, t, code, mk(P0.x + e.x * sg, P0.y + e.y * sg, P0.z + e.z * sg));
+		offer(ee > 0.0 && a > 0.0 && b < 0.0 && c > 0.0 && disc >= 0.0 && sg >= 0.0 && sg <= 1.0, t, code, mk3d(P0.x + e.x * sg, P0.y + e.y * sg, P0.z + e.z * sg));
 	};
 	edge(4u, A, e1, ap);
 	edge(5u, A, e2, ap);
@@ -135,12 +129,12 @@ __device__ __forceinline__ SweepValue sweep_value(const TriData& td, d3 o, d3 d,
 		const double u1 = u > 0 ? u : 0.0, u2 = u1 < 1 ? u1 : 1.0;
 		const double rem = 1.0 - u2;
 		const double v1 = v > 0 ? v : 0.0, v2 = v1 < rem ? v1 : rem;
-		const d3 q = mk((ap.x - e1.x * u2) - e2.x * v2, (ap.y - e1.y * u2) - e2.y * v2, (ap.z - e1.z * u2) - e2.z * v2);
+		const d3 q = mk3d((ap.x - e1.x * u2) - e2.x * v2, (ap.y - e1.y * u2) - e2.y * v2, (ap.z - e1.z * u2) - e2.z * v2);
 		if (dotd(q, q) <= rr) {
 			o_.t = 0.0;
 			if (FULL) {
 				o_.region = rule == 3u ? 4u : rule == 4u ? 3u : rule == 7u ? 0u : rule; // vertices 1 2 3, edges 4 5 6, the face 0
-				o_.c = mk((A.x + e1.x * u2) + e2.x * v2, (A.y + e1.y * u2) + e2.y * v2, (A.z + e1.z * u2) + e2.z * v2);
+				o_.c = mk3d((A.x + e1.x * u2) + e2.x * v2, (A.y + e1.y * u2) + e2.y * v2, (A.z + e1.z * u2) + e2.z * v2);
 			}
 		}
 	}
@@ -190,15 +184,6 @@ __device__ __forceinline__ float sweep_key(const SweepLane& q, float lox, float 
 	return (lox < kSweepInf && tNear <= tFar && tFar >= 0.f && tNear <= q.best) ? tNear : kSweepInf;
 }
 
-#define TYR_SWEEP_SWAP(a, b)                           \
-	{                                                  \
-		const bool s_ = k##a > k##b;                   \
-		const float tk_ = s_ ? k##b : k##a;            \
-		const uint32_t tr_ = s_ ? r##b : r##a;         \
-		k##b = s_ ? k##a : k##b, r##b = s_ ? r##a : r##b; \
-		k##a = tk_, r##a = tr_;                        \
-	}
-
 // a triangle of a reached leaf: the smallest pair (t32, index) so far stays
 __device__ __forceinline__ void sweep_take(SweepLane& q, double t, int prim) {
 	if (t < kSweepInfD) {
@@ -210,89 +195,21 @@ __device__ __forceinline__ void sweep_take(SweepLane& q, double t, int prim) {
 	}
 }
 
-// One round of the wave's traversal, the shape of n_traverse (hip/nearest_common.hpp): the descent, one pop attempt and one quad
-// step per lane per trip, until no lane descends -- or fewer than kQueryMinTraversing do and a lane is at a leaf or
-// `canRefill()` says enough lanes could start new work; then one leaf per lane that is at one, primitives in array order.
+// One round of the wave's traversal: the keyed descent (keyed_round, hip/query_common.hpp) on sweep_key against the lane's
+// `best`, then one leaf per lane that is at one, primitives in array order.
 template <class CanRefill>
 __device__ __forceinline__ void s_traverse(const DevScene& sc, LdsStack<kQueryStackLds, true>& st, const float4* stagedNodes, SweepLane& q, CanRefill canRefill) {
-	const uint32_t nStaged = sc.nStaged;
-	// (the quad array's address as an opaque global-memory pointer: see q_traverse)
-	auto held = (const __attribute__((address_space(1))) float4*)sc.quads;
-	__asm__ volatile("" : "+s"(held));
-	const float4* quads = (const float4*)held;
-	uint32_t ref = q.ref;
-	for (;;) {
-		const uint32_t nTrav = (uint32_t)__popcll(lanes_traversing(ref));
-		if (nTrav == 0)
-			break;
-		if (nTrav < kQueryMinTraversing) {
-			const bool anyLeaf = lanes_at_leaf(ref) != 0ull;
-			if (anyLeaf || canRefill(ref))
-				break;
-		}
-		if (ref == kRefPop) {
-			uint32_t pr;
-			float pk;
-			if (st.pop(pr, pk)) {
-				if (pk <= q.best) // the entry's key against what has been found since it was pushed
-					ref = pr;
-			} else {
-				ref = kRefDone;
-			}
-		}
-		if ((int)ref >= 0) {
-			const uint32_t idx = ref & kQuadIndexMask;
-			float4 x01, x23, y01, y23, z01, z23, rf;
-			if (idx < nStaged) { // (explicit LDS pointers and a tail of its own: see test_quad)
-#if defined(__HIP_DEVICE_COMPILE__)
-				typedef __attribute__((address_space(3))) const float4* lds_f4;
-				const lds_f4 c = (lds_f4)stagedNodes + idx;
-#else
-				const float4* c = stagedNodes + idx; // host pass of the same source: never executed
-#endif
-				x01 = c[0 * kStagedNodes], x23 = c[1 * kStagedNodes], y01 = c[2 * kStagedNodes], y23 = c[3 * kStagedNodes];
-				z01 = c[4 * kStagedNodes], z23 = c[5 * kStagedNodes], rf = c[6 * kStagedNodes];
-				__asm__ volatile("" : "+v"(rf.x));
-			} else {
-				const float4* n = quads + 8 * idx;
-				x01 = n[0], x23 = n[1], y01 = n[2], y23 = n[3], z01 = n[4], z23 = n[5], rf = n[6];
-			}
-			uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
-			float k0 = sweep_key(q, x01.x, x01.y, y01.x, y01.y, z01.x, z01.y);
-			float k1 = sweep_key(q, x01.z, x01.w, y01.z, y01.w, z01.z, z01.w);
-			float k2 = sweep_key(q, x23.x, x23.y, y23.x, y23.y, z23.x, z23.y);
-			float k3 = sweep_key(q, x23.z, x23.w, y23.z, y23.w, z23.z, z23.w);
-			// the four by key, nearest first: a sorting network of selects (skipped slots carry +inf and end up last)
-			TYR_SWEEP_SWAP(0, 1)
-			TYR_SWEEP_SWAP(2, 3)
-			TYR_SWEEP_SWAP(0, 2)
-			TYR_SWEEP_SWAP(1, 3)
-			TYR_SWEEP_SWAP(1, 2)
-			st.push3(lanes_where(k3 < kSweepInf), r3, k3, lanes_where(k2 < kSweepInf), r2, k2, lanes_where(k1 < kSweepInf), r1, k1);
-			ref = k0 < kSweepInf ? r0 : kRefPop;
-		}
-	}
-	if (ref_is_leaf(ref)) {
-		const uint32_t off = ref & (kMaxPrimOffset - 1);
-		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-		const d3 o = mk((double)q.ox, (double)q.oy, (double)q.oz), d = mk((double)q.dx, (double)q.dy, (double)q.dz);
-		TriData tri = triangle_load(sc.tris, off);
-		for (uint32_t i = 0; i < cnt; ++i) {
-			const TriData cur = tri; // the next primitive of the leaf is on its way while this one is evaluated
-			if (i + 1 < cnt)
-				tri = triangle_load(sc.tris, off + i + 1);
-			// the triangle's own three-corner box against the bound, as a slot's: the binary64 evaluation only behind it
-			const float bx = cur.a.x + cur.a.w, by = cur.a.y + cur.b.x, bz = cur.a.z + cur.b.y;
-			const float cx = cur.a.x + cur.b.z, cy = cur.a.y + cur.b.w, cz = cur.a.z + cur.c.x;
-			const float key = sweep_key(q, __builtin_fminf(__builtin_fminf(cur.a.x, bx), cx), __builtin_fmaxf(__builtin_fmaxf(cur.a.x, bx), cx),
-			                            __builtin_fminf(__builtin_fminf(cur.a.y, by), cy), __builtin_fmaxf(__builtin_fmaxf(cur.a.y, by), cy),
-			                            __builtin_fminf(__builtin_fminf(cur.a.z, bz), cz), __builtin_fmaxf(__builtin_fmaxf(cur.a.z, bz), cz));
-			if (key < kSweepInf)
-				sweep_take(q, sweep_value<false>(cur, o, d, (double)q.r, (double)q.tmax).t, (int)(off + i));
-		}
-		ref = kRefPop;
-	}
-	q.ref = ref;
+	q.ref = keyed_round(
+		sc, st, stagedNodes, q.ref, q.best, canRefill, [&](float lox, float hix, float loy, float hiy, float loz, float hiz) { return sweep_key(q, lox, hix, loy, hiy, loz, hiz); },
+		[&](uint32_t leaf) {
+			const d3 o = mk3d((double)q.ox, (double)q.oy, (double)q.oz), d = mk3d((double)q.dx, (double)q.dy, (double)q.dz);
+			leaf_prims<false>(sc.tris, leaf, [&](const TriData& cur, int prim) {
+				// the triangle's own three-corner box against the bound, as a slot's: the binary64 evaluation only behind it
+				const CornerBox b = tri_corner_box(cur);
+				if (sweep_key(q, b.lox, b.hix, b.loy, b.hiy, b.loz, b.hiz) < kSweepInf)
+					sweep_take(q, sweep_value<false>(cur, o, d, (double)q.r, (double)q.tmax).t, prim);
+			});
+		});
 }
 
 } // namespace
@@ -315,7 +232,7 @@ __global__ void __launch_bounds__(kBlock, 3) k_query_sweep(const SweepParams P0)
 	auto finish = [&]() {
 		const SweepParams& P = kernarg_view<SweepParams>(); // (read where it lies: not held in scalar registers through the descent)
 		const size_t i = item;
-		const d3 o = mk((double)q.ox, (double)q.oy, (double)q.oz), d = mk((double)q.dx, (double)q.dy, (double)q.dz);
+		const d3 o = mk3d((double)q.ox, (double)q.oy, (double)q.oz), d = mk3d((double)q.dx, (double)q.dy, (double)q.dz);
 		float t = valid ? q.tmax : kSweepInf;
 		uint32_t region = 0u;
 		// none: the end of the path; invalid: the origin as given
@@ -327,7 +244,7 @@ __global__ void __launch_bounds__(kBlock, 3) k_query_sweep(const SweepParams P0)
 		float px = cx, py = cy, pz = cz, nx = 0.f, ny = 0.f, nz = 0.f;
 		if (q.prim >= 0) {
 			const SweepValue w = sweep_value<true>(triangle_load(sc.tris, (uint32_t)q.prim), o, d, (double)q.r, (double)q.tmax); // the winner's operations once more: the same value
-			const d3 c = mk(o.x + w.t * d.x, o.y + w.t * d.y, o.z + w.t * d.z);
+			const d3 c = mk3d(o.x + w.t * d.x, o.y + w.t * d.y, o.z + w.t * d.z);
 			const double r = (double)q.r;
 			t = (float)w.t;
 			region = w.region;

@@ -580,6 +580,38 @@ struct QuadHits { // in visit order (ORDERED) or in node order (not ORDERED; qua
 	lanemask hit[4];
 };
 
+// A quad record's seven vectors: the boxes of slots 0 1 / 2 3 slab-major, and the four slots' references.
+struct QuadRecord {
+	float4 x01, x23, y01, y23, z01, z23, rf;
+};
+
+// The one fetch of an interior reference's record, for every descent on the quad tree: from the block's LDS copy of the
+// tree's top (STAGED and index < nStaged; vector v of node n at staged[v * STRIDE + n], q_stage_nodes and k_trace_flat fill
+// it) or from the quad array.  (The record comes back through a reference: returned by value, k_trace_flat's listing moved by
+// one instruction and a register renaming -- profiles/query_descent_refactor_isa.txt.)
+template <bool STAGED, int STRIDE = (int)kStagedNodes>
+__device__ __forceinline__ void fetch_quad(QuadRecord& n, const float4* __restrict__ quads, uint32_t ref, const float4* staged, uint32_t nStaged) {
+	const uint32_t idx = ref & kQuadIndexMask;
+	const float4* q = quads + 8 * idx;
+	if (STAGED && idx < nStaged) {
+		// an explicit LDS pointer: as a generic pointer the compiler selected between the two bases and issued
+		// 28 flat_load_dword per node
+#if defined(__HIP_DEVICE_COMPILE__)
+		typedef __attribute__((address_space(3))) const float4* lds_f4;
+		const lds_f4 c = (lds_f4)staged + idx;
+#else
+		const float4* c = staged + idx; // host pass of the same source: never executed
+#endif
+		n.x01 = c[0 * STRIDE], n.x23 = c[1 * STRIDE], n.y01 = c[2 * STRIDE], n.y23 = c[3 * STRIDE];
+		n.z01 = c[4 * STRIDE], n.z23 = c[5 * STRIDE], n.rf = c[6 * STRIDE];
+		// keeps this tail different from the global branch's: otherwise the two sets of loads are merged into
+		// loads through one generic pointer (flat_load_dword x 28)
+		__asm__ volatile("" : "+v"(n.rf.x));
+	} else {
+		n.x01 = q[0], n.x23 = q[1], n.y01 = q[2], n.y23 = q[3], n.z01 = q[4], n.z23 = q[5], n.rf = q[6];
+	}
+}
+
 template <bool FAST>
 __device__ __forceinline__ lanemask slab_any(const RayConst& r, float lox, float hix, float loy, float hiy, float loz, float hiz, float lowest, float& tOut) {
 	if (FAST)
@@ -594,27 +626,10 @@ __device__ __forceinline__ lanemask slab_any(const RayConst& r, float lox, float
 // k_trace_flat's descent, closest hit included, pushes each slot straight to its place).
 template <bool FAST, bool ORDERED, bool STAGED = false, int STAGE_STRIDE = (int)kStagedNodes>
 __device__ __forceinline__ QuadHits test_quad(const float4* __restrict__ quads, uint32_t ref, const RayConst& r, float dist, const float4* staged = nullptr, uint32_t nStaged = 0) {
-	const uint32_t idx = ref & kQuadIndexMask;
-	const float4* q = quads + 8 * idx;
 	const uint32_t meta = ref >> kQuadOrderShift; // bit 31 of an interior reference is clear
-	float4 x01, x23, y01, y23, z01, z23, rf;
-	if (STAGED && idx < nStaged) {
-		// an explicit LDS pointer: as a generic pointer the compiler selected between the two bases and issued
-		// 28 flat_load_dword per node
-#if defined(__HIP_DEVICE_COMPILE__)
-		typedef __attribute__((address_space(3))) const float4* lds_f4;
-		const lds_f4 c = (lds_f4)staged + idx;
-#else
-		const float4* c = staged + idx; // host pass of the same source: never executed
-#endif
-		x01 = c[0 * STAGE_STRIDE], x23 = c[1 * STAGE_STRIDE], y01 = c[2 * STAGE_STRIDE], y23 = c[3 * STAGE_STRIDE];
-		z01 = c[4 * STAGE_STRIDE], z23 = c[5 * STAGE_STRIDE], rf = c[6 * STAGE_STRIDE];
-		// keeps this tail different from the global branch's: otherwise the two sets of loads are merged into
-		// loads through one generic pointer (flat_load_dword x 28)
-		__asm__ volatile("" : "+v"(rf.x));
-	} else {
-		x01 = q[0], x23 = q[1], y01 = q[2], y23 = q[3], z01 = q[4], z23 = q[5], rf = q[6];
-	}
+	QuadRecord n;
+	fetch_quad<STAGED, STAGE_STRIDE>(n, quads, ref, staged, nStaged);
+	const float4 x01 = n.x01, x23 = n.x23, y01 = n.y01, y23 = n.y23, z01 = n.z01, z23 = n.z23, rf = n.rf;
 	const uint32_t r0 = __float_as_uint(rf.x), r1 = __float_as_uint(rf.y), r2 = __float_as_uint(rf.z), r3 = __float_as_uint(rf.w);
 	float t0, t1, t2, t3;
 	const lanemask H0 = slab_any<FAST>(r, x01.x, x01.y, y01.x, y01.y, z01.x, z01.y, dist, t0);

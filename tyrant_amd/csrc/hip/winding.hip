@@ -5,28 +5,19 @@
 #include "winding.hpp"
 
 #include "detmath.hpp"
+#include "vecmath64.hpp"
 
 namespace tyr {
 namespace {
 
 constexpr int kB = 256;
 
-struct d3 {
-	double x, y, z;
-};
-__device__ __forceinline__ d3 mk(double x, double y, double z) { return d3{ x, y, z }; }
-__device__ __forceinline__ d3 operator+(d3 a, d3 b) { return mk(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ d3 operator-(d3 a, d3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ d3 operator*(double s, d3 a) { return mk(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ double dotd(d3 a, d3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ d3 crossd(d3 a, d3 b) { return mk(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-
 // a triangle record of the ctx (bvh_layout.cpp "triangles"), widened
 __device__ __forceinline__ void load_tri(const float4* __restrict__ tris, uint32_t t, d3& v, d3& e1, d3& e2) {
 	const float4 q0 = tris[3 * (size_t)t + 0], q1 = tris[3 * (size_t)t + 1], q2 = tris[3 * (size_t)t + 2];
-	v = mk((double)q0.x, (double)q0.y, (double)q0.z);
-	e1 = mk((double)q0.w, (double)q1.x, (double)q1.y);
-	e2 = mk((double)q1.z, (double)q1.w, (double)q2.x);
+	v = mk3d((double)q0.x, (double)q0.y, (double)q0.z);
+	e1 = mk3d((double)q0.w, (double)q1.x, (double)q1.y);
+	e2 = mk3d((double)q1.z, (double)q1.w, (double)q2.x);
 }
 
 // ---- the moment tree -------------------------------------------------------------------------------------------------------
@@ -53,7 +44,7 @@ __device__ __forceinline__ Moments get_moments(const unsigned long long* m) {
 #pragma unroll
 	for (int k = 0; k < 7; ++k)
 		w[k] = __longlong_as_double((long long)__hip_atomic_load(m + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-	return Moments{ mk(w[0], w[1], w[2]), w[3], mk(w[4], w[5], w[6]) };
+	return Moments{ mk3d(w[0], w[1], w[2]), w[3], mk3d(w[4], w[5], w[6]) };
 }
 
 __global__ void __launch_bounds__(kB) k_winding_parents(WindingBuildArgs A) {
@@ -80,15 +71,13 @@ __device__ __forceinline__ uint32_t skip_of(const WindingBuildArgs& A, int i) {
 	return (uint32_t)A.nNodes;
 }
 
-__device__ __forceinline__ double max_second(double a, double b) { return b > a ? b : a; }
-
 // node i's record from its moments and its box
 __device__ __forceinline__ void write_node(const WindingBuildArgs& A, int i, const tyr_bvh_node& nd, const Moments& m) {
-	const d3 lo = mk((double)nd.bbox.bounds[0][0], (double)nd.bbox.bounds[0][1], (double)nd.bbox.bounds[0][2]);
-	const d3 hi = mk((double)nd.bbox.bounds[1][0], (double)nd.bbox.bounds[1][1], (double)nd.bbox.bounds[1][2]);
-	const d3 p = m.S > 0.0 ? mk(m.M.x / m.S, m.M.y / m.S, m.M.z / m.S) : 0.5 * (lo + hi);
+	const d3 lo = mk3d((double)nd.bbox.bounds[0][0], (double)nd.bbox.bounds[0][1], (double)nd.bbox.bounds[0][2]);
+	const d3 hi = mk3d((double)nd.bbox.bounds[1][0], (double)nd.bbox.bounds[1][1], (double)nd.bbox.bounds[1][2]);
+	const d3 p = m.S > 0.0 ? mk3d(m.M.x / m.S, m.M.y / m.S, m.M.z / m.S) : 0.5 * (lo + hi);
 	const d3 dl = lo - p, dh = hi - p;
-	const double r2 = (max_second(dl.x * dl.x, dh.x * dh.x) + max_second(dl.y * dl.y, dh.y * dh.y)) + max_second(dl.z * dl.z, dh.z * dh.z);
+	const double r2 = (maxd(dl.x * dl.x, dh.x * dh.x) + maxd(dl.y * dl.y, dh.y * dh.y)) + maxd(dl.z * dl.z, dh.z * dh.z);
 	WindingNode o;
 	o.p[0] = p.x, o.p[1] = p.y, o.p[2] = p.z;
 	o.N[0] = m.N.x, o.N[1] = m.N.y, o.N[2] = m.N.z;
@@ -107,7 +96,7 @@ __global__ void __launch_bounds__(kB) k_winding_moments(WindingBuildArgs A) {
 	tyr_bvh_node nd = A.src[i];
 	if (nd.primitiveCount == 0)
 		return;
-	Moments m{ mk(0.0, 0.0, 0.0), 0.0, mk(0.0, 0.0, 0.0) };
+	Moments m{ mk3d(0.0, 0.0, 0.0), 0.0, mk3d(0.0, 0.0, 0.0) };
 	if (nd.offset >= 0 && (uint32_t)nd.offset + nd.primitiveCount <= A.nPrims) {
 		for (uint32_t t = (uint32_t)nd.offset; t < (uint32_t)nd.offset + nd.primitiveCount; ++t) {
 			d3 v, e1, e2;
@@ -115,7 +104,7 @@ __global__ void __launch_bounds__(kB) k_winding_moments(WindingBuildArgs A) {
 			const d3 n = 0.5 * crossd(e1, e2);
 			const double a = __builtin_sqrt(dotd(n, n));
 			const d3 es = e1 + e2;
-			const d3 c = v + mk(es.x / 3.0, es.y / 3.0, es.z / 3.0);
+			const d3 c = v + mk3d(es.x / 3.0, es.y / 3.0, es.z / 3.0);
 			m.N = m.N + n;
 			m.S = m.S + a;
 			m.M = m.M + a * c;
@@ -164,7 +153,7 @@ __global__ void __launch_bounds__(kB) k_winding(WindingParams P) {
 	uint32_t dipoles = 0, triangles = 0;
 	float w = __uint_as_float(0x7fc00000u);
 	if (finite32(fx) && finite32(fy) && finite32(fz)) {
-		const d3 q = mk((double)fx, (double)fy, (double)fz);
+		const d3 q = mk3d((double)fx, (double)fy, (double)fz);
 		const double B2 = (double)P.accuracy * (double)P.accuracy;
 		const uint32_t nNodes = (uint32_t)P.nNodes;
 		double sum = 0.0;
@@ -173,11 +162,11 @@ __global__ void __launch_bounds__(kB) k_winding(WindingParams P) {
 			const double2 r0 = rec[0], r1 = rec[1], r2 = rec[2], r3 = rec[3];
 			const unsigned long long ab = (unsigned long long)__double_as_longlong(r3.y);
 			const uint32_t a = (uint32_t)ab, b = (uint32_t)(ab >> 32);
-			const d3 d = mk(r0.x, r0.y, r1.x) - q;
+			const d3 d = mk3d(r0.x, r0.y, r1.x) - q;
 			const double d2 = dotd(d, d);
 			uint32_t next = b > 0u ? i + 1u : a;
 			if (d2 > B2 * r3.x) {
-				sum += dotd(d, mk(r1.y, r2.x, r2.y)) / (d2 * __builtin_sqrt(d2));
+				sum += dotd(d, mk3d(r1.y, r2.x, r2.y)) / (d2 * __builtin_sqrt(d2));
 				++dipoles;
 			} else if (b > 0u) {
 				for (uint32_t t = a; t < a + b; ++t) {
