@@ -572,8 +572,9 @@ int tyr_query_error(tyr_ctx* ctx, uint32_t* bits_out, int reset);
  * state.  It is a query like the ray queries: a later tyr_scene_refit waits for it, a query issued after a refit sees the
  * refitted scene, and a traversal stack overflow sets bit 1 of tyr_query_error.
  * TYR_ERR_INVALID: ctx, points, out, out->dist2 or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
- * Not part of it: the sphere table (flags must be 0), signed distance (region is what a caller needs to pick a face, edge or
- * vertex pseudo-normal itself).  The k nearest and all triangles within a radius: tyr_query_nearest_k below. */
+ * Not part of it: the sphere table (flags must be 0).  Signed distance is tyr_query_signed below (region is what a caller needs
+ * to pick a face, edge or vertex pseudo-normal itself).  The k nearest and all triangles within a radius: tyr_query_nearest_k
+ * below. */
 typedef struct tyr_nearest_out {
 	float*   dist2;  /* n, required */
 	int32_t* prim;   /* n, required: build-order index as tyr_query_closest's prim, -1 = none */
@@ -612,7 +613,8 @@ int tyr_query_nearest(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 */,
  * buffer.  Without a count the search is pruned by the k-th value found so far; with it, by bound2 alone.
  * TYR_ERR_INVALID: ctx, points, out, out->dist2 or out->prim NULL, n >= 2^31, k 0 or above TYR_QUERY_NEAREST_K_MAX, or
  * flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
- * Not part of it: the sphere table, signed distance, more than TYR_QUERY_NEAREST_K_MAX entries per point, approximate search. */
+ * Not part of it: the sphere table, signed distance (tyr_query_signed), more than TYR_QUERY_NEAREST_K_MAX entries per point,
+ * approximate search. */
 #define TYR_QUERY_NEAREST_K_MAX 32
 typedef struct tyr_nearest_k_out {
 	float*    dist2;   /* n x k, required */
@@ -671,7 +673,7 @@ int tyr_query_nearest_k(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 *
  * TYR_ERR_INVALID: ctx, origins, directions, out, out->count, out->t or out->prim NULL, n >= 2^31, max_hits 0 or above
  * TYR_QUERY_HITS_MAX, or a flag other than TYR_QUERY_TWO_SIDED (TYR_QUERY_SPHERES included: the sphere table is not part of it);
  * TYR_ERR_NO_SCENE: nothing uploaded.
- * Not part of it: spheres, distance pruning, more than TYR_QUERY_HITS_MAX entries per ray, signed distance as a call. */
+ * Not part of it: spheres, distance pruning, more than TYR_QUERY_HITS_MAX entries per ray, signed distance (tyr_query_signed). */
 #define TYR_QUERY_TWO_SIDED 2u   /* tyr_query_hits only */
 #define TYR_QUERY_HITS_MAX 32
 typedef struct tyr_hits_out {
@@ -808,8 +810,9 @@ int tyr_query_occlusion(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 *
  * sees the refitted scene and its rebuilt moments.
  * TYR_ERR_INVALID: ctx, points or w_out NULL, n >= 2^31, an accuracy that is NaN or negative; TYR_ERR_UNSUPPORTED: a ctx
  * without TYR_FLAG_WINDING; TYR_ERR_NO_SCENE: nothing uploaded.
- * Not part of it: higher-order expansions, the spheres, a signed-distance call, a voxel-grid helper (tyr_query_box answers the surface
- * voxels, this call the solid ones at their centres), point clouds. */
+ * Not part of it: higher-order expansions, the spheres, point clouds.  The signed-distance call and the voxel-grid helper built
+ * on this one are tyr_query_signed and tyr_bake_sdf (tyr_query_box answers the surface voxels, this call the solid ones at their
+ * centres). */
 int tyr_query_winding(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3, device */, float accuracy, float* w_out /* n */,
                       uint32_t* terms_out /* n x 2, NULL ok */, void* stream);
 /* Test hook in the spirit of tyr_scene_hash: nodes first .. first + count - 1 of the moment tree the ctx holds, read back into
@@ -940,8 +943,8 @@ int tyr_query_sweep(tyr_ctx* ctx, uint32_t n, const float* origins, const float*
  * TYR_ERR_INVALID: ctx, lo, hi, out or out->count NULL, out->prim NULL with max_prims > 0, n >= 2^31, max_prims above
  * TYR_QUERY_BOX_MAX, a flag other than TYR_QUERY_BOX_ANY, or TYR_QUERY_BOX_ANY with max_prims != 0; TYR_ERR_NO_SCENE: nothing
  * uploaded.
- * Not part of it: the sphere table, oriented boxes, more than TYR_QUERY_BOX_MAX indices per box, a voxel-grid call, clipping
- * the triangles to the box. */
+ * Not part of it: the sphere table, oriented boxes, more than TYR_QUERY_BOX_MAX indices per box, a voxel-grid call (signed
+ * distances on a grid: tyr_bake_sdf), clipping the triangles to the box. */
 #define TYR_QUERY_BOX_ANY 4u      /* tyr_query_box only */
 #define TYR_QUERY_BOX_MAX 32
 typedef struct tyr_box_out {
@@ -1086,7 +1089,7 @@ int tyr_query_tri(tyr_ctx* ctx, uint32_t n, const float* a /* n x 3 */, const fl
  * out->on_segment, out->on_triangle n x 3 (each may be NULL).
  * TYR_ERR_INVALID: ctx, p, q, out, out->dist2 or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
  * Not part of it: the sphere table (flags must be 0), an any-only mode, the k nearest, moving capsules (a moving sphere:
- * tyr_query_sweep), signed distance. */
+ * tyr_query_sweep), signed distance (of points: tyr_query_signed). */
 typedef struct tyr_segment_out {
 	float*   dist2;       /* n, required */
 	int32_t* prim;        /* n, required: build-order index, -1 = none */
@@ -1098,6 +1101,83 @@ typedef struct tyr_segment_out {
 } tyr_segment_out;
 int tyr_query_segment(tyr_ctx* ctx, uint32_t n, const float* p /* n x 3 */, const float* q /* n x 3 */, const float* max_dist /* n or NULL */,
                       uint32_t flags /* must be 0 */, const tyr_segment_out* out, void* stream);
+
+/* ---- signed-distance queries and the SDF grid bake (extension) -------------------------------------------------------------
+ * How far a point is from the mesh and on which side: tyr_query_signed for the caller's points, tyr_bake_sdf for the voxel
+ * centres of a regular grid, made on the device.  A signed distance is defined through two contracts above and through nothing
+ * else, so the ctx needs TYR_FLAG_WINDING.  For a point p with its max_dist (NULL: +inf) and the call's accuracy:
+ *   (dist2, prim, point)   what tyr_query_nearest answers for p and max_dist, bit for bit;
+ *   w                      what tyr_query_winding answers for p at accuracy, bit for bit;
+ *   inside = w > 0.5f;
+ *   m  = prim >= 0 ? (float)sqrt((double)dist2) : max_dist      (the correctly rounded binary32 root of dist2; without a
+ *                                                                 triangle nearer than max_dist the bound itself, +inf for NULL);
+ *   sd = inside ? -m : m.
+ * A scene without triangles therefore answers +max_dist (or +inf) for every valid point.
+ * gradient, in binary64 from the binary32 p and point, every operation rounded once, in this order:
+ *   with a winner, dist2 > 0 and p != point:   d = p - point (per component), len = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z),
+ *                                              gradient = (float)((inside ? -d : d) / len): away from the surface outside, and
+ *                                              still outward inside -- the direction in which sd grows;
+ *   with a winner otherwise (p on the triangle, or so near that point rounds to p):
+ *                                              n = cross(e1, e2) of prim's record, len = sqrt((n.x * n.x + n.y * n.y)
+ *                                              + n.z * n.z), gradient = (float)(n / len), 0 for a triangle without
+ *                                              area (len == 0);
+ *   without a winner:                          0.
+ * Invalid input -- a NaN or infinite coordinate, a NaN or negative max_dist: sd and w are the quiet NaN 0x7fc00000, prim = -1,
+ * point = p, gradient = 0.
+ *
+ * Arrays (DEVICE pointers, contiguous, float32 / int32, indexed with 64-bit offsets), n up to 2^31 - 1 and n == 0, streams, the
+ * device, "touches no render state", tyr_scene_refit (a call after a refit sees the refitted scene and its rebuilt moments) and
+ * bit 1 of tyr_query_error are tyr_query_nearest's and tyr_query_winding's: points n x 3; max_dist n or NULL; out->sd n
+ * (required); out->prim, out->w n, out->point, out->gradient n x 3 (each may be NULL).
+ * TYR_ERR_INVALID: ctx, points, out or out->sd NULL, n >= 2^31, flags != 0, an accuracy that is NaN or negative;
+ * TYR_ERR_UNSUPPORTED: a ctx without TYR_FLAG_WINDING; TYR_ERR_NO_SCENE: nothing uploaded.
+ *
+ * tyr_bake_sdf: a narrow-band grid of nx * ny * nz voxels, x fastest.  Every operation below is rounded to binary32; none is
+ * contracted to an fma.
+ *   voxel (i, j, k)      its centre is origin.x + cell * ((float)i + 0.5f), and so per axis;
+ *   brick (bi, bj, bk)   the voxels 4 b .. 4 b + 3 per axis that the grid has (an edge cuts a brick short); its centre is
+ *                        origin.x + cell * (float)(4 * bi + 2), and so per axis;
+ *   reach                band + 2.625f * cell: no voxel centre of a brick lies farther from the brick's centre (1.5 * sqrt(3) =
+ *                        2.598 cells; DESIGN.md "Signed distance" derives that 2.625 leaves room for the roundings);
+ *   a far brick          tyr_query_nearest at its centre with max_dist = reach answers prim = -1.  With w_c what
+ *                        tyr_query_winding answers at the centre, every voxel of it gets sd = (w_c > 0.5f) ? -band : band and
+ *                        prim = -1;
+ *   a near brick         every other one.  Each voxel of it gets exactly tyr_query_signed's sd and prim at its centre with
+ *                        max_dist = band and the grid's accuracy: +-band, with its own sign, without a triangle inside band;
+ *   stats                (near bricks, far bricks).
+ * What the shortcut assumes: inside a ball the surface does not enter the exact winding number is constant, so the voxels of
+ * a far brick are on their centre's side.  For a closed, well-shaped mesh at an accuracy of about 2 the bake therefore equals
+ * tyr_query_signed at the voxel centres with max_dist = band, voxel by voxel.  For a soup, an open sheet, or slivers whose
+ * tyr_query_nearest value lies above the true distance, the bake is what the rules above say: the definition's answer, and a
+ * deterministic one -- the order in which the near bricks are worked through varies from run to run, the outputs do not.
+ * TYR_ERR_INVALID: ctx, grid, out or out->sd NULL, flags != 0, a cell or band that is not finite and > 0, an origin that is not
+ * finite, a dimension of 0, nx * ny * nz >= 2^31, an accuracy that is NaN or negative; the other errors, streams, refit and
+ * tyr_query_error as above.  The list of near bricks is scratch the ctx keeps from one bake to the next (4 bytes per brick,
+ * counted in tyr_scene_info.device_bytes once a bake has run); bakes of one ctx run one after another, whatever their streams.
+ * Not part of it: the sphere table, other brick sizes, sparse output, gradients on the grid (difference sd, or ask
+ * tyr_query_signed at the voxels of interest). */
+typedef struct tyr_signed_out {
+	float*   sd;        /* n, required */
+	int32_t* prim;      /* n or NULL: build-order index of the nearest triangle, -1 = none */
+	float*   point;     /* n x 3 or NULL: the closest point */
+	float*   gradient;  /* n x 3 or NULL */
+	float*   w;         /* n or NULL: the winding number that decided the sign */
+} tyr_signed_out;
+int tyr_query_signed(tyr_ctx* ctx, uint32_t n, const float* points /* n x 3 */, const float* max_dist /* n or NULL */,
+                     float accuracy, uint32_t flags /* must be 0 */, const tyr_signed_out* out, void* stream);
+typedef struct tyr_sdf_grid {
+	float    origin[3]; /* the corner of voxel (0, 0, 0) */
+	float    cell;      /* a voxel's edge */
+	uint32_t dims[3];   /* nx, ny, nz */
+	float    band;      /* distances are answered up to this */
+	float    accuracy;  /* tyr_query_winding's */
+} tyr_sdf_grid;
+typedef struct tyr_sdf_out {
+	float*    sd;       /* nz * ny * nx, x fastest, required */
+	int32_t*  prim;     /* the same shape, or NULL */
+	uint32_t* stats;    /* 2 or NULL: near bricks, far bricks */
+} tyr_sdf_out;
+int tyr_bake_sdf(tyr_ctx* ctx, const tyr_sdf_grid* grid, uint32_t flags /* must be 0 */, const tyr_sdf_out* out, void* stream);
 
 /* ---- refit: moving geometry in the uploaded tree (extension) -------------------------------------------------------------
  * New triangles for the scene the ctx holds, in the tree's shape: the same leaves, primitive order, split axes and child order;

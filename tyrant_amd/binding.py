@@ -168,6 +168,24 @@ class SegmentOut(C.Structure):
     _fields_ = [("dist2", P), ("prim", P), ("s", P), ("feature", P), ("region", P), ("on_segment", P), ("on_triangle", P)]
 
 
+class SignedOut(C.Structure):
+    """tyr_signed_out: device pointers of tyr_query_signed's outputs; prim, point, gradient, w may be NULL"""
+
+    _fields_ = [("sd", P), ("prim", P), ("point", P), ("gradient", P), ("w", P)]
+
+
+class SdfGrid(C.Structure):
+    """tyr_sdf_grid: the voxel grid of tyr_bake_sdf"""
+
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("dims", c_u32 * 3), ("band", C.c_float), ("accuracy", C.c_float)]
+
+
+class SdfOut(C.Structure):
+    """tyr_sdf_out: device pointers of tyr_bake_sdf's outputs; prim, stats may be NULL"""
+
+    _fields_ = [("sd", P), ("prim", P), ("stats", P)]
+
+
 class HitsOut(C.Structure):
     """tyr_hits_out: device pointers of tyr_query_hits's outputs; uv, side, back_count may be NULL"""
 
@@ -334,6 +352,8 @@ SYMBOLS = {
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
     "tyr_query_winding": (C.c_int, [P, c_u32, P, C.c_float, P, P, P]),
+    "tyr_query_signed": (C.c_int, [P, c_u32, P, P, C.c_float, c_u32, P, P]),
+    "tyr_bake_sdf": (C.c_int, [P, P, c_u32, P, P]),
     "tyr_scene_moments": (C.c_int, [P, c_i32, c_i32, P]),
     "tyr_scene_refit": (C.c_int, [P, P, P, c_i32, c_u32, P, P]),
     "tyr_render_aov": (C.c_int, [P, c_u32, P, P]),
@@ -954,6 +974,42 @@ class Renderer:
         w, t = self._query_outputs(n, ((), torch.float32), ((2,), torch.int32) if terms else None)
         self._query_call("tyr_query_winding", stream, staged, n, p.data_ptr(), float(accuracy), *_dptrs(w, t))
         return (w, t) if terms else w
+
+    def query_signed(self, points, max_dist=None, accuracy=2.0, gradient=False, stream=None):
+        """tyr_query_signed: the signed distance of every point to the uploaded triangles (include/tyr_c.h "Signed-distance queries";
+        the ctx needs TYR_FLAG_WINDING) -- tyr_query_nearest's distance with the sign of tyr_query_winding's inside test, negative
+        inside.  points: (N, 3) float32, max_dist: (N,) or None -- torch tensors on this ctx's device, taken as they are, or numpy
+        arrays; accuracy: query_winding's.  Returns torch tensors (sd, prim, point, w), and gradient (N, 3) behind them with
+        gradient=True: the unit direction in which sd grows.  Without a triangle nearer than max_dist, sd = +-max_dist, prim = -1
+        and point = the query point; an invalid point or max_dist has sd = w = NaN."""
+        import torch
+
+        n, ins, staged = self._query_inputs(("points", points, (3,)), ("max_dist", max_dist, ()), optional=("max_dist",))
+        vec = ((3,), torch.float32)
+        sd, prim, point, grad, w = self._query_outputs(n, ((), torch.float32), ((), torch.int32), vec, vec if gradient else None, ((), torch.float32))
+        out = SignedOut(*_dptrs(sd, prim, point, grad, w))
+        self._query_call("tyr_query_signed", stream, staged, n, *_dptrs(*ins), float(accuracy), 0, C.byref(out))
+        return (sd, prim, point, w, grad) if gradient else (sd, prim, point, w)
+
+    def bake_sdf(self, origin, cell, dims, band, accuracy=2.0, prim=False, stats=False, stream=None):
+        """tyr_bake_sdf: a narrow-band signed-distance grid of the uploaded triangles (include/tyr_c.h "Signed-distance queries"; the
+        ctx needs TYR_FLAG_WINDING).  origin: the corner of voxel (0, 0, 0); cell: a voxel's edge; dims: (nx, ny, nz); band:
+        distances are answered up to it, +-band beyond.  The voxel centres are made on the device.  Returns the torch tensor sd
+        (nz, ny, nx) float32; with prim=True the nearest triangle per voxel (the same shape, int32, -1 = none inside band) behind
+        it; with stats=True (near bricks, far bricks) as an int32 tensor of 2 (the library's uint32) behind that."""
+        import torch
+
+        nx, ny, nz = (int(d) for d in dims)
+        grid = SdfGrid((C.c_float * 3)(*(float(o) for o in origin)), float(cell), (c_u32 * 3)(nx, ny, nz), float(band), float(accuracy))
+        dev = torch.device("cuda", self.device)
+        ok = min(nx, ny, nz) >= 1 and nx * ny * nz < 2**31
+        shape = (nz, ny, nx) if ok else (0, 0, 0)  # (a refused grid: the library says so, nothing is written)
+        sd = torch.empty(shape, dtype=torch.float32, device=dev)
+        pr = torch.empty(shape, dtype=torch.int32, device=dev) if prim else None
+        st = torch.empty(2, dtype=torch.int32, device=dev) if stats else None
+        out = SdfOut(*_dptrs(sd, pr, st))
+        self._query_call("tyr_bake_sdf", stream, False, C.byref(grid), 0, C.byref(out))
+        return sd if not (prim or stats) else tuple(x for x in (sd, pr, st) if x is not None)
 
     def scene_moments(self, first=0, count=None) -> np.ndarray:
         """tyr_scene_moments: (count, 8) float64 -- p xyz, N xyz, r2, S of nodes first .. first + count - 1 of the moment tree this

@@ -169,6 +169,11 @@ struct tyr_ctx {
 	tyr::RefitPlan refit{};
 	// TYR_FLAG_WINDING: the moment tree every scene upload and refit builds for tyr_query_winding (host/winding.cpp)
 	tyr::WindingTree winding{};
+	// tyr_bake_sdf (host/signed.cpp): the near-brick list -- word 0 the count, then sdfListCap brick indices -- kept from call to
+	// call and grown as needed, and the event behind the last bake, which the next one waits for (they share the list)
+	uint32_t* dSdfList = nullptr;
+	size_t sdfListCap = 0;
+	hipEvent_t sdfDone = nullptr;
 
 	hipEvent_t ev[2][2 * TYR_K_COUNT]{}; // TYR_FLAG_PROFILE: start / stop per stage, two sets (iteration i uses set i & 1: two iterations may be queued)
 	bool evUsed[2][TYR_K_COUNT]{};

@@ -616,6 +616,7 @@ int tyr_destroy(tyr_ctx* c) {
 	dev_free(c->dPalette);
 	refit_free(c);
 	winding_free(c);
+	sdf_free(c);
 	if (c->ownBlit)
 		dev_free(c->blit);
 	if (c->hK)

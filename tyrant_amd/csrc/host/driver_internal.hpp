@@ -95,6 +95,8 @@ void refit_free(tyr_ctx* c);
 // stream, which is idle on return
 int winding_build(tyr_ctx* c, const tyr_bvh_node* dNodes, const tyr_bvh_node* hostNodes, int32_t nNodes);
 void winding_free(tyr_ctx* c);
+// host/signed.cpp: wait for the last tyr_bake_sdf; free its near-brick list and event (tyr_destroy)
+void sdf_free(tyr_ctx* c);
 // host/query.cpp: wait for the ctx's queries in flight on any stream; free their device words (tyr_destroy)
 int query_wait(tyr_ctx* c);
 // ... and the bracket round every launch of a query-like pass (tyr_query_*, tyr_render_aov, tyr_render_motion) on the caller's

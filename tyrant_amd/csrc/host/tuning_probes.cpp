@@ -106,7 +106,8 @@ int tyr_get_scene_info(tyr_ctx* c, tyr_scene_info* out) {
 	const bool havePairs = (c->cfg.flags & (TYR_FLAG_COUNT_VISITS | TYR_FLAG_DEBUG_BVH)) != 0;
 	out->device_bytes = static_cast<uint64_t>(c->scene.nQuads) * 128 + (havePairs ? static_cast<uint64_t>(c->scene.nPairs) * 64 : 0) + static_cast<uint64_t>(c->scene.nPrims) * 48
 	                    + c->refit.bytes    // TYR_FLAG_REFIT's plan (host/refit.cpp); 0 without the flag
-	                    + c->winding.bytes; // TYR_FLAG_WINDING's moment tree (host/winding.cpp); 0 without the flag
+	                    + c->winding.bytes // TYR_FLAG_WINDING's moment tree (host/winding.cpp); 0 without the flag
+	                    + (c->dSdfList ? (c->sdfListCap + 1) * sizeof(uint32_t) : 0); // tyr_bake_sdf's near-brick list, once a bake has run (host/signed.cpp)
 	out->upload_layout_s = c->uploadLayoutS;
 	out->upload_copy_s = c->uploadCopyS;
 	out->layout_on_device = c->layoutOnDevice ? 1u : 0u;
