@@ -4,18 +4,12 @@ The oracle has no mapped mode, so mapped renders are pinned from three sides: a 
 oracle); the pixels of the mapped camera rays must be the ticket list's (tests/adaptive_ref.py); and everything after the
 camera rays must match the oracle when it is handed the GPU's post-primary queue.  The allocator is held to its numpy
 restatement bit for bit."""
-import os
-import re
-import subprocess
-
 import numpy as np
 import pytest
 
 import adaptive_ref as ar
 from conftest import bits, built_scene
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "tyrant_amd", "csrc")
+from kernel_resources import kernel_resources, parse_resources
 
 
 # ---- CPU: the restatements -----------------------------------------------------------------------
@@ -71,24 +65,14 @@ def test_allocator_restatement_properties():
 
 
 def test_new_kernels_have_no_spills_and_no_scratch():
-    subprocess.run(["make", "-s", "-C", CSRC, "build/adaptive.s"], check=True, capture_output=True, timeout=900)
-    cur, found = None, {}
-    for line in open(os.path.join(CSRC, "build", "adaptive.resources.txt")):
-        m = re.search(r"remark:\s+(.*?)\s+\[-Rpass-analysis", line)
-        if not m:
-            continue
-        text = m.group(1)
-        if text.startswith("Function Name:"):
-            cur = found.setdefault(text.split(":", 1)[1].strip(), {})
-        elif cur is not None and ":" in text:
-            k, v = text.rsplit(":", 1)
-            cur[k.strip()] = v.strip()
+    found = kernel_resources("adaptive")
+    found.update(parse_resources("frame"))  # k_primary_mapped is one of primary_rays' kernels (hip/frame.hip)
     names = ("k_primary_mapped", "k_map_hist", "k_pass_count", "k_pass_scan_blocks", "k_pass_scatter", "k_pass_repeat", "k_pass_tail", "k_alloc_max", "k_alloc_scan", "k_alloc_scan_blocks", "k_alloc_map")
     for n in names:
         ks = [v for k, v in found.items() if f"{len(n)}{n}E" in k]
         assert len(ks) == 1, (n, list(found))
         r = ks[0]
-        assert r["SGPRs Spill"] == "0" and r["VGPRs Spill"] == "0" and r["ScratchSize [bytes/lane]"] == "0", (n, r)
+        assert r["SGPRs Spill"] == 0 and r["VGPRs Spill"] == 0 and r["ScratchSize [bytes/lane]"] == 0, (n, r)
 
 
 # ---- GPU -------------------------------------------------------------------------------------------

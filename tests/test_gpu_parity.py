@@ -258,14 +258,23 @@ def test_axis_aligned_rays_and_long_leaves(orc, hip, flags):
     assert np.array_equal(qo["identifier"][hit], qg["identifier"][hit]) and np.array_equal(qo["geometry_type"][hit], qg["geometry_type"][hit])
 
 
-def test_visit_counters_match_reference_counting_rule(orc, hip):
-    """TYR_FLAG_COUNT_VISITS reproduces the oracle's nodes-visited / triangles-tested counts (bvh.h:164-209 rule)"""
-    o, g = pair(orc, hip, "cornell_soup2k", 96, 64, 6144, flags=4)
+@pytest.mark.parametrize("name", ["cornell_soup2k", "mesh32", "cornell_area_light"])
+def test_visit_counters_match_reference_counting_rule(orc, hip, name):
+    """TYR_FLAG_COUNT_VISITS reproduces everything the oracle counts by the reference's rule (bvh.h:164-209 for extend,
+    bvh.h:213-256 for connect): nodes visited, triangles tested and rays that passed the root box, per walk, and what the
+    counting build's connect kernel finds visible.  Both of that kernel's retire paths have to run: some shadow rays
+    occluded, some visible."""
+    o, g = pair(orc, hip, name, 96, 64, 6144, flags=4)
     for _ in range(3):
         o.launch_kernels(), g.launch_kernels()
     ko, kg = o.counters(), g.counters()
-    for f in ("nodes_extend", "tris_extend", "nodes_connect", "tris_connect"):
-        assert ko[f] == kg[f] and ko[f] > 0, f
+    assert kg["device_error"] == 0
+    counting = ("nodes_extend", "tris_extend", "rays_in_tree_extend", "nodes_connect", "tris_connect", "rays_in_tree_connect")
+    for f in counting + ("n_shadow_visible", "total_shadow_rays"):
+        assert ko[f] == kg[f], (f, ko[f], kg[f])
+    for f in counting:
+        assert ko[f] > 0, f
+    assert 0 < ko["n_shadow_visible"] < ko["total_shadow_rays"]
 
 
 def test_edge_cases(orc, hip):

@@ -1,121 +1,13 @@
-// adaptive.hip -- adaptive sampling (include/tyr_c.h "Adaptive sampling", DESIGN.md "Adaptive sampling"): the camera-ray kernel
-// of mapped mode, the build of a sample map's sample-major ticket list, and the allocator that turns a per-pixel error estimate
-// into a sample map with an exact total.
+// adaptive.hip -- adaptive sampling (include/tyr_c.h "Adaptive sampling", DESIGN.md "Adaptive sampling"): the build of a sample
+// map's sample-major ticket list, and the allocator that turns a per-pixel error estimate into a sample map with an exact total.
+// (The camera rays of mapped mode are made by hip/frame.hip's k_primary_mapped.)
 #include <algorithm>
 #include <cfloat>
 
 #include "adaptive.hpp"
 #include "device_common.hpp"
-#include "prologue.hpp"
 
 namespace tyr {
-
-// ======================================================================================
-// primary_rays in mapped mode.  This is frame.hip's k_primary line for line except for where the pixel comes from: ticket
-// total - budget + index of the list instead of the raster cursor start + index.  The body is a copy, not a shared helper:
-// k_primary's ISA is pinned instruction for instruction (tests/test_kernel_resources.py, profiles/r06_pmc_k_primary.txt), and
-// device_common.hpp's camera_focus / camera_lens record how a split of this code once moved its instructions -- frame.hip is
-// left as it is.  A change to one of the two bodies belongs in both.
-// ======================================================================================
-__global__ void __launch_bounds__(kBlock) k_primary_mapped(const FrameParams P, const MappedPrimary M) {
-	__shared__ uint32_t baseSh[kClasses], cntSh[8], lastSh;
-	const uint32_t index = blockIdx.x * kBlock + threadIdx.x;
-	const uint32_t cnt = P.k->primary_ray_cnt; // survivors already in the buffer (kernel.cu:253)
-	const unsigned long long room = (unsigned long long)(P.N - cnt);
-	const unsigned long long budget = P.k->budget_remaining;
-	const uint32_t nNew = (uint32_t)(room < budget ? room : budget);
-	const bool mine = index < nNew;
-	const uint32_t vslot = index + cnt;
-	uint32_t seed = camera_seed(P, index); // kernel.cu:258: the launch index, as in raster mode
-
-	// the ticket: budget <= total in mapped mode (tyr_set_sample_map sets it to total, launches only lower it) and index < nNew <= budget.
-	// A budget above the list is a broken invariant: the rays are made from pixel 0 and the error word says so.
-	const bool inList = budget <= (unsigned long long)M.total;
-	const uint32_t ticket = M.total - (uint32_t)budget + index;
-	const uint32_t p = (mine && inList) ? M.list[ticket] : 0u;
-	if (mine && !inList && index == 0u)
-		atomicOr(&P.k->device_error, kErrTicketRange);
-	const int x = (int)(p % P.W);
-	const int yl = (int)(p / P.W);
-	const int y = yl * (int)P.nranks + (int)P.rank;
-
-	const CameraRay cr = camera_lens(P, seed, camera_focus(P, seed, x, y), ld3(P.camPos), ld3(P.camRight), ld3(P.camUp));
-	const f3 lensPoint = cr.origin, direction = cr.direction;
-
-	const float2 hitRecord = sphere_hit_record(P, lensPoint, direction);
-	const bool tree = mine && P.scene.rootRef != kRefDone && root_ref(P.scene, make_ray(lensPoint, direction), hitRecord.x) != kRefDone;
-	const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-	const bool sky = P.retireSky != 0u && mine && !tree && !(hitRecord.x < kVeryFar);
-	if (__ballot(sky) != 0ull) {
-		f3 radiance = mk3(0.f, 0.f, 0.f);
-		if (sky) {
-			if (P.sun.sunAngularDiameterCos == 1.0f) {
-				radiance = mk3(1.0f, 0.0f, 0.0f); // sunsky.cu:118-119
-			} else {
-				const Atmosphere a = atmosphere(P.sun, direction);
-				radiance = sunsky_radiance(P.sun, a);
-			}
-			P.survFlag[vslot] = 0;
-		}
-		accumulate_pixels_wave(P.blit, y * (int)P.W + x, radiance, sky ? 1 : 0);
-	}
-	const unsigned long long bt = __ballot(tree), bsky = __ballot(mine && !tree && !sky), below = (1ull << lane) - 1ull;
-	if (lane == 0) {
-		cntSh[wave] = (uint32_t)__popcll(bt);
-		cntSh[4 + wave] = (uint32_t)__popcll(bsky);
-	}
-	__syncthreads();
-	uint32_t before[2] = { 0, 0 }, total[2] = { 0, 0 };
-#pragma unroll
-	for (uint32_t w = 0; w < kBlock / 64; ++w) {
-		if (w < wave) {
-			before[0] += cntSh[w];
-			before[1] += cntSh[4 + w];
-		}
-		total[0] += cntSh[w];
-		total[1] += cntSh[4 + w];
-	}
-	const uint32_t seg = blockIdx.x & (kSegs - 1u);
-	if (threadIdx.x < kClasses) {
-		const uint32_t c = threadIdx.x, n = total[c];
-		uint32_t base = 0;
-		if (n) {
-			base = atomicAdd(&P.segWork[c * kClassWords + seg * kSegStride], n);
-			if (base + n > P.segCap) {
-				atomicOr(&P.k->device_error, kErrQueueOverflow);
-				base = 0xffffffffu;
-			}
-		}
-		baseSh[c] = base;
-	}
-	__syncthreads();
-	const uint32_t cls = tree ? 0u : 1u;
-	if (mine && !sky && baseSh[cls] != 0xffffffffu) {
-		const uint32_t rank = before[cls] + (uint32_t)__popcll((tree ? bt : bsky) & below);
-		const uint32_t slot = cls * P.classStride + seg_phys(seg, baseSh[cls] + rank);
-		P.work.o_dx[slot] = make_float4(lensPoint.x, lensPoint.y, lensPoint.z, direction.x);
-		P.work.dyz[slot] = make_float2(direction.y, direction.z);
-		P.work.direct_ix[slot] = make_float4(1.0f, 1.0f, 1.0f, __int_as_float(y * (int)P.W + x));
-		P.work.flags[slot] = 0u | (1u << 8);
-		P.work.hit[slot] = hitRecord;
-		P.work.key[slot] = vslot;
-	}
-	// set_wavefront_globals by the block that finishes last (frame.hip k_primary: the same counting, the same reasons)
-	__syncthreads();
-	if (threadIdx.x == 0) {
-		const uint32_t w = blockIdx.x & (kTicketWords - 1u);
-		const uint32_t mineOfWord = (gridDim.x - w + kTicketWords - 1u) / kTicketWords;
-		uint32_t last = 0;
-		if (atomicAdd(&P.k->primary_done[w * 32], 1u) + 1u == mineOfWord) {
-			const uint32_t words = gridDim.x < kTicketWords ? gridDim.x : kTicketWords;
-			last = atomicAdd(&P.k->primary_blocks_done, 1u) + 1u == words ? 1u : 0u;
-		}
-		lastSh = last;
-	}
-	__syncthreads();
-	if (lastSh)
-		wavefront_globals(P);
-}
 
 // ======================================================================================
 // The ticket list L of a sample map: pass s lists, in increasing order, the local pixels p with c[p] > s; L is the passes
@@ -484,10 +376,6 @@ __global__ void __launch_bounds__(kBlock) k_alloc_map(const AllocateArgs A) {
 
 // ---- launch wrappers ---------------------------------------------------------------------
 
-void launch_primary_mapped(const FrameParams& P, const MappedPrimary& M, uint32_t maxNew, hipStream_t stream) {
-	// always launched: its last block is set_wavefront_globals
-	launch_in_stage(k_primary_mapped, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), stream, P, M);
-}
 void launch_map_hist(const SampleMapArgs& A, uint32_t localPixels, hipStream_t stream) {
 	hipLaunchKernelGGL(k_map_hist, dim3(blocks_for(localPixels)), dim3(kBlock), 0, stream, A, localPixels);
 }

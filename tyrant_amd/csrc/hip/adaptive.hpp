@@ -1,17 +1,11 @@
-// adaptive.hpp -- launch interface of adaptive sampling (hip/adaptive.hip) for host/adaptive.cpp and host/driver.cpp: the mapped
-// camera-ray kernel, the build of a sample map's ticket list, and the allocator that turns an error estimate into a sample map.
+// adaptive.hpp -- launch interface of adaptive sampling (hip/adaptive.hip) for host/adaptive.cpp: the build of a sample map's
+// ticket list, and the allocator that turns an error estimate into a sample map.  (The camera-ray kernel that reads the list is
+// one of primary_rays' kernels: hip/frame.hip k_primary_mapped, hip/kernels.hpp launch_primary_mapped.)
 #pragma once
 
 #include "kernels.hpp"
 
 namespace tyr {
-
-// k_primary_mapped's second argument: the ticket list L of the ctx's sample map (include/tyr_c.h "Adaptive sampling").  The
-// new ray at launch index i of a launch that starts with budget_remaining = b takes local pixel list[total - b + i].
-struct MappedPrimary {
-	const uint32_t* list; // total entries, local pixel indices
-	uint32_t total;       // T = sum of the map over the ctx's rows
-};
 
 // where the map of one tyr_set_sample_map call is read and what its first pass leaves for the host
 struct SampleMapArgs {
@@ -21,7 +15,6 @@ struct SampleMapArgs {
 	uint32_t* summary;    // [kMapSummaryWords + kMaxSpp + 1]: T (two words, low first), the largest count, a bad-value flag, then hist[v]
 };
 constexpr uint32_t kMaxSpp = 65535u;
-constexpr uint32_t kErrTicketRange = 16u; // DevCounters::device_error: a mapped camera ray's ticket fell outside the list (budget above T: cannot happen through the C ABI)
 constexpr uint32_t kMapSummaryWords = 4u;
 constexpr uint32_t kCompactTile = 1024u; // elements per block of the list build's compaction (256 threads x 4 rounds)
 
@@ -47,8 +40,5 @@ struct AllocateArgs {
 	unsigned long long* totalOut;  // sum of the map written
 };
 void launch_allocate(const AllocateArgs& A, hipStream_t stream);
-
-// primary_rays in mapped mode (frame.hip k_primary with the pixel taken from the ticket list)
-void launch_primary_mapped(const FrameParams& P, const MappedPrimary& M, uint32_t maxNew, hipStream_t stream);
 
 } // namespace tyr

@@ -9,11 +9,13 @@ namespace tyr {
 // ======================================================================================
 // primary_rays, kernel.cu:247-297.  One thread per new queue slot.
 // ======================================================================================
-// Three kernels share the body.  k_primary makes a whole top-up.  k_primary_window and k_primary_rest make it in two parts
+// Four kernels share the body.  k_primary makes a whole top-up.  k_primary_window and k_primary_rest make it in two parts
 // (DESIGN.md 4.8 (6)): the rays whose pixel lies in the camera window -- the only ones that can pass the root box, so the
 // only ones the iteration's traversal launch reads -- and, beside that launch on a second stream, all the others.  A ray is
-// the same ray whichever kernel makes it: its ticket `index` gives it its seed, its pixel and its virtual slot.
-enum : int { kPrimaryWhole = 0, kPrimaryWindow = 1, kPrimaryRest = 2 };
+// the same ray whichever of the three makes it: its ticket `index` gives it its seed, its pixel and its virtual slot.
+// k_primary_mapped makes a whole top-up of adaptive sampling (include/tyr_c.h "Adaptive sampling"): the pixel comes from the
+// sample map's ticket list instead of the raster cursor, everything else is k_primary's.
+enum : int { kPrimaryWhole = 0, kPrimaryWindow = 1, kPrimaryRest = 2, kPrimaryMapped = 3 };
 
 // A ray of k_primary_rest that does pass the root box (the window is a bound the host computed, not something the result may
 // rest on): the traversal launch is already running and does not know of it, so it is traced here -- the quad tree in the
@@ -78,17 +80,18 @@ __device__ __forceinline__ float2 trace_stray(const DevScene& sc, uint2* stack, 
 }
 
 template <int PART>
-__device__ __forceinline__ void primary_rays(const FrameParams& P, const PrimaryWindow& win) {
+__device__ __forceinline__ void primary_rays(const FrameParams& P, const PrimaryWindow& win, const MappedPrimary& map = MappedPrimary{}) {
 	__shared__ uint32_t baseSh[kClasses], cntSh[8], lastSh;
 	__shared__ uint2 strayStack[PART == kPrimaryRest ? (kBlock / 64) * kStackSize : 1];
 	uint32_t index = blockIdx.x * kBlock + threadIdx.x;
 	uint32_t cnt, nNew, start;
+	unsigned long long budget = 0ull;
 	if (PART == kPrimaryRest) {
 		cnt = P.k->plan_cnt, nNew = P.k->plan_new, start = P.k->plan_start;
 	} else {
 		cnt = P.k->primary_ray_cnt; // survivors already in the buffer (kernel.cu:253)
 		const unsigned long long room = (unsigned long long)(P.N - cnt);
-		const unsigned long long budget = P.k->budget_remaining;
+		budget = P.k->budget_remaining;
 		nNew = (uint32_t)(room < budget ? room : budget);
 		start = P.k->start_position;
 	}
@@ -103,6 +106,17 @@ __device__ __forceinline__ void primary_rays(const FrameParams& P, const Primary
 		const unsigned long long at = (unsigned long long)sweep * P.localPixels + (uint32_t)yl * P.W + (uint32_t)x; // = start + ticket
 		mine = at >= start && at - start < nNew;
 		index = (uint32_t)(at - start);
+	} else if (PART == kPrimaryMapped) {
+		// the ticket: budget <= total in mapped mode (tyr_set_sample_map sets it to total, launches only lower it) and index < nNew <= budget.
+		// A budget above the list is a broken invariant: the rays are made from pixel 0 and the error word says so.
+		mine = index < nNew;
+		const bool inList = budget <= (unsigned long long)map.total;
+		const uint32_t ticket = map.total - (uint32_t)budget + index;
+		const uint32_t p = (mine && inList) ? map.list[ticket] : 0u;
+		if (mine && !inList && index == 0u)
+			atomicOr(&P.k->device_error, kErrTicketRange);
+		x = (int)(p % P.W);
+		yl = (int)(p / P.W);
 	} else {
 		x = (int)((start + index) % P.W);
 		yl = (int)(((start + index) / P.W) % P.localRows);
@@ -116,8 +130,9 @@ __device__ __forceinline__ void primary_rays(const FrameParams& P, const Primary
 	f3 lensPoint = mk3(0.f, 0.f, 0.f), direction = mk3(0.f, 0.f, 0.f);
 	float2 hitRecord = make_float2(kVeryFar, 0.f);
 	bool tree = false, sky = false;
-	// (the two parts: a wave none of whose lanes has a ray -- the other part's pixels -- has nothing to compute)
-	if (PART == kPrimaryWhole || __ballot(mine) != 0ull) {
+	// (the two parts: a wave none of whose lanes has a ray -- the other part's pixels -- has nothing to compute; a whole
+	// top-up, raster or mapped, computes every wave)
+	if (PART == kPrimaryWhole || PART == kPrimaryMapped || __ballot(mine) != 0ull) {
 		uint32_t seed = camera_seed(P, index);
 		const CameraRay cr = camera_lens(P, seed, camera_focus(P, seed, x, y), ld3(P.camPos), ld3(P.camRight), ld3(P.camUp));
 		lensPoint = cr.origin, direction = cr.direction;
@@ -240,6 +255,7 @@ __device__ __forceinline__ void primary_rays(const FrameParams& P, const Primary
 __global__ void __launch_bounds__(kBlock) k_primary(const FrameParams P) { primary_rays<kPrimaryWhole>(P, PrimaryWindow{}); }
 __global__ void __launch_bounds__(kBlock) k_primary_window(const FrameParams P, const PrimaryWindow win) { primary_rays<kPrimaryWindow>(P, win); }
 __global__ void __launch_bounds__(kBlock) k_primary_rest(const FrameParams P, const PrimaryWindow win) { primary_rays<kPrimaryRest>(P, win); }
+__global__ void __launch_bounds__(kBlock) k_primary_mapped(const FrameParams P, const MappedPrimary map) { primary_rays<kPrimaryMapped>(P, PrimaryWindow{}, map); }
 
 // extend pre-pass: kernel.cu:125-136 (spheres first; their distance bounds the BVH search)
 // (grid-stride over the device's count: the host may have sized the grid from an upper bound, and a capped grid makes a
@@ -709,8 +725,8 @@ __global__ void __launch_bounds__(kBlock) k_sunsky_probe(const SunParams S, int 
 __global__ void __launch_bounds__(kBlock) k_extend_debug(const FrameParams P) {
 	uint32_t refs[kStackSize];
 	float ts[kStackSize];
-	TravStack<0> st;
-	st.bind(nullptr, refs, ts);
+	TravStack st;
+	st.bind(refs, ts);
 	st.reset();
 	uint32_t slot = blockIdx.x * kBlock + threadIdx.x;
 	{
@@ -726,7 +742,7 @@ __global__ void __launch_bounds__(kBlock) k_extend_debug(const FrameParams P) {
 	if (P.scene.rootRef != kRefDone) {
 		VisitCount vc{ 0, 0 };
 		const RayConst r = make_ray(mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y));
-		const bool hit = bvh_closest<true>(P.scene, r, dist, prim, st, vc);
+		const bool hit = bvh_closest(P.scene, r, dist, prim, st, vc);
 		traversals = (int)vc.nodes - 1; // bvh.h:172-175: the counter starts at -1 and counts loop iterations
 		P.work.hit[slot] = make_float2(dist, __uint_as_float(hit ? (uint32_t)prim : 0u));
 		if (st.overflow)
@@ -761,6 +777,10 @@ void launch_pad_holes(const FrameParams& P, bool workQueue, bool shadowQueue, hi
 void launch_primary(const FrameParams& P, uint32_t maxNew, hipStream_t stream) {
 	// always launched: its last block is set_wavefront_globals
 	launch_in_stage(k_primary, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), stream, P);
+}
+void launch_primary_mapped(const FrameParams& P, const MappedPrimary& map, uint32_t maxNew, hipStream_t stream) {
+	// always launched: its last block is set_wavefront_globals
+	launch_in_stage(k_primary_mapped, dim3(maxNew ? blocks_for(maxNew) : 1u), dim3(kBlock), stream, P, map);
 }
 void launch_primary_window(const FrameParams& P, const PrimaryWindow& win, uint32_t maxNew, hipStream_t stream) {
 	// the sweeps over the rank's rows that maxNew tickets can touch from any start position, each with the window's pixels

@@ -141,6 +141,7 @@ constexpr uint32_t kErrStackOverflow = 1u;
 // (bit 2 was the look-back time-out of rounds 1-2's stable compaction: no longer raised, not reused)
 constexpr uint32_t kErrNoProgress = 4u; // -DTYR_GUARD_PASSES builds: a wave of a flat traversal kernel ran out of passes (kMaxPasses)
 constexpr uint32_t kErrQueueOverflow = 8u; // a queue segment ran out of room (the records beyond it were dropped); cannot happen with segCap as host/driver.cpp sizes it, kept as a check
+constexpr uint32_t kErrTicketRange = 16u; // a mapped camera ray's ticket fell outside the list (budget above T: cannot happen through the C ABI)
 
 struct FrameParams {
 	uint32_t W, H, N;
@@ -289,6 +290,13 @@ struct PrimaryWindow {
 };
 void launch_primary_window(const FrameParams& P, const PrimaryWindow& win, uint32_t maxNew, hipStream_t stream);
 void launch_primary_rest(const FrameParams& P, const PrimaryWindow& win, uint32_t maxNew, hipStream_t stream, hipEvent_t stop);
+// launch_primary in mapped mode (adaptive sampling, hip/adaptive.hpp): the ticket list L of the ctx's sample map.  The new ray at
+// launch index i of a launch that starts with budget_remaining = b takes local pixel list[total - b + i].
+struct MappedPrimary {
+	const uint32_t* list; // total entries, local pixel indices
+	uint32_t total;       // T = sum of the map over the ctx's rows
+};
+void launch_primary_mapped(const FrameParams& P, const MappedPrimary& map, uint32_t maxNew, hipStream_t stream);
 void launch_pad_holes(const FrameParams& P, bool workQueue, bool shadowQueue, hipStream_t stream, bool resetTickets = false); // the slots at the segments' ends that hold no record become rays that enter nothing
 void launch_scan(const FrameParams& P, uint32_t maxLive, hipStream_t stream); // the survive bytes of this iteration -> vWordOut / vPreOut / vBlkOut
 // nSurvivors: upper bound of the slots the sphere pre-pass still has to do (primary rays get theirs in k_primary)

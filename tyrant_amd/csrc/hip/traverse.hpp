@@ -194,34 +194,22 @@ __device__ __forceinline__ float triangle_test_select(const TriData& d, const Ra
 	return (out0 || out1 || out2) ? 0.0f : t;
 }
 
-// Per-lane traversal stack: the first LDS_DEPTH entries in LDS, the rest in a private (scratch)
-// array, the top entry cached in registers (a push followed by a pop never touches memory).
-//
-// Why LDS: on CDNA, vmcnt retires loads AND stores in issue order, so a scratch push (a store)
-// sits in front of the next node fetch's wait and a scratch pop is a vector-memory round trip on
-// the critical path "pop -> node address -> fetch".  LDS traffic is counted by lgkmcnt instead and
-// returns in ~64 cycles.  Layout [depth][thread]: a lane always hits its own pair of banks whatever
-// its depth (depth * 256 threads * 8 B is a whole number of 256-byte bank rows), so divergent
-// depths never conflict.
+// Per-lane traversal stack of the one-thread-per-ray pair-node walk (bvh_closest): kStackSize entries in private (scratch)
+// arrays, the top entry cached in registers (a push followed by a pop never touches memory).
 //
 // The arrays live OUTSIDE this struct (the kernel declares them and binds pointers): with the
 // arrays as members, the compiler kept the whole object -- n, hasTop, the cached top -- in scratch
 // (scratch_store_dword in the descent loop of the first build), because a struct holding a
 // dynamically indexed array is not split into registers.
-template <int LDS_DEPTH>
 struct TravStack {
-	static constexpr int kBlockThreads = 256;
-	static constexpr int kSpill = kStackSize - LDS_DEPTH; // entries of the private arrays
-	uint2* lds;          // this thread's column: entry d at lds[d * kBlockThreads]
-	uint32_t* spillRef;  // kSpill entries
+	uint32_t* spillRef;  // kStackSize entries each
 	float* spillT;
 	int n;               // entries in memory
 	uint32_t topRef;
 	float topT;
 	bool hasTop;
 	bool overflow;
-	__device__ __forceinline__ void bind(uint2* ldsColumn, uint32_t* refs, float* ts) {
-		lds = ldsColumn;
+	__device__ __forceinline__ void bind(uint32_t* refs, float* ts) {
 		spillRef = refs;
 		spillT = ts;
 	}
@@ -232,12 +220,9 @@ struct TravStack {
 	}
 	__device__ __forceinline__ void push(uint32_t r, float t) {
 		if (hasTop) {
-			if (LDS_DEPTH > 0 && n < LDS_DEPTH) {
-				lds[n * kBlockThreads] = make_uint2(topRef, __float_as_uint(topT));
-				++n;
-			} else if (n < kStackSize - 1) {
-				spillRef[n - LDS_DEPTH] = topRef;
-				spillT[n - LDS_DEPTH] = topT;
+			if (n < kStackSize - 1) {
+				spillRef[n] = topRef;
+				spillT[n] = topT;
 				++n;
 			} else {
 				overflow = true; // the reference's 64-entry array would be overrun here (bvh.h:124)
@@ -257,19 +242,22 @@ struct TravStack {
 		if (n == 0)
 			return false;
 		--n;
-		if (LDS_DEPTH > 0 && n < LDS_DEPTH) {
-			const uint2 e = lds[n * kBlockThreads];
-			r = e.x;
-			t = __uint_as_float(e.y);
-		} else {
-			r = spillRef[n - LDS_DEPTH];
-			t = spillT[n - LDS_DEPTH];
-		}
+		r = spillRef[n];
+		t = spillT[n];
 		return true;
 	}
 };
 
-// The flat traversal kernels' stack: the same storage, but no register-cached top and a wave-level fast path.
+// The flat traversal kernels' stack: the first LDS_DEPTH entries in LDS, the rest in a private (scratch) array, no
+// register-cached top, and a wave-level fast path.
+//
+// Why LDS: on CDNA, vmcnt retires loads AND stores in issue order, so a scratch push (a store)
+// sits in front of the next node fetch's wait and a scratch pop is a vector-memory round trip on
+// the critical path "pop -> node address -> fetch".  LDS traffic is counted by lgkmcnt instead and
+// returns in ~64 cycles.  Layout [depth][thread]: a lane always hits its own pair of banks whatever
+// its depth (depth * 256 threads * 8 B is a whole number of 256-byte bank rows), so divergent
+// depths never conflict.  The arrays live outside the struct and are bound as pointers, for TravStack's reason.
+//
 // PMC on the tuned kernel: 2.25 G scalar against 2.05 G vector instructions per frame -- the scalar unit (one per
 // CU, shared by the four SIMDs) was as busy as the vector units, most of it exec-mask bookkeeping around the
 // three pushes of a quad step: each push nested "is there a cached top", "LDS or private", "full?".  Here a wave
@@ -700,10 +688,10 @@ struct VisitCount {
 	uint32_t nodes, tris;
 };
 
-// Closest hit.  `dist` / `prim` are updated like ray.distance / ray.identifier (bvh.h:135-136).
-// COUNT: also count nodes visited / triangles tested by the reference's rule (bvh.h:164-209:
+// Closest hit, one thread per ray (k_extend_debug).  `dist` / `prim` are updated like ray.distance / ray.identifier
+// (bvh.h:135-136).  vc counts nodes visited / triangles tested by the reference's rule (bvh.h:164-209:
 // one per loop iteration = every node fetched, including those whose box test fails).
-template <bool COUNT, class Stack>
+template <class Stack>
 __device__ __forceinline__ bool bvh_closest(const DevScene& sc, const RayConst& r, float& dist, int& prim, Stack& st, VisitCount& vc) {
 	bool hit = false;
 	st.reset();
@@ -712,15 +700,14 @@ __device__ __forceinline__ bool bvh_closest(const DevScene& sc, const RayConst& 
 		float t0;
 		const bool ok = slab_test(r, r.nx ? sc.rootMax[0] : sc.rootMin[0], r.nx ? sc.rootMin[0] : sc.rootMax[0], r.ny ? sc.rootMax[1] : sc.rootMin[1], r.ny ? sc.rootMin[1] : sc.rootMax[1],
 			r.nz ? sc.rootMax[2] : sc.rootMin[2], r.nz ? sc.rootMin[2] : sc.rootMax[2], dist, t0);
-		if (COUNT)
-			vc.nodes += 1;
+		vc.nodes += 1;
 		ref = ok ? sc.rootRef : kRefDone;
 	}
 	while (ref != kRefDone) {
 		// interior nodes: keep descending until this lane holds a leaf (or is done)
 		while ((int)ref >= 0) {
 			const PairTest p = test_pair(sc.nodes, ref, r, dist);
-			if (COUNT && !p.synthetic)
+			if (!p.synthetic)
 				vc.nodes += 2; // closest hit never exits early: both children are visited by the reference
 			if (p.nearHit) {
 				if (p.farHit)
@@ -747,8 +734,7 @@ __device__ __forceinline__ bool bvh_closest(const DevScene& sc, const RayConst& 
 		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
 		for (uint32_t i = 0; i < cnt; ++i) {
 			const float t = triangle_test(sc.tris, off + i, r);
-			if (COUNT)
-				vc.tris += 1;
+			vc.tris += 1;
 			if (t > kEpsilon && t < dist && ((dist - t) > kEpsilon)) {
 				prim = (int)(off + i);
 				dist = t;
@@ -766,79 +752,6 @@ __device__ __forceinline__ bool bvh_closest(const DevScene& sc, const RayConst& 
 		}
 	}
 	return hit;
-}
-
-// Any hit within `closest` (bvh.h:213-256).  The bound never shrinks, so the result does not
-// depend on visit order; the same near-first order is kept so COUNT reproduces the reference's
-// visit counts (nodes popped before the early return).
-template <bool COUNT, class Stack>
-__device__ __forceinline__ bool bvh_any(const DevScene& sc, const RayConst& r, float closest, Stack& st, VisitCount& vc) {
-	st.reset();
-	uint32_t ref;
-	{
-		float t0;
-		const bool ok = slab_test(r, r.nx ? sc.rootMax[0] : sc.rootMin[0], r.nx ? sc.rootMin[0] : sc.rootMax[0], r.ny ? sc.rootMax[1] : sc.rootMin[1], r.ny ? sc.rootMin[1] : sc.rootMax[1],
-			r.nz ? sc.rootMax[2] : sc.rootMin[2], r.nz ? sc.rootMin[2] : sc.rootMax[2], closest, t0);
-		if (COUNT)
-			vc.nodes += 1;
-		ref = ok ? sc.rootRef : kRefDone;
-	}
-	const float kFailed = __builtin_inff(); // COUNT only: a far child that failed its box test but is still "visited" when popped
-	while (ref != kRefDone) {
-		while ((int)ref >= 0) {
-			const PairTest p = test_pair(sc.nodes, ref, r, closest);
-			if (COUNT && !p.synthetic) {
-				vc.nodes += 1; // the near child is visited next
-				st.push(p.farRef, p.farHit ? p.farT : kFailed);
-				ref = p.nearHit ? p.nearRef : kRefDone;
-			} else {
-				if (p.nearHit) {
-					if (p.farHit)
-						st.push(p.farRef, p.farT);
-					ref = p.nearRef;
-				} else if (p.farHit) {
-					ref = p.farRef;
-				} else {
-					ref = kRefDone;
-				}
-			}
-			if (ref == kRefDone) {
-				uint32_t pr;
-				float pt;
-				while (st.pop(pr, pt)) {
-					if (COUNT)
-						vc.nodes += 1;
-					if (pt < closest) {
-						ref = pr;
-						break;
-					}
-				}
-			}
-		}
-		if (ref == kRefDone)
-			break;
-		const uint32_t off = ref & (kMaxPrimOffset - 1);
-		const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-		for (uint32_t i = 0; i < cnt; ++i) {
-			const float t = triangle_test(sc.tris, off + i, r);
-			if (COUNT)
-				vc.tris += 1;
-			if (t > kEpsilon && ((closest - t) > kEpsilon))
-				return true; // bvh.h:232-236
-		}
-		ref = kRefDone;
-		uint32_t pr;
-		float pt;
-		while (st.pop(pr, pt)) {
-			if (COUNT)
-				vc.nodes += 1;
-			if (pt < closest) {
-				ref = pr;
-				break;
-			}
-		}
-	}
-	return false;
 }
 
 #endif // __HIPCC__

@@ -150,36 +150,60 @@ __device__ __forceinline__ uint32_t static_slot(uint32_t s, uint32_t blockBegin,
 
 // ======================================================================================
 // The counting build (TYR_FLAG_COUNT_VISITS): extend and connect as launches of their own on PAIR nodes -- the only
-// layout that reproduces the reference's visit counts (intersect_debug's rule, bvh.h:164-209: every fetched node counts,
-// a leaf's triangles count one each) -- with the same flat per-lane state machine as the production kernel.  Block b owns
-// the physical slots [b * raysPerBlock, +raysPerBlock) of the queue and hands them to the free lanes of its four waves
-// through a counter in LDS; slots that hold no record are skipped (slot_valid).  Not a hot path: n-bar of the roofline
-// comes from ONE untimed render of this build.
+// layout that reproduces the reference's visit counts (every fetched node counts, a leaf's triangles count one each) --
+// with the same flat per-lane state machine as the production kernel.  Block b owns the physical slots
+// [b * raysPerBlock, +raysPerBlock) of the queue and hands them to the free lanes of its four waves through a counter in
+// LDS; slots that hold no record are skipped (slot_valid).  Not a hot path: n-bar of the roofline comes from ONE untimed
+// render of this build.
+// One text for both walks: ANY = false is extend's closest-hit walk (intersect_debug's rule, bvh.h:164-209) over class 0
+// of the work queue, ANY = true connect's any-hit walk (bvh.h:213-256) over the shadow queue.  The compile-time branches
+// stand where the reference's two walks differ: the queue a ray is read from, the pop's count, the push of failed far
+// boxes, the leaf's accept and stop rule, and what a finished ray does.
 // ======================================================================================
-template <int STACK_LDS>
-__global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_extend_count(const FrameParams P) {
-	constexpr bool COUNT = true; // (TYR_DBG)
-	TYR_DECLARE_FLAT_STACK(st, true)
+template <bool ANY, int STACK_LDS>
+__device__ __forceinline__ void count_rays(const FrameParams& P) {
+	constexpr bool COUNT = !ANY; // (TYR_DBG: tyr_counters.debug is the closest-hit walk's, tools/loop_occupancy.py)
+	TYR_DECLARE_FLAT_STACK(st, true) // (the any-hit walk marks failed boxes through the entry distance)
 	const uint32_t lane = lane_id();
 	const unsigned long long below = (1ull << lane) - 1ull;
-	const uint32_t nSlots = queue_extent(P.segWork); // class 0; the few slots that hold no record are skipped
+	const uint32_t* const seg = ANY ? P.kc->seg : P.segWork; // the shadow queue / class 0 of the work queue
+	const uint32_t nSlots = queue_extent(seg);               // physical slots; the few that hold no record are skipped
 	const DevScene& sc = P.scene;
+	const bool haveBvh = (sc.rootRef != kRefDone);
 	float rox = 0.f, roy = 0.f, roz = 0.f, rdx = 0.f, rdy = 0.f, rdz = 0.f, rix = 0.f, riy = 0.f, riz = 0.f;
 	bool regular = true, allRegular = true;
-	float dist = 0.0f;
+	float dist = 0.0f; // the bound of the search: the closest hit so far / the shadow ray's closestDistance, which never shrinks
 	uint32_t ref = kRefDone, slot = 0;
 	int prim = 0;
-	bool hitTri = false, live = false, overflow = false;
+	bool hit = false; // closest hit: a triangle was accepted; any hit: the ray is occluded, by a sphere of the pre-pass or by a triangle
+	bool live = false, overflow = false;
 	VisitCount vc{ 0, 0 };
-	uint32_t inTree = 0; // rays of this lane that passed the root box
+	uint32_t inTree = 0;  // rays of this lane that passed the root box
+	uint32_t visible = 0; // any hit: rays of this lane that came through unoccluded
 	uint32_t dbg[16] = {};
+	// kernel.cu:640-644, deferred: a lane whose shadow ray came through unoccluded notes the slot; the wave adds all such
+	// colours to their pixels at its next refill (and once after the loop), transposed (accumulate_pixels_wave)
+	constexpr uint32_t kNoPending = 0xffffffffu;
+	uint32_t pendIdx = kNoPending;
+	auto flush_visible = [&]() {
+		float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
+		int px = 0;
+		if (pendIdx != kNoPending) {
+			c = P.shadow.color[pendIdx];
+			px = __float_as_int(P.shadow.dyz_cd_ix[pendIdx].w);
+		}
+		accumulate_pixels_wave(P.blit, px, mk3(c.x, c.y, c.z), 0);
+		pendIdx = kNoPending;
+	};
 	__shared__ uint32_t blockNext;
 	const uint32_t blockBegin = blockIdx.x * P.raysPerBlock;
 	const uint32_t blockEnd = (blockBegin + P.raysPerBlock) < nSlots ? (blockBegin + P.raysPerBlock) : nSlots;
 	if (threadIdx.x == 0)
 		blockNext = blockBegin;
 	__syncthreads();
-	bool exhausted = (sc.rootRef == kRefDone) || blockBegin >= nSlots;
+	// (without a BVH an extend ray keeps the pre-pass's answer and counts nothing; a shadow ray is still retired)
+	bool exhausted = blockBegin >= nSlots || (!ANY && !haveBvh);
+	const float kFailed = __builtin_inff();
 	uint32_t passes = 0; // see kMaxPasses
 
 	for (;;) {
@@ -199,28 +223,45 @@ __global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_extend_count(
 			exhausted = (base + nIdle >= blockEnd);
 			const uint32_t s = base + rank;
 			bool fed = !live && rank < take;
+			if (ANY && __ballot(pendIdx != kNoPending) != 0ull)
+				flush_visible();
 			if (fed)
-				fed = slot_valid(P.segWork, s);
+				fed = slot_valid(seg, s);
 			if (fed) {
 				TYR_DBG(6)
-				const float4 a = P.work.o_dx[s];
-				const float2 b = P.work.dyz[s];
-				const float2 h = P.work.hit[s];
-				const RayConst nr = make_ray(mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y));
-				rox = nr.o.x, roy = nr.o.y, roz = nr.o.z, rdx = nr.d.x, rdy = nr.d.y, rdz = nr.d.z, rix = nr.inv.x, riy = nr.inv.y, riz = nr.inv.z;
-				regular = ray_is_regular(nr);
-				dist = h.x; // the sphere pre-pass's distance bounds the search
+				f3 o, d;
+				if (ANY) { // kernel.cu:162-174
+					const float4 a = P.shadow.o_dx[s];
+					const float4 b = P.shadow.dyz_cd_ix[s];
+					o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
+					dist = b.z;
+					hit = reinterpret_cast<const float*>(&P.shadow.color[s])[3] != 0.0f; // the sphere pre-pass's answer
+				} else { // kernel.cu:125-142
+					const float4 a = P.work.o_dx[s];
+					const float2 b = P.work.dyz[s];
+					o = mk3(a.x, a.y, a.z), d = mk3(a.w, b.x, b.y);
+					dist = P.work.hit[s].x; // the sphere pre-pass's distance bounds the search
+					hit = false;
+				}
 				slot = s;
-				hitTri = false;
 				st.reset();
-				ref = root_ref(sc, nr, dist);
-				// a ray that misses the root box (or is already stopped short of it by a sphere) is finished here
-				live = (ref != kRefDone);
-				vc.nodes += 1;
-				inTree += live ? 1u : 0u;
+				ref = kRefDone;
+				// (any hit: the counting rule traverses the BVH whatever the spheres said, kernel.cu:164-172 tests it first -- if there is
+				// one; closest hit: without one nothing is fed, see `exhausted`, and the test of it here costs a scalar spill)
+				if (!ANY || haveBvh) {
+					const RayConst nr = make_ray(o, d);
+					rox = nr.o.x, roy = nr.o.y, roz = nr.o.z, rdx = nr.d.x, rdy = nr.d.y, rdz = nr.d.z, rix = nr.inv.x, riy = nr.inv.y, riz = nr.inv.z;
+					regular = ray_is_regular(nr);
+					ref = root_ref(sc, nr, dist);
+					vc.nodes += 1;
+					inTree += (ref != kRefDone) ? 1u : 0u;
+				}
+				// a closest-hit ray that misses the root box (or is already stopped short of it by a sphere) is finished here;
+				// a shadow ray that does still has its answer to hand in
+				live = ANY || ref != kRefDone;
 			}
-			if (!exhausted && (uint32_t)__popcll(__ballot(live)) < P.minTraversing)
-				continue;
+			if (!ANY && !exhausted && (uint32_t)__popcll(__ballot(live)) < P.minTraversing)
+				continue; // top the wave up again first
 		}
 		if (__ballot(live) == 0ull) {
 			if (exhausted)
@@ -245,6 +286,8 @@ __global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_extend_count(
 				uint32_t pr;
 				float pt;
 				if (st.pop(pr, pt)) {
+					if (ANY)
+						vc.nodes += 1; // the reference fetches the popped node before testing its box (bvh.h:222-224)
 					if (pt < dist) // the pop-time half of Bbox.h:61
 						ref = pr;
 				} else {
@@ -255,171 +298,8 @@ __global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_extend_count(
 				TYR_DBG(0)
 				const PairTest p = allRegular ? test_pair_fast(sc.nodes, ref, r, dist) : test_pair(sc.nodes, ref, r, dist);
 				if (!p.synthetic)
-					vc.nodes += 2;
-				if (p.nearHit) {
-					if (p.farHit)
-						st.push(p.farRef, p.farT);
-					ref = p.nearRef;
-				} else if (p.farHit) {
-					ref = p.farRef;
-				} else {
-					ref = kRefPop;
-				}
-			}
-		}
-		// ---- leaves: bvh.h:129-140 ----
-		if (ref_is_leaf(ref)) {
-			const uint32_t off = ref & (kMaxPrimOffset - 1);
-			const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-			TriData tri = triangle_load(sc.tris, off);
-			for (uint32_t i = 0; i < cnt; ++i) {
-				TYR_DBG(4)
-				const TriData cur = tri;
-				if (i + 1 < cnt)
-					tri = triangle_load(sc.tris, off + i + 1);
-				const float t = triangle_test(cur, r);
-				vc.tris += 1;
-				if (t > kEpsilon && t < dist && ((dist - t) > kEpsilon)) {
-					prim = (int)(off + i);
-					dist = t;
-					hitTri = true;
-				}
-			}
-			ref = kRefPop;
-		}
-		// ---- finished rays ----
-		if (live && ref == kRefDone) {
-			finish_extend_ray(P.work.hit, slot, hitTri, dist, prim);
-			overflow = overflow || st.overflow;
-			live = false;
-		}
-	}
-	if (overflow)
-		atomicOr(&P.k->device_error, kErrStackOverflow);
-	if (kGuardPasses && passes > kMaxPasses)
-		atomicOr(&P.k->device_error, kErrNoProgress);
-	// the rays of class 1 never come here: the reference tests the root box for each of them once and stops (bvh.h:127)
-	if (blockIdx.x == 0 && threadIdx.x == 0)
-		atomicAdd(&P.k->nodes_extend, (unsigned long long)queue_records(P.segWork + kClassWords));
-	wave_add_u64(&P.k->nodes_extend, vc.nodes);
-	wave_add_u64(&P.k->tris_extend, vc.tris);
-	wave_add_u64(&P.k->rays_in_tree_extend, inTree);
-	for (int i = 0; i < 13; ++i)
-		wave_add_u64(&P.k->debug[i], dbg[i]);
-}
-
-template <int STACK_LDS>
-__global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_connect_count(const FrameParams P) {
-	TYR_DECLARE_FLAT_STACK(st, true) // (the counting path marks failed boxes through the entry distance)
-	const uint32_t lane = lane_id();
-	const unsigned long long below = (1ull << lane) - 1ull;
-	const uint32_t nSlots = queue_extent(P.kc->seg); // physical slots of the shadow queue
-	const DevScene& sc = P.scene;
-	const bool haveBvh = (sc.rootRef != kRefDone);
-	float rox = 0.f, roy = 0.f, roz = 0.f, rdx = 0.f, rdy = 0.f, rdz = 0.f, rix = 0.f, riy = 0.f, riz = 0.f;
-	bool regular = true, allRegular = true;
-	float closest = 0.0f;
-	uint32_t ref = kRefDone, index = 0;
-	bool live = false, occluded = false, overflow = false;
-	VisitCount vc{ 0, 0 };
-	uint32_t inTree = 0;
-	uint32_t visible = 0;
-	// kernel.cu:640-644, deferred: a lane whose ray came through unoccluded notes the slot; the wave adds all such colours
-	// to their pixels at its next refill (and once after the loop), transposed (accumulate_pixels_wave)
-	constexpr uint32_t kNoPending = 0xffffffffu;
-	uint32_t pendIdx = kNoPending;
-	auto flush_visible = [&]() {
-		float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-		int px = 0;
-		if (pendIdx != kNoPending) {
-			c = P.shadow.color[pendIdx];
-			px = __float_as_int(P.shadow.dyz_cd_ix[pendIdx].w);
-		}
-		accumulate_pixels_wave(P.blit, px, mk3(c.x, c.y, c.z), 0);
-		pendIdx = kNoPending;
-	};
-	__shared__ uint32_t blockNext;
-	const uint32_t blockBegin = blockIdx.x * P.raysPerBlock;
-	const uint32_t blockEnd = (blockBegin + P.raysPerBlock) < nSlots ? (blockBegin + P.raysPerBlock) : nSlots;
-	if (threadIdx.x == 0)
-		blockNext = blockBegin;
-	__syncthreads();
-	bool exhausted = blockBegin >= nSlots;
-	const float kFailed = __builtin_inff();
-	uint32_t passes = 0; // see kMaxPasses
-
-	for (;;) {
-		if (kGuardPasses && ++passes > kMaxPasses)
-			break;
-		const unsigned long long idleMask = __ballot(!live);
-		const uint32_t nIdle = __popcll(idleMask);
-		if (!exhausted && nIdle >= P.refillMinIdle) {
-			const uint32_t rank = __popcll(idleMask & below);
-			uint32_t base = 0;
-			if (lane == 0)
-				base = atomicAdd(&blockNext, nIdle); // LDS
-			base = __shfl(base, 0, 64);
-			const uint32_t avail = base < blockEnd ? blockEnd - base : 0u;
-			const uint32_t take = avail < nIdle ? avail : nIdle;
-			exhausted = (base + nIdle >= blockEnd);
-			const uint32_t s = base + rank;
-			bool fed = !live && rank < take;
-			if (__ballot(pendIdx != kNoPending) != 0ull)
-				flush_visible();
-			if (fed)
-				fed = slot_valid(P.kc->seg, s);
-			if (fed) {
-				const float4 a = P.shadow.o_dx[s];
-				const float4 b = P.shadow.dyz_cd_ix[s];
-				const float sphereOccluded = reinterpret_cast<const float*>(&P.shadow.color[s])[3];
-				index = s;
-				closest = b.z;
-				occluded = (sphereOccluded != 0.0f);
-				live = true;
-				st.reset();
-				ref = kRefDone;
-				if (haveBvh) { // (the counting rule traverses the BVH whatever the spheres said: kernel.cu:164-172 tests it first)
-					const RayConst nr = make_ray(mk3(a.x, a.y, a.z), mk3(a.w, b.x, b.y));
-					rox = nr.o.x, roy = nr.o.y, roz = nr.o.z, rdx = nr.d.x, rdy = nr.d.y, rdz = nr.d.z, rix = nr.inv.x, riy = nr.inv.y, riz = nr.inv.z;
-					regular = ray_is_regular(nr);
-					ref = root_ref(sc, nr, closest);
-					vc.nodes += 1;
-					inTree += (ref != kRefDone) ? 1u : 0u;
-				}
-			}
-		}
-		if (__ballot(live) == 0ull) {
-			if (exhausted)
-				break;
-			continue;
-		}
-		allRegular = (__ballot(live && !regular) == 0ull);
-		const RayConst r = { mk3(rox, roy, roz), mk3(rdx, rdy, rdz), mk3(rix, riy, riz), rix < 0, riy < 0, riz < 0 }; // bvh.h:120-121
-		for (;;) {
-			const uint32_t nTrav = __popcll(lanes_traversing(ref));
-			if (nTrav == 0)
-				break;
-			if (nTrav < P.minTraversing) {
-				const bool anyLeaf = lanes_at_leaf(ref) != 0ull;
-				const bool canRefill = !exhausted && (uint32_t)__popcll(__ballot(!live || ref == kRefDone)) >= P.refillMinIdle;
-				if (anyLeaf || canRefill)
-					break;
-			}
-			if (ref == kRefPop) {
-				uint32_t pr;
-				float pt;
-				if (st.pop(pr, pt)) {
-					vc.nodes += 1; // the reference fetches the popped node before testing its box (bvh.h:222-224)
-					if (pt < closest)
-						ref = pr;
-				} else {
-					ref = kRefDone;
-				}
-			}
-			if ((int)ref >= 0) {
-				const PairTest p = allRegular ? test_pair_fast(sc.nodes, ref, r, closest) : test_pair(sc.nodes, ref, r, closest);
-				if (!p.synthetic) {
-					vc.nodes += 1;
+					vc.nodes += ANY ? 1 : 2; // any hit: the near child is visited next; closest hit never exits early: both children are visited
+				if (ANY && !p.synthetic) { // a far child that failed its box test is still "visited" when popped
 					st.push(p.farRef, p.farHit ? p.farT : kFailed);
 					ref = p.nearHit ? p.nearRef : kRefPop;
 				} else if (p.nearHit) {
@@ -433,45 +313,64 @@ __global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_connect_count
 				}
 			}
 		}
+		// ---- leaves: bvh.h:129-140 / 230-238 ----
 		if (ref_is_leaf(ref)) {
 			const uint32_t off = ref & (kMaxPrimOffset - 1);
 			const uint32_t cnt = ((ref >> 26) & 31u) + 1u;
-			bool found = false;
+			bool found = false; // any hit: the walk ends at the first triangle in the way
 			TriData tri = triangle_load(sc.tris, off);
 			for (uint32_t i = 0; i < cnt && !found; ++i) {
+				TYR_DBG(4)
 				const TriData cur = tri; // next record in flight while this one is tested
 				if (i + 1 < cnt)
 					tri = triangle_load(sc.tris, off + i + 1);
 				const float t = triangle_test(cur, r);
 				vc.tris += 1;
-				found = (t > kEpsilon && ((closest - t) > kEpsilon)); // bvh.h:232-236
+				if (ANY) {
+					found = (t > kEpsilon && ((dist - t) > kEpsilon)); // bvh.h:232-236
+				} else if (t > kEpsilon && t < dist && ((dist - t) > kEpsilon)) { // bvh.h:134
+					prim = (int)(off + i);
+					dist = t;
+					hit = true;
+				}
 			}
-			if (found) {
-				occluded = true;
-				ref = kRefDone;
-			} else {
-				ref = kRefPop;
-			}
+			hit = hit || found;
+			ref = found ? kRefDone : kRefPop;
 		}
+		// ---- finished rays ----
 		if (live && ref == kRefDone) {
-			if (!occluded) {
-				pendIdx = index;
+			if (!ANY) {
+				finish_extend_ray(P.work.hit, slot, hit, dist, prim);
+			} else if (!hit) {
+				pendIdx = slot;
 				visible += 1;
 			}
 			overflow = overflow || st.overflow;
 			live = false;
 		}
 	}
-	flush_visible();
 	if (overflow)
 		atomicOr(&P.k->device_error, kErrStackOverflow);
 	if (kGuardPasses && passes > kMaxPasses)
 		atomicOr(&P.k->device_error, kErrNoProgress);
-	wave_add_u64(&P.k->n_shadow_visible, visible);
-	wave_add_u64(&P.k->nodes_connect, vc.nodes);
-	wave_add_u64(&P.k->tris_connect, vc.tris);
-	wave_add_u64(&P.k->rays_in_tree_connect, inTree);
+	if (ANY) {
+		flush_visible();
+		wave_add_u64(&P.k->n_shadow_visible, visible);
+	} else {
+		// the rays of class 1 never come here: the reference tests the root box for each of them once and stops (bvh.h:127)
+		if (blockIdx.x == 0 && threadIdx.x == 0)
+			atomicAdd(&P.k->nodes_extend, (unsigned long long)queue_records(P.segWork + kClassWords));
+		for (int i = 0; i < 13; ++i)
+			wave_add_u64(&P.k->debug[i], dbg[i]);
+	}
+	wave_add_u64(ANY ? &P.k->nodes_connect : &P.k->nodes_extend, vc.nodes);
+	wave_add_u64(ANY ? &P.k->tris_connect : &P.k->tris_extend, vc.tris);
+	wave_add_u64(ANY ? &P.k->rays_in_tree_connect : &P.k->rays_in_tree_extend, inTree);
 }
+template <int STACK_LDS>
+__global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_extend_count(const FrameParams P) { count_rays<false, STACK_LDS>(P); }
+template <int STACK_LDS>
+__global__ void __launch_bounds__(kBlock, TYR_FLAT_WAVES_PER_EU) k_connect_count(const FrameParams P) { count_rays<true, STACK_LDS>(P); }
 
 // LDS executes a wave's instructions in order; this only keeps the COMPILER from moving a lane's LDS read above another
 // lane's write of the same wave (no instruction is emitted)

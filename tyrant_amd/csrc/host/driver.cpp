@@ -20,7 +20,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include "../hip/adaptive.hpp"
 #include "driver_internal.hpp"
 
 using namespace tyr;
