@@ -367,6 +367,7 @@ enum {
 	TYR_TUNE_OVERLAP_TRACE_BLOCKS = 29, /* ... the traversal launch of such an iteration runs this many 256-thread blocks per CU (3..5, default 3) instead of what the occupancy query admits, so that the second part has registers, wave slots and LDS to be resident beside it: for that one launch this key stands in for TYR_TUNE_WAVES_PER_SIMD, and TYR_TUNE_WIDE_BLOCK_MIN_ITEMS does not apply (no 768-thread blocks); every other launch keeps the caller's values */
 	TYR_TUNE_OVERLAP_MIN_NEW = 30,   /* ... only top-ups of at least this many rays, and at least four times the survivors they join (the host's upper bounds), are made in two parts: beside a traversal launch fat with survivors the second part only slows it; default 1 Mi, 0 = every top-up */
 	TYR_TUNE_WINDOW_INSET = 31,      /* test only: the camera window shrunk by this many pixels on every side (default 0), so that rays which do enter the tree lie outside it and the second part has to trace them itself (tyr_primary_window_info.strays) */
+	TYR_TUNE_SHADE_DENSE = 32,       /* k_shade (tyr_render and the stage API alike; a ctx with TYR_FLAG_LIGHT_LIST always runs 0): 1 (default) = a tile's atmosphere requests (sun(toSun) of a next-event sample, sky / sunsky of a miss or of a survivor finished in place) and its shadow rays' sphere and root-box tests (with TYR_TUNE_FOLD_SPHERES) are gathered across the tile's four waves and evaluated on dense lanes -- only requests and answers cross LDS, every ray's own arithmetic and the order of its sums stay, so the results are the same bits; 0 = each in the lane that asks, as a pass of the whole wave */
 	TYR_TUNE_FOLD_SPHERES = 19       /* merged path of tyr_render: 1 (default) = shade does the sphere pre-passes' work (kernel.cu:127-136, 168-172) for the rays it emits, while they are in registers; 0 = the pre-pass kernels re-read them */
 };
 int tyr_set_tuning(tyr_ctx* ctx, int key, int value);

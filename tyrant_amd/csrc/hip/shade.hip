@@ -34,6 +34,19 @@ struct ShadeOut {
 	bool ghost;
 };
 
+// what a ray can want from the atmosphere model (sunsky.cu): sun(toSun) of a next-event sample, sky / sunsky(direction) of a miss
+enum { kAtmoNone = 0, kAtmoSun, kAtmoSky, kAtmoSunSky };
+// DENSE (k_shade<false, true>, TYR_TUNE_SHADE_DENSE): the three sections of shade_ray that run for a whole wave as soon as one lane
+// needs them -- the ray's own atmosphere request, its ghost's, the shadow ray's sphere and root-box test -- are not
+// evaluated in the lane: the lane leaves a request, the tile evaluates all requests of its four waves on dense lanes
+// (the dense phase of the tile loop) and the lane applies the answers with the expressions and in the order below.
+struct ShadeReq {
+	int atmo;         // the ray's own request (its direction: out.sDir -- a miss puts its ray direction there), or kAtmoNone
+	float atmoScale;  // kAtmoSun: cosSun, what the answer is multiplied with
+	int ghostAtmo;    // its ghost's request (direction: out.direction): kAtmoSky / kAtmoSunSky, or kAtmoNone
+	bool shadowTest;  // its shadow ray (out.sOrigin, out.sDir, out.sClosest) awaits the sphere and root-box test
+};
+
 // NEE toward spheres[6], kernel.cu:419-447 / 559-590 (common part)
 struct LightSample {
 	f3 toLightUnit, toLight;
@@ -124,8 +137,8 @@ __device__ __forceinline__ EmitterSample sample_emitter(const FrameParams& P, ui
 // before).
 // Lanes past the end of the queue come along with valid = false (they load nothing and produce nothing) so that
 // afterLoads is reached by the whole wave.
-template <bool LIGHTS, class AfterLoads>
-__device__ __forceinline__ void shade_ray(const FrameParams& P, uint32_t slot, bool valid, float2 hitRecord, ShadeOut& out, uint32_t& vslotOut, AfterLoads&& afterLoads) {
+template <bool LIGHTS, bool DENSE, class AfterLoads>
+__device__ __forceinline__ void shade_ray(const FrameParams& P, uint32_t slot, bool valid, float2 hitRecord, ShadeOut& out, [[maybe_unused]] ShadeReq& req, uint32_t& vslotOut, AfterLoads&& afterLoads) {
 	float4 a = make_float4(0.f, 0.f, 0.f, 0.f), dq = a;
 	float2 b = make_float2(0.f, 0.f), h = make_float2(kVeryFar, 0.f);
 	uint32_t fl = 0, key = 0;
@@ -158,7 +171,6 @@ __device__ __forceinline__ void shade_ray(const FrameParams& P, uint32_t slot, b
 	out.sVisible = false;
 	out.ghost = false;
 
-	enum { kAtmoNone = 0, kAtmoSun, kAtmoSky, kAtmoSunSky };
 	int atmo = kAtmoNone;   // what this ray wants from the atmosphere model, evaluated once for the whole wave below
 	float atmoScale = 0.0f;
 	const bool hit = valid && distance < kVeryFar;
@@ -361,7 +373,17 @@ __device__ __forceinline__ void shade_ray(const FrameParams& P, uint32_t slot, b
 	// miss (sky / sunsky(direction), kernel.cu:613-617).  A ray asks at most once, nothing random is drawn in
 	// between, so all of them evaluate it HERE, in one pass of the wave, instead of one pass per place of call; every
 	// lane still performs exactly the operations the reference's order of evaluation prescribes.
-	if (atmo != kAtmoNone) {
+	if constexpr (DENSE) {
+		if (atmo == kAtmoSunSky && P.sun.sunAngularDiameterCos == 1.0f) {
+			color = color + direct * mk3(1.0f, 0.0f, 0.0f); // sunsky.cu:118-119
+			atmo = kAtmoNone;
+		} else if (atmo != kAtmoNone && !hit) {
+			out.sDir = direction; // (a miss emits no shadow ray and does not survive: the fields carry the request's direction
+			out.direct = direct;  // and the throughput its answer is multiplied with)
+		}
+		req.atmo = atmo;
+		req.atmoScale = atmoScale;
+	} else if (atmo != kAtmoNone) {
 		const bool miss = !hit;
 		const f3 viewDir = miss ? direction : out.sDir;
 		if (atmo == kAtmoSunSky && P.sun.sunAngularDiameterCos == 1.0f) {
@@ -403,7 +425,16 @@ __device__ __forceinline__ void shade_ray(const FrameParams& P, uint32_t slot, b
 	} else if (valid) {
 		new_frame++;
 	}
-	if (out.ghost) {
+	if constexpr (DENSE) {
+		req.ghostAtmo = kAtmoNone;
+		if (out.ghost) {
+			if (lastSpecular && P.sun.sunAngularDiameterCos == 1.0f)
+				color = color + direct * mk3(1.0f, 0.0f, 0.0f); // sunsky.cu:118-119 (a ghost is a hit: nothing else has touched `color` since its emission term)
+			else
+				req.ghostAtmo = lastSpecular ? kAtmoSunSky : kAtmoSky;
+			new_frame++;
+		}
+	} else if (out.ghost) {
 		// the next iteration's shade of this ray, now (kernel.cu:613-617 with its lastSpecular, its throughput): one more
 		// evaluation of the atmosphere for the lanes that need it; the pixel receives this iteration's and the next one's
 		// contribution as one sum, and the path is finished
@@ -419,7 +450,9 @@ __device__ __forceinline__ void shade_ray(const FrameParams& P, uint32_t slot, b
 	}
 
 	out.sBlocked = 0.0f;
-	if (P.foldSpheres && out.shadow) { // kernel.cu:168-172 (k_connect_spheres' test, on the ray in registers)
+	if constexpr (DENSE) {
+		req.shadowTest = P.foldSpheres && out.shadow;
+	} else if (P.foldSpheres && out.shadow) { // kernel.cu:168-172 (k_connect_spheres' test, on the ray in registers)
 		bool occluded = false;
 #pragma unroll
 		for (int i = TYR_NUM_SPHERES; i--;) {
@@ -470,13 +503,27 @@ struct ShadeStage { // one tile's output, waiting for the tile's place in the qu
 // queue on the counter of segment (tile / 2) % 8, issued as soon as the tile's counts are known; the records wait in LDS at
 // their rank inside the tile and leave as coalesced stores (thread t writes record t) AFTER the next tile has been
 // shaded -- by then the atomics have long returned.
-template <bool LIGHTS>
-__global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const FrameParams P_) {
+//
+// DENSE (k_shade<false, true>): a tile is a lane phase (shade_ray without its three wave-wide sections), a dense phase and a
+// finish.  The requests of the tile's four waves are ranked like its survivors (ballot, lanes_below, four counts through
+// sh[]) and wait in LDS where the records of the tile before waited -- flush_prev runs first: those records' places
+// arrived a whole lane phase ago -- a wave answers 64 consecutive requests and writes each answer over its request, and
+// every lane reads its own answers back.  Only requests and answers cross LDS, never a ray's state; a lane's sums are the same
+// operations in the same order, so its outputs are the same bits.
+struct DenseStage { // aliases ShadeStage: 16 KB of its 27
+	float4 atmo[2 * kBlock];   // request: viewDir.xyz, kAtmo* kind; answer: the radiance
+	float4 sh_o_dx[kBlock];    // shadow candidate: origin.xyz, direction.x
+	float4 sh_dyz_c[kBlock];   // direction.y, direction.z, closestDistance; answer in .w: bit 0 occluded by a sphere, bit 1 may enter the tree
+};
+static_assert(sizeof(DenseStage) <= sizeof(ShadeStage), "the dense phase's requests live in the staging area: no LDS of their own");
+
+template <bool LIGHTS, bool DENSE>
+__device__ __forceinline__ void shade_tiles(const FrameParams& P_) {
 	const FrameParams& P = P_;
 	__shared__ uint32_t sh[32];
 	__shared__ ShadeStage stage;
-	const uint32_t tid = threadIdx.x;
-	const uint32_t lane = tid & 63u, wave = tid >> 6;
+	uint32_t tid = threadIdx.x;
+	uint32_t lane = tid & 63u, wave = tid >> 6;
 	// class 0's tiles, then class 1's (from the device's counts: the host may have sized the grid from an upper bound)
 	const uint32_t tiles0 = queue_extent(P.segWork) / kBlock;
 	const uint32_t nTiles = tiles0 + queue_extent(P.segWork + kClassWords) / kBlock;
@@ -487,6 +534,13 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 #define TYR_STAMP(i) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc_[i] += now_ - t_; t_ = now_; }
 #else
 #define TYR_STAMP(i)
+#endif
+#ifdef TYR_SHADE_CENSUS
+	// diagnostic build: what the dense path's three sections are asked for, summed over the launch whose FrameParams::censusOn is set
+	// (tools/shade_census.py).  debug[0] valid lanes, [1] sun requests, [2] miss requests, [3] ghost requests, [4] shadow
+	// candidates, [5..7] waves with at least one own / ghost / shadow request (the passes the lane path runs), [8] waves with
+	// a valid lane, [9] tiles, [10] / [11] sum over tiles of ceil(atmosphere requests / 64) / ceil(shadow candidates / 64)
+	uint32_t census_[12] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
 #endif
 	bool havePrev = false;            // a shaded tile whose records wait in `stage`
 	uint32_t pendPixel = 0;           // this lane's pixel contribution of that tile, not yet added
@@ -499,6 +553,12 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 	[[maybe_unused]] uint32_t snapShadows = 0;
 	uint32_t waveGhosts = 0; // (wave-uniform) survivors finished in place (P.retireGhosts): they count as survivors
 	uint32_t waveResolved = 0, waveVisible = 0; // (wave-uniform) shadow rays answered in place (P.resolveShadows): they count as emitted, the visible ones as visible
+	if constexpr (DENSE) {
+		// (DENSE: the three sums are kept where the kernel's end reads them, sh[20 / 24 / 28 + wave], by the wave's lane 0 -- three
+		// scalar registers fewer through the dense phase, which wants them for the atmosphere model's constants)
+		if (lane == 0)
+			sh[20 + wave] = sh[24 + wave] = sh[28 + wave] = 0u;
+	}
 
 	// finish the waiting tile: its places have arrived (sh[12], sh[13]); move its records from LDS to the queues
 	auto flush_prev = [&]() {
@@ -563,6 +623,16 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 	for (uint32_t vb = nTiles != 0u ? draw_tile() : nTiles; vb < nTiles; vb = draw_tile()) { // vb = tile id = 256 physical slots of one class
 		TYR_STAMP(3) // (the draw: ticket)
 		const FrameParams& P = kernarg_view<FrameParams>(); // this tile's reads of the arguments: loaded where they are used (device_common.hpp; 113 scalar spills -> 2, 128 vector registers -> 96)
+		if constexpr (DENSE) {
+			// (the lane masks of `tid == 0`, `lane == 0` ... are made where a tile uses them, not held in scalar register pairs through the
+			// loop: the dense phase wants those registers for the atmosphere model's constants.  This, the flags packed into `bits`
+			// between two empty asm statements, the arguments read again through `tail` and the per-wave sums kept in sh[] are what
+			// brings this kernel to no spill with the compiler at hand; none of it is guaranteed by the language.
+			// tests/test_shade_dense_resources.py is the guard: when it reports scalar spills after a compiler update, look here)
+			__asm__ volatile("" : "+v"(tid));
+			lane = tid & 63u;
+			wave = tid >> 6;
+		}
 		const uint32_t cls = vb >= tiles0 ? 1u : 0u;
 		const uint32_t inClass = (vb - cls * tiles0) * kBlock + tid; // slot inside the class
 		const uint32_t slot = cls * P.classStride + inClass;
@@ -584,18 +654,163 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 			hitRecord = P.work.hit[slot];
 		if (valid)
 			pixelBits = __float_as_uint(P.work.direct_ix[slot].w);
-		shade_ray<LIGHTS>(P, slot, valid, hitRecord, out, vslot, flush_pixels);
+		ShadeReq req;
+		shade_ray<LIGHTS, DENSE>(P, slot, valid, hitRecord, out, req, vslot, flush_pixels);
 		if (valid)
 			P.survFlag[vslot] = out.survive ? 1 : 0; // what k_scan_words turns into next iteration's slots
 		TYR_STAMP(0)
 
+		const FrameParams* tail = &P; // the arguments as the rest of the tile reads them (DENSE: loaded again behind the dense phase, not held through it)
+		if constexpr (DENSE) {
+			DenseStage& dense = *reinterpret_cast<DenseStage*>(&stage);
+			// ---- ranks of the requests inside the tile: a wave's own requests, then its ghosts'; the shadow candidates ----
+			const bool qa = req.atmo != kAtmoNone;
+			const bool qg = req.ghostAtmo != kAtmoNone;
+			const bool qs = req.shadowTest;
+			const unsigned long long ba = __ballot(qa), bg = __ballot(qg), bs = __ballot(qs);
+			const uint32_t na = (uint32_t)__popcll(ba);
+			if (lane == 0) { // (sh[4..11]: the survivor and shadow counts of the ranks below are written three barriers on)
+				sh[4 + wave] = na + (uint32_t)__popcll(bg);
+				sh[8 + wave] = (uint32_t)__popcll(bs);
+			}
+			__syncthreads();
+			uint32_t ka = 0, ks = 0, nAtmo = 0, nShadow = 0;
+#pragma unroll
+			for (uint32_t w = 0; w < kBlock / 64; ++w) {
+				const uint32_t ca = sh[4 + w], cs = sh[8 + w];
+				if (w < wave) {
+					ka += ca;
+					ks += cs;
+				}
+				nAtmo += ca;
+				nShadow += cs;
+			}
+			nAtmo = (uint32_t)__builtin_amdgcn_readfirstlane((int)nAtmo); // block-uniform: every thread takes the same way through the barriers below
+			nShadow = (uint32_t)__builtin_amdgcn_readfirstlane((int)nShadow);
+			const uint32_t ia = ka + lanes_below(ba), ig = ka + na + lanes_below(bg), is = ks + lanes_below(bs);
+#ifdef TYR_SHADE_CENSUS
+			if (P.censusOn) { // (wave-uniform sums; [9..11] are the tile's, kept by wave 0)
+				const unsigned long long bsun = __ballot(qa && req.atmo == kAtmoSun);
+				census_[0] += (uint32_t)__popcll(__ballot(valid));
+				census_[1] += (uint32_t)__popcll(bsun);
+				census_[2] += na - (uint32_t)__popcll(bsun);
+				census_[3] += (uint32_t)__popcll(bg);
+				census_[4] += (uint32_t)__popcll(bs);
+				census_[5] += ba != 0ull;
+				census_[6] += bg != 0ull;
+				census_[7] += bs != 0ull;
+				census_[8] += __ballot(valid) != 0ull;
+				if (wave == 0) {
+					census_[9] += 1u;
+					census_[10] += (nAtmo + 63u) / 64u;
+					census_[11] += (nShadow + 63u) / 64u;
+				}
+			}
+#endif
+			// The lane's flags wait in one vector register, not as nine lane masks in scalar register pairs: the atmosphere model
+			// below wants the scalar file for the sun's constants and its binary64 coefficients (the empty asm keeps the compiler
+			// from seeing through the round trip).
+			uint32_t bits = (out.survive ? 1u : 0u) | (out.survive && out.tree ? 2u : 0u) | (out.ghost ? 4u : 0u) | (out.shadow ? 8u : 0u) | (out.sResolved ? 16u : 0u) |
+			                (out.sVisible ? 32u : 0u) | (qa ? 64u : 0u) | (qg ? 128u : 0u) | (qs ? 256u : 0u);
+			__asm__ volatile("" : "+v"(bits));
+			if (havePrev)
+				flush_prev(); // ends with a barrier: `stage` is free, and the tile before has its places long since (a whole lane phase has passed)
+			if (bits & 64u)
+				dense.atmo[ia] = make_float4(out.sDir.x, out.sDir.y, out.sDir.z, __int_as_float(req.atmo));
+			if (bits & 128u)
+				dense.atmo[ig] = make_float4(out.direction.x, out.direction.y, out.direction.z, __int_as_float(req.ghostAtmo));
+			if (bits & 256u) {
+				dense.sh_o_dx[is] = make_float4(out.sOrigin.x, out.sOrigin.y, out.sOrigin.z, out.sDir.x);
+				dense.sh_dyz_c[is] = make_float4(out.sDir.y, out.sDir.z, out.sClosest, 0.0f);
+			}
+			__syncthreads();
+			// ---- dense phase: a wave answers 64 consecutive requests; one whose share is past the count skips the section.  Wave w
+			// of every resident block runs on SIMD w, so "thread t answers request t" would leave the passes to SIMDs 0 and 1 of
+			// the CU in every tile and the others idle at the barrier: the atmosphere's passes start at a wave that turns with the
+			// tile, the shadow tests' passes at the wave behind them. ----
+			const uint32_t turn = (uint32_t)__builtin_amdgcn_readfirstlane((int)((wave - (vb >> 3)) & 3u));
+			const uint32_t tidAtmo = turn * 64u + lane;
+			const uint32_t tidShadow = ((turn - ((nAtmo + 63u) >> 6)) & 3u) * 64u + lane;
+			for (uint32_t first = 0; first < nAtmo; first += kBlock) { // (block-uniform; at most two rounds: a lane holds at most two requests)
+				const uint32_t t = first + tidAtmo;
+				if (t >= nAtmo)
+					continue;
+				const FrameParams& PD = kernarg_view<FrameParams>(); // (the sun's constants: loaded here, not held through the lane phase)
+				const float4 q = dense.atmo[t];
+				const int kind = __float_as_int(q.w);
+				const Atmosphere a = atmosphere(PD.sun, mk3(q.x, q.y, q.z));
+				const f3 r = kind == kAtmoSun ? sun_radiance(PD.sun, a) : (kind == kAtmoSky ? sky_radiance(a) : sunsky_radiance(PD.sun, a));
+				dense.atmo[t] = make_float4(r.x, r.y, r.z, 0.0f);
+			}
+			if (tidShadow < nShadow) { // kernel.cu:168-172 (k_connect_spheres' test), and the traversal kernel's own first test for the ray's bound
+				const FrameParams& PD = kernarg_view<FrameParams>(); // (the spheres, the root box: likewise)
+				const float4 c0 = dense.sh_o_dx[tidShadow], c1 = dense.sh_dyz_c[tidShadow];
+				const f3 sOrigin = mk3(c0.x, c0.y, c0.z), sDir = mk3(c0.w, c1.x, c1.y);
+				bool occluded = false;
+#pragma unroll
+				for (int i = TYR_NUM_SPHERES; i--;) {
+					const float t = sphere_intersect(PD.spheres[i], sOrigin, sDir);
+					occluded = occluded || (t && (t + kEpsilon) < c1.z);
+				}
+				uint32_t answer = occluded ? 1u : 0u;
+				if (PD.resolveShadows) {
+					const bool mayEnter = PD.scene.rootRef != kRefDone && root_ref(PD.scene, make_ray(sOrigin, sDir), c1.z) != kRefDone;
+					answer |= mayEnter ? 2u : 0u;
+				}
+				dense.sh_dyz_c[tidShadow].w = __uint_as_float(answer);
+			}
+			__syncthreads();
+			tail = &kernarg_view<FrameParams>();
+			// ---- finish, in the lane: the answers applied with the section's own expressions, in shade_ray's order ----
+			__asm__ volatile("" : "+v"(bits));
+			out.survive = (bits & 1u) != 0u;
+			out.tree = (bits & 2u) != 0u;
+			out.ghost = (bits & 4u) != 0u;
+			out.shadow = (bits & 8u) != 0u;
+			out.sResolved = (bits & 16u) != 0u;
+			out.sVisible = (bits & 32u) != 0u;
+			if (bits & 64u) {
+				const float4 q = dense.atmo[ia];
+				const f3 r = mk3(q.x, q.y, q.z);
+				if (req.atmo == kAtmoSun)
+					out.sColor = out.sColor * ((r * req.atmoScale) * 1E-5f);
+				else
+					out.color = out.color + out.direct * r;
+			}
+			if (bits & 128u) {
+				const float4 q = dense.atmo[ig];
+				out.color = out.color + out.direct * mk3(q.x, q.y, q.z);
+			}
+			if (bits & 256u) {
+				const uint32_t answer = __float_as_uint(dense.sh_dyz_c[is].w);
+				const bool occluded = (answer & 1u) != 0u;
+				out.sBlocked = occluded ? 1.0f : 0.0f;
+				if (tail->resolveShadows && (occluded || (answer & 2u) == 0u)) {
+					out.shadow = false;
+					out.sResolved = true;
+					out.sVisible = !occluded;
+				}
+			}
+			if (out.sVisible)
+				out.color = out.color + out.sColor; // kernel.cu:640-644 for a shadow ray answered here
+			// (these reads of `dense` are ordered before the records' writes to `stage` by the barrier of the ranks below)
+		}
+
+		const FrameParams& PT = *tail;
 		// ---- ranks inside the tile: survivors that may enter the tree, survivors that cannot, shadow rays ----
 		const bool sT = out.survive && out.tree, sS = out.survive && !out.tree && !out.ghost;
-		if (P.retireGhosts)
+		if constexpr (DENSE) {
+			const uint32_t g = (uint32_t)__popcll(__ballot(out.ghost)), r = (uint32_t)__popcll(__ballot(out.sResolved)), v = (uint32_t)__popcll(__ballot(out.sVisible));
+			if (lane == 0) { // (out.ghost needs retireGhosts, out.sResolved resolveShadows: zeros otherwise)
+				sh[28 + wave] += g;
+				sh[20 + wave] += r;
+				sh[24 + wave] += v;
+			}
+		} else if (PT.retireGhosts)
 			waveGhosts += (uint32_t)__popcll(__ballot(out.ghost));
 		const unsigned long long bt = __ballot(sT), bk = __ballot(sS);
 		const unsigned long long bh = __ballot(out.shadow);
-		if (P.resolveShadows) {
+		if (!DENSE && PT.resolveShadows) {
 			waveResolved += (uint32_t)__popcll(__ballot(out.sResolved));
 			waveVisible += (uint32_t)__popcll(__ballot(out.sVisible));
 		}
@@ -624,10 +839,12 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 		totH = (uint32_t)__builtin_amdgcn_readfirstlane((int)totH);
 		const uint32_t totS = totT + totK;
 		TYR_STAMP(1)
-		if (havePrev)
-			flush_prev(); // ends with a barrier: sh[4..13] have been read by every thread
-		else
-			__syncthreads();
+		if constexpr (!DENSE) {
+			if (havePrev)
+				flush_prev(); // ends with a barrier: sh[4..13] have been read by every thread
+			else
+				__syncthreads();
+		} // (DENSE: flush_prev has run, behind a barrier of its own -- sh[12], [13] and [18] are free; sh[4..11] and [14..17] are next written two barriers on)
 		// tiles 2k and 2k + 1 hold records [64k, 64k + 64) of all eight segments between them and both append to segment
 		// k % 8: whichever rays survive, a segment receives at most an eighth of the queue's records (+ 64 per segment)
 		const uint32_t seg = (vb >> 1) & (kSegs - 1u);
@@ -635,22 +852,22 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 			// this tile's places: consumed by flush_prev one tile later
 			uint32_t bT = 0, bK = 0, bH = 0;
 			if (totT) {
-				bT = atomicAdd(&P.segNext[seg * kSegStride], totT);
-				if (bT + totT > P.segCap)
+				bT = atomicAdd(&PT.segNext[seg * kSegStride], totT);
+				if (bT + totT > PT.segCap)
 					bT = 0xffffffffu;
 			}
 			if (totK) {
-				bK = atomicAdd(&P.segNext[kClassWords + seg * kSegStride], totK);
-				if (bK + totK > P.segCap)
+				bK = atomicAdd(&PT.segNext[kClassWords + seg * kSegStride], totK);
+				if (bK + totK > PT.segCap)
 					bK = 0xffffffffu;
 			}
 			if (totH) {
-				bH = atomicAdd(&P.kc->seg[seg * kSegStride], totH);
-				if (bH + totH > P.segCap)
+				bH = atomicAdd(&PT.kc->seg[seg * kSegStride], totH);
+				if (bH + totH > PT.segCap)
 					bH = 0xffffffffu;
 			}
 			if (bT == 0xffffffffu || bK == 0xffffffffu || bH == 0xffffffffu)
-				atomicOr(&P.k->device_error, kErrQueueOverflow);
+				atomicOr(&PT.k->device_error, kErrQueueOverflow);
 			sh[12] = bT;
 			sh[13] = bH;
 			sh[18] = bK;
@@ -664,7 +881,7 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 			stage.sv_direct_ix[k] = make_float4(out.direct.x, out.direct.y, out.direct.z, __uint_as_float(pixelBits));
 			stage.sv_flags[k] = out.flags;
 			stage.sv_key[k] = vslot | kKeyIndirect; // next iteration's slot = rank of vslot among this iteration's survivors
-			if (P.foldSpheres)
+			if (PT.foldSpheres)
 				stage.sv_hit[k] = out.hitRec;
 		}
 		if (out.shadow) {
@@ -697,7 +914,7 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 	}
 	uint32_t myResolved = 0;
 	if (PE.resolveShadows || PE.retireGhosts) { // (block-uniform)
-		if (lane == 0) {
+		if (!DENSE && lane == 0) {
 			sh[20 + wave] = waveResolved;
 			sh[24 + wave] = waveVisible;
 			sh[28 + wave] = waveGhosts;
@@ -718,6 +935,12 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 		for (int i = 0; i < 6; ++i)
 			atomicAdd(&PE.k->debug[i], tacc_[i]);
 		atomicAdd(&PE.k->debug[7], ntiles_);
+	}
+#endif
+#ifdef TYR_SHADE_CENSUS
+	if (DENSE && lane == 0 && PE.censusOn) {
+		for (int i = 0; i < 12; ++i)
+			atomicAdd(&PE.k->debug[i], (unsigned long long)census_[i]);
 	}
 #endif
 	if (tid == 0) {
@@ -794,30 +1017,53 @@ __global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const
 #undef TYR_STAMP
 }
 
+template <bool LIGHTS>
+__global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const FrameParams P_) {
+	shade_tiles<LIGHTS, false>(P_);
+}
+// TYR_TUNE_SHADE_DENSE (FrameParams::shadeDense): the dense path, k_shade<false, true>.  A second function template of the same
+// name, not a defaulted parameter of the first: tests/test_kernel_resources.py finds the lane path's kernels by their mangled names
+// (k_shadeILb0EEE, k_shadeILb1EEE), which a second parameter would change, and the bench's counter passes and the tools take
+// the rows that start with "k_shade<" for the shade launches -- so the name stays and the lane path keeps its symbols.
+// k_shade<L> can only mean the template above (DENSE is not deducible); k_shade<L, false> does not exist.
+// There is no dense kernel with LIGHTS: the emitter pick's nested branches keep two more lane masks alive through the lane
+// phase, and beside the dense phase's constants the compiler spilled them to vector lanes (four scalar values).  The
+// kernel's rule is no spill at all, so a ctx with TYR_FLAG_LIGHT_LIST runs the lane path whatever the key says.
+template <bool LIGHTS, bool DENSE>
+__global__ void __launch_bounds__(kBlock, TYR_SHADE_BLOCKS_PER_CU) k_shade(const FrameParams P_) {
+	static_assert(DENSE && !LIGHTS, "the lane path is k_shade<LIGHTS>; the dense path has no light-list form");
+	shade_tiles<false, true>(P_);
+}
+
+using ShadeKernel = void (*)(const FrameParams);
+static ShadeKernel shade_kernel(bool lights, bool dense) {
+	if (lights)
+		return k_shade<true>;
+	return dense ? k_shade<false, true> : k_shade<false>;
+}
+
 // blocks of a shade launch over (at most) maxSlots physical slots
 uint32_t shade_grid(const FrameParams& P, uint32_t maxSlots, int numCUs, LaunchCache& lc) {
 	const uint32_t nTiles = blocks_for(maxSlots); // an upper bound is fine: the kernel takes the tile count from the device
 	// A persistent grid: as many blocks as stay resident (more would only wait for a slot and then find no tile
 	// left; the tile tickets make any grid size safe).  Asked once: the occupancy query is a slow host call.
 	const bool lights = (P.flags & TYR_FLAG_LIGHT_LIST) != 0; // its own instantiation: the default kernel keeps its registers
-	int* perCU = lc.perCU[kLcShade]; // [0] default kernel, [1] the light-list instantiation
-	if (perCU[lights] == 0) {
+	int* perCU = lc.perCU[kLcShade]; // [0] default kernel, [1] the light-list instantiation, [2] the dense path
+	const uint32_t which = lights ? 1u : (P.shadeDense != 0u ? 2u : 0u);
+	if (perCU[which] == 0) {
 		int q = 0;
-		const hipError_t e = lights ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, k_shade<true>, kBlock, 0) : hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, k_shade<false>, kBlock, 0);
+		const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&q, shade_kernel(lights, P.shadeDense != 0u), kBlock, 0);
 		if (e != hipSuccess || q < 1)
 			q = 2;
-		perCU[lights] = q > 6 ? 6 : q;
+		perCU[which] = q > 6 ? 6 : q;
 	}
-	const uint32_t resident = (uint32_t)perCU[lights] * (uint32_t)numCUs;
+	const uint32_t resident = (uint32_t)perCU[which] * (uint32_t)numCUs;
 	return nTiles < resident ? (nTiles ? nTiles : 1u) : resident;
 }
 void launch_shade(const FrameParams& P0, uint32_t maxSlots, int numCUs, LaunchCache& lc, hipStream_t stream) {
 	FrameParams P = P0;
 	P.shadeBlocks = shade_grid(P, maxSlots, numCUs, lc);
-	if (P.flags & TYR_FLAG_LIGHT_LIST)
-		launch_in_stage((k_shade<true>), dim3(P.shadeBlocks), dim3(kBlock), stream, P);
-	else
-		launch_in_stage((k_shade<false>), dim3(P.shadeBlocks), dim3(kBlock), stream, P);
+	launch_in_stage(shade_kernel((P.flags & TYR_FLAG_LIGHT_LIST) != 0, P.shadeDense != 0u), dim3(P.shadeBlocks), dim3(kBlock), stream, P);
 }
 
 } // namespace tyr

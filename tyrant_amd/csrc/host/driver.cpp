@@ -137,6 +137,13 @@ FrameParams make_params(const tyr_ctx* c) {
 	P.survFlag = c->survFlag;
 	P.scanLive = &c->dK->n_live;
 	P.foldSpheres = 0u;
+	P.shadeDense = c->tuning.shadeDense ? 1u : 0u;
+#ifdef TYR_SHADE_CENSUS
+	{
+		const char* const it = std::getenv("TYR_CENSUS_ITER"); // the iteration (since tyr_create) whose shade launch is counted
+		P.censusOn = (it && static_cast<uint32_t>(std::atoi(it)) == c->iter) ? 1u : 0u;
+	}
+#endif
 	{
 		const int out = static_cast<int>(c->iter & 1u), prev = out ^ 1;
 		P.vPrev = tyr::VTable{ c->vWord[prev], c->vPre[prev], c->vBlk[prev] };

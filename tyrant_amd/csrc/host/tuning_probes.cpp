@@ -221,6 +221,7 @@ int tyr_set_tuning(tyr_ctx* c, int key, int value) {
 		{ TYR_TUNE_OVERLAP_TRACE_BLOCKS, 3, 5, &Tuning::overlapTraceBlocks },
 		{ TYR_TUNE_OVERLAP_MIN_NEW, 0, 0x7fffffff, &Tuning::overlapMinNew },
 		{ TYR_TUNE_WINDOW_INSET, 0, 1024, &Tuning::windowInset },
+		{ TYR_TUNE_SHADE_DENSE, 0, 1, &Tuning::shadeDense },
 	};
 	for (const Knob& k : knobs) {
 		if (k.key != key)
