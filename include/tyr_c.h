@@ -1018,9 +1018,10 @@ int tyr_query_box(tyr_ctx* ctx, uint32_t n, const float* lo /* n x 3 */, const f
  * TYR_QUERY_TRI_MAX, a flag other than TYR_QUERY_TRI_ANY and TYR_QUERY_TRI_SKIP_SHARED, or TYR_QUERY_TRI_ANY with
  * max_prims != 0; TYR_ERR_NO_SCENE: nothing uploaded.
  * Not part of it: the sphere table, the intersection segment of a pair, moving triangles (a moving sphere: tyr_query_sweep),
- * more than TYR_QUERY_TRI_MAX indices per query, an exact answer for triangles of zero area. */
+ * more than TYR_QUERY_TRI_MAX indices per query, an exact answer for triangles of zero area, how near a triangle that does not
+ * touch comes (tyr_query_tri_distance). */
 #define TYR_QUERY_TRI_ANY 4u          /* tyr_query_tri only: count is 0 or 1, max_prims must be 0, the walk may stop at the first member */
-#define TYR_QUERY_TRI_SKIP_SHARED 8u  /* tyr_query_tri only: a scene triangle with a corner equal to a corner of the query is no member */
+#define TYR_QUERY_TRI_SKIP_SHARED 8u  /* tyr_query_tri and tyr_query_tri_distance: a scene triangle with a corner equal to a corner of the query is no member / no candidate */
 #define TYR_QUERY_TRI_MAX 32
 typedef struct tyr_tri_out {
 	uint32_t* count;   /* n, required */
@@ -1090,7 +1091,7 @@ int tyr_query_tri(tyr_ctx* ctx, uint32_t n, const float* a /* n x 3 */, const fl
  * out->on_segment, out->on_triangle n x 3 (each may be NULL).
  * TYR_ERR_INVALID: ctx, p, q, out, out->dist2 or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
  * Not part of it: the sphere table (flags must be 0), an any-only mode, the k nearest, moving capsules (a moving sphere:
- * tyr_query_sweep), signed distance (of points: tyr_query_signed). */
+ * tyr_query_sweep), signed distance (of points: tyr_query_signed), a triangle instead of a segment (tyr_query_tri_distance). */
 typedef struct tyr_segment_out {
 	float*   dist2;       /* n, required */
 	int32_t* prim;        /* n, required: build-order index, -1 = none */
@@ -1102,6 +1103,97 @@ typedef struct tyr_segment_out {
 } tyr_segment_out;
 int tyr_query_segment(tyr_ctx* ctx, uint32_t n, const float* p /* n x 3 */, const float* q /* n x 3 */, const float* max_dist /* n or NULL */,
                       uint32_t flags /* must be 0 */, const tyr_segment_out* out, void* stream);
+
+/* ---- closest-triangle queries (extension) ----------------------------------------------------------------------------------
+ * "How near does this triangle come to the mesh, where, and to which triangle?" for a caller's batch of triangles (corners a,
+ * b, c), against the scene the ctx holds: cloth against a body and against itself within a thickness (max_dist = thickness,
+ * TYR_QUERY_TRI_SKIP_SHARED for the mesh's own triangles), the clearance between two parts, the least distance between two
+ * meshes as a min over the answers.  tyr_query_tri reports only contact; tyr_query_nearest on the three corners and
+ * tyr_query_segment on the three edges both miss a mesh vertex that faces the query's interior, and the latter also a mesh edge
+ * that pierces the interior without touching the rim.  The contract is an argmin over all triangles of the uploaded array with
+ * no traversal order in it.
+ *
+ * Arithmetic, corners and conventions are the "Closest-segment queries" block's: all arithmetic is binary64, one IEEE operation
+ * per operation written, nothing contracted, divisions correctly rounded; dot, cross, vector - and clamp01 as there; a
+ * comparison with a NaN is false.  Scene corners: A = vert, B = the BINARY32 sum vert + e1, C = the binary32 sum vert + e2, all
+ * widened.  Query corners: P0, P1, P2 = a, b, c widened.  A query is valid when all nine components are finite; a triangle of
+ * zero area (a segment, a point) is valid.
+ *
+ * Shared operands, each computed once as written:
+ *   scene edges   G0 = A -> B, G1 = A -> C, G2 = B -> C with vectors g0 = B - A, g1 = C - A, g2 = C - B;   n = cross(g0, g1), nn = dot(n, n)
+ *   query edges   E0 = P0 -> P1, E1 = P1 -> P2, E2 = P2 -> P0 with vectors d0 = P1 - P0, d1 = P2 - P1, d2 = P0 - P2
+ *   the query as a triangle: (P0, u1, u2) with u1 = P1 - P0 (= d0), u2 = P2 - P0;   m = cross(u1, u2), mm = dot(m, m)
+ *   ap_j = P_j - A (j = 0, 1, 2);   bp_j = P_j - B;   vp_0 = A - P0, vp_1 = B - P0, vp_2 = C - P0
+ *
+ * Value of a (query, scene triangle) pair.  21 candidates are offered in the order of their codes; a candidate replaces the one
+ * held only when its F is strictly smaller (the first one offered is held), so of equal F the lower code stays.  Each gives F,
+ * the squared distance, x, a point of the query, y, a point of the scene triangle, and a region of y numbered as
+ * tyr_query_nearest's (0 face, 1 2 3 = A B C, 4 5 6 = the edges G0 G1 G2).
+ *   codes 0, 1, 2: the query edge E_j (from S = P_j, vector d = d_j, to P_j' with j' = (j + 1) mod 3) crosses the scene triangle:
+ *     h0 = dot(n, ap_j),  h1 = dot(n, ap_j')
+ *     conditions: nn > 0, h0 != h1, and (h0 <= 0 and h1 >= 0) or (h0 >= 0 and h1 <= 0)
+ *     s = h0 / (h0 - h1),  x_k = S_k + s*d_k,  w = x - A,  bv = dot(cross(w, g1), n),  bw = dot(cross(g0, w), n)
+ *     conditions: bv >= 0, bw >= 0, bv + bw <= nn;   F = 0, y = x, region 0
+ *   codes 3, 4, 5: the scene edge G_j (from S = A, A, B with vector d = g_j) crosses the query triangle (P0, u1, u2):
+ *     h0 = dot(m, vp_i0),  h1 = dot(m, vp_i1)   with (i0, i1) = (0, 1), (0, 2), (1, 2): the edge's two ends relative to P0
+ *     conditions: mm > 0, h0 != h1, and (h0 <= 0 and h1 >= 0) or (h0 >= 0 and h1 <= 0)
+ *     s = h0 / (h0 - h1),  y_k = S_k + s*d_k,  w = y - P0,  bv = dot(cross(w, u2), m),  bw = dot(cross(u1, w), m)
+ *     conditions: bv >= 0, bw >= 0, bv + bw <= mm;   F = 0, x = y, region = the edge's code 4, 5, 6
+ *   codes 6, 7, 8: the query corner P_j against the scene triangle: the "Closest-point queries" block's rules, clamp, q and c in
+ *     binary64 with vert, e1, e2 := A, g0, g1 and ap := ap_j (so bp = ap_j - g0, cp = ap_j - g1, d1 = dot(g0, ap_j), ...,
+ *     c_k = (A_k + g0_k*u2) + g1_k*v2), as features 1 and 2 of the segment block;   F = dot(q, q), x = P_j as given, y = c,
+ *     region = that block's region
+ *   codes 9, 10, 11: the scene corner V = A, B, C against the query triangle: the same rules with vert, e1, e2 := P0, u1, u2 and
+ *     ap := vp_j (so bp = vp_j - u1, cp = vp_j - u2, d1 = dot(u1, vp_j), d2 = dot(u2, vp_j), d3 = dot(u1, bp), d4 = dot(u2, bp),
+ *     d5 = dot(u1, cp), d6 = dot(u2, cp), q_k = (vp_j_k - u1_k*u2') - u2_k*v2' and c_k = (P0_k + u1_k*u2') + u2_k*v2' for the
+ *     clamped u2', v2' of the rule);   F = dot(q, q), x = c, y = V as widened, region = the corner's vertex code 1, 2, 3
+ *   codes 12 + 3*i + j: the edge pair (E_i, G_j), i = 0, 1, 2 outer, j = 0, 1, 2 inner: the segment block's edge rule with the
+ *     segment := E_i (P0 := P_i, d := d_i, a = dot(d_i, d_i)) and the edge Q0 -> Q1 := G_j (e = g_j, r = P_i - Q0: ap_i for G0 and
+ *     G1, bp_i for G2);   x_k = P_i_k + s*d_i_k,  y_k = Q0_k + e_k*t,  F = dot(x - y, x - y), region as there
+ * Why 21 suffice: two disjoint triangles attain their least distance at a vertex of one and a point of the other (6-11) or at a
+ * pair of edges (12-20); two triangles that meet have an edge of one crossing the other (0-5) or meet in their edges or with a
+ * corner inside the other (12-20, 6-11, with F = 0 up to rounding).  Every candidate is the squared distance of a point of the
+ * query and a point of the scene triangle, so no candidate is below the distance.
+ * Zero area: a query of zero area has mm == 0, which rules out 3-5; codes 0-2, 6-8 and 12-20 measure the segment or the point
+ * it is, and 9-11 the distance to some point of it.  A scene triangle of zero area has nn == 0, which rules out 0-2, and the rest
+ * measure the segment or point it is, as in the segment block.  a == b == c is the point's distance by these binary64 rules; it is
+ * not promised to be tyr_query_segment's for p == q to the last bit, because codes 9-11 add the corners' own distances
+ * dot(V - P0, V - P0), which the segment block reaches only through its clamped edge parameters (on the test families the two
+ * agree bit for bit).
+ * The value is not symmetric under exchanging the two triangles: the order of the candidates and of the operands is not.
+ * On the test families sqrt(F) is within 1e-11 units of a binary64 truth (a nested ternary search of the point distance over
+ * the query; DESIGN.md "Closest-triangle queries" has the table).
+ *
+ * Answer per query: F32_i = (float)F_i.  bound2 = max_dist * max_dist in binary32 (one multiplication), +inf when max_dist is
+ * NULL.  Over all triangles i of the uploaded array the winner is the smallest pair (F32_i, i) in lexicographic order among
+ * those with F32_i < bound2 (strictly): of bit-equal values the lowest build-order index wins.  With TYR_QUERY_TRI_SKIP_SHARED a
+ * scene triangle that shares a corner with the query -- rule 0 of "Triangle-overlap queries": some P_i equals some of A, B, C as
+ * binary32 values on all three components (==, so -0 equals +0) -- is no candidate.
+ *   a winner:  dist2 = F32, prim = i, feature = the code that decided, region, on_query = x, on_triangle = y, each rounded to
+ *              binary32 once
+ *   none:      dist2 = bound2, prim = -1, feature = region = 0, on_query = on_triangle = a as given
+ *   invalid:   dist2 = +inf, otherwise as "none".  A query is invalid when a, b or c has a NaN or infinite component, or when
+ *              its max_dist is NaN or negative.
+ * A scene without triangles answers every valid query with "none".
+ *
+ * Scope of the guarantee, arrays (DEVICE pointers, contiguous, float32 / int32 / uint8, indexed with 64-bit offsets), n up to
+ * 2^31 - 1 and n == 0, streams, the device, "touches no render state", tyr_scene_refit and bit 1 of tyr_query_error are
+ * tyr_query_segment's: a, b, c n x 3; max_dist n or NULL; out->dist2, out->prim n (required); out->feature, out->region n,
+ * out->on_query, out->on_triangle n x 3 (each may be NULL).
+ * TYR_ERR_INVALID: ctx, a, b, c, out, out->dist2 or out->prim NULL, n >= 2^31, or a flag other than TYR_QUERY_TRI_SKIP_SHARED;
+ * TYR_ERR_NO_SCENE: nothing uploaded.
+ * Not part of it: the sphere table, the k nearest, an any-only mode (tyr_query_tri is that at distance 0), moving triangles,
+ * penetration depth, symmetry of the value under exchanging the two triangles. */
+typedef struct tyr_tri_distance_out {
+	float*   dist2;        /* n, required */
+	int32_t* prim;         /* n, required: build-order index, -1 = none */
+	uint8_t* feature;      /* n or NULL: the candidate code 0..20 that decided -- 0-2 a query edge crosses, 3-5 a scene edge crosses, 6-8 a query corner, 9-11 a scene corner, 12-20 an edge pair */
+	uint8_t* region;       /* n or NULL: of on_triangle -- 0 face, 1 2 3 vertices, 4 5 6 edges, numbered as tyr_query_nearest's */
+	float*   on_query;     /* n x 3 or NULL: the point of the caller's triangle */
+	float*   on_triangle;  /* n x 3 or NULL: the point of the scene triangle */
+} tyr_tri_distance_out;
+int tyr_query_tri_distance(tyr_ctx* ctx, uint32_t n, const float* a /* n x 3 */, const float* b /* n x 3 */, const float* c /* n x 3 */,
+                           const float* max_dist /* n or NULL */, uint32_t flags, const tyr_tri_distance_out* out, void* stream);
 
 /* ---- signed-distance queries and the SDF grid bake (extension) -------------------------------------------------------------
  * How far a point is from the mesh and on which side: tyr_query_signed for the caller's points, tyr_bake_sdf for the voxel

@@ -35,7 +35,7 @@ TYR_QUERY_HITS_MAX = 32
 TYR_QUERY_BOX_ANY = 4  # tyr_query_box only
 TYR_QUERY_BOX_MAX = 32
 TYR_QUERY_TRI_ANY = 4  # tyr_query_tri only
-TYR_QUERY_TRI_SKIP_SHARED = 8  # tyr_query_tri only
+TYR_QUERY_TRI_SKIP_SHARED = 8  # tyr_query_tri and tyr_query_tri_distance
 TYR_QUERY_TRI_MAX = 32
 TYR_QUERY_NEAREST_K_MAX = 32
 TYR_QUERY_OCCLUSION_MAX_SAMPLES = 1024
@@ -166,6 +166,12 @@ class SegmentOut(C.Structure):
     """tyr_segment_out: device pointers of tyr_query_segment's outputs; s, feature, region, on_segment, on_triangle may be NULL"""
 
     _fields_ = [("dist2", P), ("prim", P), ("s", P), ("feature", P), ("region", P), ("on_segment", P), ("on_triangle", P)]
+
+
+class TriDistanceOut(C.Structure):
+    """tyr_tri_distance_out: device pointers of tyr_query_tri_distance's outputs; feature, region, on_query, on_triangle may be NULL"""
+
+    _fields_ = [("dist2", P), ("prim", P), ("feature", P), ("region", P), ("on_query", P), ("on_triangle", P)]
 
 
 class SignedOut(C.Structure):
@@ -349,6 +355,7 @@ SYMBOLS = {
     "tyr_query_box": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_tri": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_segment": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
+    "tyr_query_tri_distance": (C.c_int, [P, c_u32, P, P, P, P, c_u32, P, P]),
     "tyr_query_hits": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_occlusion": (C.c_int, [P, c_u32, P, P, P, c_u32, C.c_float, c_u32, c_u32, P, P]),
     "tyr_query_winding": (C.c_int, [P, c_u32, P, C.c_float, P, P, P]),
@@ -843,6 +850,29 @@ class Renderer:
         out = SegmentOut(*_dptrs(*outs))
         self._query_call("tyr_query_segment", stream, staged, n, *_dptrs(a, b, md), 0, C.byref(out))
         return tuple(outs)
+
+    def query_tri_distance(self, a, b, c, max_dist=None, skip_shared=False, feature=False, region=False, points=False, stream=None):
+        """tyr_query_tri_distance: for every triangle (a, b, c) the triangle of the uploaded scene that comes nearest to it
+        (include/tyr_c.h "Closest-triangle queries").  a, b, c: (N, 3) float32, max_dist: a number, (N,) or None -- torch tensors on
+        this ctx's device, taken as they are, or numpy arrays.  skip_shared: a scene triangle with a corner equal to one of the
+        query's is no candidate (the mesh's own triangles as queries: self-proximity).  Returns torch tensors (dist2, prim), and
+        behind them those asked for, in this order: feature, region, on_query and on_triangle (points=True: both).  Without a
+        triangle nearer than max_dist, dist2 = max_dist^2 (+inf for an invalid query or max_dist), prim = -1, feature = region = 0
+        and both points = a."""
+        import torch
+
+        ins = (("a", a, (3,)), ("b", b, (3,)), ("c", c, (3,)))
+        if isinstance(max_dist, (int, float, np.floating, np.integer)):
+            n, (ta, tb, tc), staged = self._query_inputs(*ins)
+            md = torch.full((max(n, 0),), float(max_dist), dtype=torch.float32, device=ta.device)
+            staged = True  # filled on torch's current stream: `stream` has to wait for it like for a copied numpy input
+        else:
+            n, (ta, tb, tc, md), staged = self._query_inputs(*ins, ("max_dist", max_dist, ()), optional=("max_dist",))
+        vec, byte = ((3,), torch.float32), ((), torch.uint8)
+        outs = self._query_outputs(n, ((), torch.float32), ((), torch.int32), byte if feature else None, byte if region else None, vec if points else None, vec if points else None)
+        out = TriDistanceOut(*_dptrs(*outs))
+        self._query_call("tyr_query_tri_distance", stream, staged, n, *_dptrs(ta, tb, tc, md), TYR_QUERY_TRI_SKIP_SHARED if skip_shared else 0, C.byref(out))
+        return tuple(x for x in outs if x is not None)
 
     def query_box(self, lo, hi, max_prims=0, any=False, stream=None):
         """tyr_query_box: for every axis-aligned box [lo, hi] the triangles of the uploaded scene it touches (include/tyr_c.h
