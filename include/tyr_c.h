@@ -877,7 +877,7 @@ int tyr_scene_moments(tyr_ctx* ctx, int32_t first, int32_t count, double* host_o
  * out->normal n x 3 (each may be NULL).
  * TYR_ERR_INVALID: ctx, origins, directions, radius, out, out->t or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE:
  * nothing uploaded.
- * Not part of it: the sphere table (flags must be 0), moving capsules and moving boxes (a capsule at rest: tyr_query_segment; a box at rest: tyr_query_box), all contacts rather than the first, rotating or
+ * Not part of it: the sphere table (flags must be 0), moving boxes (a moving capsule: tyr_query_sweep_capsule below; a capsule at rest: tyr_query_segment; a box at rest: tyr_query_box), all contacts rather than the first, rotating or
  * deforming bodies, triangles that move during the sweep, penetration depth beyond what `normal` carries. */
 typedef struct tyr_sweep_out {
 	float*   t;       /* n, required */
@@ -890,6 +890,84 @@ typedef struct tyr_sweep_out {
 int tyr_query_sweep(tyr_ctx* ctx, uint32_t n, const float* origins, const float* directions, const float* radius /* n */,
                     const float* tmax /* n, or NULL: 1 = the whole displacement d */, uint32_t flags /* must be 0 */,
                     const tyr_sweep_out* out, void* stream);
+
+/* ---- swept-capsule queries (extension) -------------------------------------------------------------------------------------
+ * "A capsule of radius r around the axis p -> q moves along d: when does it first touch the mesh, where, and on which
+ * triangle?" for a caller's batch of capsules, against the scene the ctx holds -- the capsule cast of character controllers,
+ * struts, limbs, cables and thick edges in continuous collision.  Sphere sweeps at samples along the axis slip past mesh
+ * vertices and edges that lie between the samples, and tyr_query_segment with max_dist = r at the start misses what the capsule
+ * meets on the way.  The contract is an argmin over all triangles of the uploaded array with no traversal order in it.
+ *
+ * Arithmetic, inputs, triangle corners (A, B, C, e1' = B - A, e2' = C - A) and conventions are the "Swept-sphere queries" block's:
+ * all arithmetic is binary64, one IEEE operation per operation written, nothing contracted, divisions and square roots correctly
+ * rounded; inputs (triangle records, p, q, d, r, tmax) are binary32 widened exactly; a comparison with a NaN is false.
+ * a = q - p (per component); -a is its negation; e3' = C - B;  A- = A - a, B- = B - a, C- = C - a (per component);  o := p,
+ * rr = r*r, dd = dot(d, d).  A capsule is everything within r of the axis p -> q; both ends move by t*d for t in [0, tmax].
+ *
+ * Value of a (capsule, triangle) pair.
+ *  1. Initial overlap.  The "Closest-segment queries" block's pair value (F, s, y, region) with P0 = p, P1 = q.  When F <= rr:
+ *     t = 0, s = its s, point = its y, region = its region, feature = 0.
+ *  2. Otherwise.  The capsule touches the triangle T at t exactly when the sphere of radius r centred at p + t*d touches the
+ *     prism M = { x - sigma*a : x in T, sigma in [0, 1] }.  M is convex; its boundary lies in two cap triangles and three side
+ *     parallelograms, each a subset of M, so the least candidate over the pieces (faces, their vertices, their edges) is the
+ *     first contact -- also when a lies in the triangle's plane or along an edge, where pieces degenerate.  Twenty candidates
+ *     are offered in the order of their feature codes; a candidate is taken when its conditions hold, 0 <= t <= tmax and t < the
+ *     t taken so far (strict: of equal t the lower feature code stays).  Each is the "Swept-sphere queries" block's formula of
+ *     its kind with that block's o := p, and the operands named here in place of that block's:
+ *     a face with the origin O and the edges f1, f2 (that block's face with A := O, e1' := f1, e2' := f2, ap := o - O):
+ *       n = cross(f1, f2),  nn, ln, h = dot(n, o - O), s_, sdn, ah, rl, t, k, q, w = q - O, bv = dot(cross(w, f2), n),
+ *       bw = dot(cross(f1, w), n) as there;  conditions: nn > 0, sdn < 0, ah > rl, bv >= 0, bw >= 0 and the containment below
+ *         feature 0: O = A,  f1 = e1', f2 = e2', containment bv + bw <= nn;   s = 0, point = q, region 0
+ *         feature 1: O = A-, f1 = e1', f2 = e2', containment bv + bw <= nn;   s = 1, point_k = q_k + a_k, region 0
+ *         features 2, 3, 4: (O, f1) = (A, e1'), (A, e2'), (B, e3'), f2 = -a, containment bv <= nn and bw <= nn;
+ *                    u = bv / nn, v = bw / nn;   s = v, point_k = O_k + f1_k*u, region 4 / 5 / 6
+ *     a vertex P (that block's vertex with m = o - P):
+ *         features 5, 6, 7:  P = A, B, C;     s = 0, point = P, region 1 / 2 / 3
+ *         features 8, 9, 10: P = A-, B-, C-;  s = 1, point = A / B / C, region 1 / 2 / 3
+ *     an edge from P0 along e (that block's edge with m = o - P0; its P1 is not used):
+ *         features 11, 12, 13: (P0, e) = (A, e1'), (A, e2'), (B, e3');     s = 0, point_k = P0_k + e_k*sg, region 4 / 5 / 6
+ *         features 14, 15, 16: (P0, e) = (A-, e1'), (A-, e2'), (B-, e3');  s = 1, point_k = V_k + e_k*sg with V = A, A, B (the
+ *                    edge's start before it was moved), region 4 / 5 / 6
+ *         features 17, 18, 19: P0 = A, B, C, e = -a;     s = sg, point = P0, region 1 / 2 / 3
+ *     A zero-area cap or side face fails nn > 0, a zero-length edge fails ee > 0: p == q leaves the sphere's own candidates
+ *     (0, 5-7, 11-13; the moved copies tie and lose), r == 0 is a swept needle whose crossings of mesh edges the side faces
+ *     catch, d == 0 leaves only rule 1.
+ *  3. No candidate taken: the pair has no value.
+ *
+ * Answer per capsule: t32 = (float)t.  Over all triangles i of the uploaded array the winner is the smallest pair (t32_i, i) in
+ * lexicographic order: of bit-equal t32 the lowest build-order index wins.
+ *   a winner:  t = t32, prim = i, s, feature, region, point;  center_k = (p_k + s*a_k) + t*d_k with the binary64 s and t -- the
+ *              point of the moved axis that touches;  normal_k = (center_k - point_k) / r, or (0, 0, 0) when r == 0.  Each is
+ *              rounded to binary32 once.
+ *   none:      t = tmax as given (1 when tmax is NULL), prim = -1, s = 0, feature = region = 0, center = point = p_k + tmax*d_k,
+ *              normal = 0
+ *   invalid:   t = +inf, center = point = p as given, otherwise as "none".  A capsule is invalid when p, q or d has a NaN or
+ *              infinite component, or its radius or its tmax is NaN, negative or infinite.
+ * A scene without triangles answers every valid capsule with "none".  The value is within 4e-12 units of t of a
+ * sampled-and-bisected binary64 truth on the test families (DESIGN.md "Swept-capsule queries" has the table); hit or miss can
+ * differ from it only for a path that grazes: least clearance within rounding of r.
+ *
+ * Scope of the guarantee, arrays (DEVICE pointers, contiguous, indexed with 64-bit offsets), n up to 2^31 - 1 and n == 0,
+ * streams, the device, "touches no render state", tyr_scene_refit and bit 1 of tyr_query_error are tyr_query_sweep's: p, q,
+ * directions n x 3; radius n; tmax n or NULL; out->t, out->prim n (required); out->s, out->feature, out->region n, out->point,
+ * out->center, out->normal n x 3 (each may be NULL).
+ * TYR_ERR_INVALID: ctx, p, q, directions, radius, out, out->t or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE:
+ * nothing uploaded.
+ * Not part of it: the sphere table (flags must be 0), moving boxes, all contacts rather than the first, rotation of the axis
+ * during the sweep, triangles that move during the sweep. */
+typedef struct tyr_sweep_capsule_out {
+	float*   t;        /* n, required */
+	int32_t* prim;     /* n, required: build-order index, -1 = none */
+	float*   s;        /* n or NULL: where on the axis the contact is, 0 at p, 1 at q */
+	uint8_t* feature;  /* n or NULL: which candidate decided, 0..19 above; 0 at an initial overlap */
+	uint8_t* region;   /* n or NULL: of `point` on the triangle, numbered as tyr_query_nearest's */
+	float*   point;    /* n x 3 or NULL: the contact point on the triangle */
+	float*   center;   /* n x 3 or NULL: the axis point p + s*a + t*d that touches */
+	float*   normal;   /* n x 3 or NULL: (center - point) / r, 0 when r == 0 */
+} tyr_sweep_capsule_out;
+int tyr_query_sweep_capsule(tyr_ctx* ctx, uint32_t n, const float* p /* n x 3 */, const float* q /* n x 3 */, const float* directions /* n x 3 */,
+                            const float* radius /* n */, const float* tmax /* n, or NULL: 1 */, uint32_t flags /* must be 0 */,
+                            const tyr_sweep_capsule_out* out, void* stream);
 
 /* ---- box-overlap queries (extension) --------------------------------------------------------------------------------------
  * "Which triangles are in this box, and is there anything in it at all?" for a caller's batch of axis-aligned boxes [lo, hi],
@@ -1090,8 +1168,9 @@ int tyr_query_tri(tyr_ctx* ctx, uint32_t n, const float* a /* n x 3 */, const fl
  * tyr_query_nearest's: p, q n x 3; max_dist n or NULL; out->dist2, out->prim n (required); out->s, out->feature, out->region n,
  * out->on_segment, out->on_triangle n x 3 (each may be NULL).
  * TYR_ERR_INVALID: ctx, p, q, out, out->dist2 or out->prim NULL, n >= 2^31, or flags != 0; TYR_ERR_NO_SCENE: nothing uploaded.
- * Not part of it: the sphere table (flags must be 0), an any-only mode, the k nearest, moving capsules (a moving sphere:
- * tyr_query_sweep), signed distance (of points: tyr_query_signed), a triangle instead of a segment (tyr_query_tri_distance). */
+ * Not part of it: the sphere table (flags must be 0), an any-only mode, the k nearest, motion (a moving capsule:
+ * tyr_query_sweep_capsule, a moving sphere: tyr_query_sweep), signed distance (of points: tyr_query_signed), a triangle
+ * instead of a segment (tyr_query_tri_distance). */
 typedef struct tyr_segment_out {
 	float*   dist2;       /* n, required */
 	int32_t* prim;        /* n, required: build-order index, -1 = none */

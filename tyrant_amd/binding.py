@@ -150,6 +150,12 @@ class SweepOut(C.Structure):
     _fields_ = [("t", P), ("prim", P), ("region", P), ("point", P), ("center", P), ("normal", P)]
 
 
+class SweepCapsuleOut(C.Structure):
+    """tyr_sweep_capsule_out: device pointers of tyr_query_sweep_capsule's outputs; s, feature, region, point, center, normal may be NULL"""
+
+    _fields_ = [("t", P), ("prim", P), ("s", P), ("feature", P), ("region", P), ("point", P), ("center", P), ("normal", P)]
+
+
 class BoxOut(C.Structure):
     """tyr_box_out: device pointers of tyr_query_box's outputs; prim may be NULL when max_prims is 0"""
 
@@ -352,6 +358,7 @@ SYMBOLS = {
     "tyr_query_nearest": (C.c_int, [P, c_u32, P, P, c_u32, P, P]),
     "tyr_query_nearest_k": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_sweep": (C.c_int, [P, c_u32, P, P, P, P, c_u32, P, P]),
+    "tyr_query_sweep_capsule": (C.c_int, [P, c_u32, P, P, P, P, P, c_u32, P, P]),
     "tyr_query_box": (C.c_int, [P, c_u32, P, P, c_u32, c_u32, P, P]),
     "tyr_query_tri": (C.c_int, [P, c_u32, P, P, P, c_u32, c_u32, P, P]),
     "tyr_query_segment": (C.c_int, [P, c_u32, P, P, P, c_u32, P, P]),
@@ -830,6 +837,28 @@ class Renderer:
         out = SweepOut(*_dptrs(*outs))
         self._query_call("tyr_query_sweep", stream, staged, n, *_dptrs(o, d, r, tm), 0, C.byref(out))
         return tuple(outs) if normal else tuple(outs[:5])
+
+    def query_sweep_capsule(self, p, q, directions, radius, tmax=None, normal=False, stream=None):
+        """tyr_query_sweep_capsule: for every capsule of radius `radius` around the axis p -> q whose ends both move along
+        `directions`, the first contact with the uploaded scene (include/tyr_c.h "Swept-capsule queries").  p, q, directions:
+        (N, 3) float32, radius: a number or (N,), tmax: (N,) or None (1: the whole displacement) -- torch tensors on this ctx's
+        device, taken as they are, or numpy arrays.  Returns torch tensors (t, prim, s, feature, region, point, center), and normal
+        behind them with normal=True: s is where on the axis the contact is (0 at p, 1 at q), center that point of the moved axis;
+        without a contact t = tmax, prim = -1 and center = point = the end of p's path; an invalid capsule has t = +inf."""
+        import torch
+
+        n, (a, b, d, tm), staged = self._query_inputs(("p", p, (3,)), ("q", q, (3,)), ("directions", directions, (3,)), ("tmax", tmax, ()), optional=("tmax",))
+        if isinstance(radius, (int, float, np.floating, np.integer)):
+            r = torch.full((max(n, 0),), float(radius), dtype=torch.float32, device=a.device)
+            staged = True  # filled on torch's current stream: `stream` has to wait for it like for a copied numpy input
+        else:
+            staged = staged or not isinstance(radius, torch.Tensor)
+            r = self._query_take(radius, "radius", (n,))
+        vec, byte = ((3,), torch.float32), ((), torch.uint8)
+        outs = self._query_outputs(n, ((), torch.float32), ((), torch.int32), ((), torch.float32), byte, byte, vec, vec, vec if normal else None)
+        out = SweepCapsuleOut(*_dptrs(*outs))
+        self._query_call("tyr_query_sweep_capsule", stream, staged, n, *_dptrs(a, b, d, r, tm), 0, C.byref(out))
+        return tuple(outs) if normal else tuple(outs[:7])
 
     def query_segment(self, p, q, max_dist=None, stream=None):
         """tyr_query_segment: for every segment p -> q the triangle of the uploaded scene that comes nearest to it (include/tyr_c.h

@@ -240,7 +240,7 @@ constexpr int kBlock = 256; // 4 wave64 per workgroup
 
 // Per-context cache of the occupancy queries that size the persistent grids (a slow host call: asked once per
 // kernel, not once per launch).  Lives in tyr_ctx -- one ctx per device, no process-wide statics.
-enum { kLcShade = 0, kLcTrace, kLcQuery, kLcNearest, kLcHits, kLcNearestK, kLcOcclusion, kLcSweep, kLcBox, kLcTri, kLcSegment, kLcSigned, kLcTriDistance, kLcKinds }; // kLcQuery: [any * 2 + spheres] (hip/query.hip), [4] the AOV pass, [5] its specular-chain variant (hip/aov.hip); kLcNearest: [0] (hip/nearest.hip); kLcHits: [two-sided] (hip/hits.hip); kLcNearestK: [with a count] (hip/nearest_k.hip); kLcOcclusion: [spheres] (hip/occlusion.hip); kLcSweep: [0] (hip/sweep.hip); kLcBox: [any] (hip/box.hip); kLcTri: [any] (hip/tri.hip); kLcSegment: [0] (hip/segment.hip); kLcSigned: [0] points, [1] the bake's bricks, [2] its voxels (hip/signed.hip); kLcTriDistance: [0] (hip/tri_distance.hip)
+enum { kLcShade = 0, kLcTrace, kLcQuery, kLcNearest, kLcHits, kLcNearestK, kLcOcclusion, kLcSweep, kLcBox, kLcTri, kLcSegment, kLcSigned, kLcTriDistance, kLcSweepCapsule, kLcKinds }; // kLcQuery: [any * 2 + spheres] (hip/query.hip), [4] the AOV pass, [5] its specular-chain variant (hip/aov.hip); kLcNearest: [0] (hip/nearest.hip); kLcHits: [two-sided] (hip/hits.hip); kLcNearestK: [with a count] (hip/nearest_k.hip); kLcOcclusion: [spheres] (hip/occlusion.hip); kLcSweep: [0] (hip/sweep.hip); kLcBox: [any] (hip/box.hip); kLcTri: [any] (hip/tri.hip); kLcSegment: [0] (hip/segment.hip); kLcSigned: [0] points, [1] the bake's bricks, [2] its voxels (hip/signed.hip); kLcTriDistance: [0] (hip/tri_distance.hip); kLcSweepCapsule: [0] (hip/sweep_capsule.hip)
 struct LaunchCache {
 	int perCU[kLcKinds][6] = {};
 };
